@@ -20,8 +20,16 @@ its own `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-
 under torchrun / the driver's launcher it is one rank.  Fewer visible devices than ranks is an error (exit 2) — unless
 VPT_BENCH_DEVICE pins every rank to one device, the 1-GPU-box test hook (the gather then goes through host memory).
 
-After the timed region the same workload runs a few more steps with profiling ON (HIP events the library records
-around every launch on its own stream) and with traversal counters, which feed
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, the K
+timed steps, `--dump-outputs DIR` if given, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, ...).
+`--dump-outputs DIR` writes, on rank 0 after the timed region, what the timed path handed its caller after the last step: the
+accumulated radiance image (DIR/radiance.npy, float32 H x W x 4) and, for the workloads with post, the RGBA8 image of the last
+post-process (DIR/postprocessed.npy, as float32).  Inputs are fixed by the arguments (scene, seed, frame counts), so two builds
+run with the same arguments can be compared output for output.  Above 64 MB in all, every array keeps the same fixed, seeded
+sample of pixels, and DIR/pixel_index.npy (float64) says which.
+
+Everything else is behind `--full` (off by default): after the timed region the same workload runs a few more steps with
+profiling ON (HIP events the library records around every launch on its own stream) and with traversal counters, which feed
 
   roofline     — for the kernel with the largest share of GPU time (the headline's is the whole-path launch k_whole,
                  timed under "primary"): `bound` says what limits it ("valu" for the Cornell kernels: VALU issue
@@ -40,6 +48,8 @@ around every launch on its own stream) and with traversal counters, which feed
                  every workload runs sharded over all ranks, once weak (per-rank batch fixed) and once strong (job fixed).
   cpu_baseline — the CPU oracle (oracle/, a port of the reference shaders; the reference has no CPU path) on this
                  box's host cores, on a bounded sample of the headline workload.
+  latency      — the reference's one-frame-per-call pattern (frame_latency), at N = 1.
+The --no-* options switch single blocks of a --full run off.
 """
 import argparse
 import importlib
@@ -93,6 +103,8 @@ def parse():
     ap.add_argument("--steps", type=int, default=8)   # weak: 8 batches of 226 frames = 1808 samples per pixel (covers config 2's 1024 spp); strong: 8 x 129 frames = its 1032-spp job
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cornell_1080p_d8", choices=sorted(WORKLOADS), help="headline workload (the default is BASELINE's metric config)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also the profiled pass + roofline (live rocprofv3 --pmc passes), latency, the extra workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0, float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-workloads", action="store_true", help="skip the atrium / atrium 4K / glass-bust blocks")
     ap.add_argument("--extra-steps", type=int, default=4, help="timed steps of each extra workload (a step of a regenerating context is a batch of 4 x 226 frames at 1080p)")
@@ -271,7 +283,27 @@ class Ranks:
         return [float(x) for x in t.tolist()]
 
 
-def timed_run(vpt, sharding, R, name, scene, pipeline, frames_in_flight, steps, warmup, scaling):
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this many bytes of .npy files in all
+
+
+def write_outputs(out_dir, images, budget=DUMP_BYTES):
+    """images: name -> H x W x C array.  Written as DIR/<name>.npy in float32; when they exceed `budget` together, each keeps the same
+    fixed, seeded sample of pixels (n x C, in pixel order) and DIR/pixel_index.npy (float64, y * W + x) names them."""
+    import numpy as np
+    images = {k: np.ascontiguousarray(v, np.float32) for k, v in images.items()}
+    h, w = next(iter(images.values())).shape[:2]
+    if sum(a.nbytes for a in images.values()) > budget:
+        per_pixel = sum(a.nbytes for a in images.values()) // (h * w) + 8     # + the float64 index
+        keep = (budget - 4096) // per_pixel                                    # (4096: the .npy headers)
+        idx = np.sort(np.random.default_rng(BASE_SEED).choice(h * w, keep, replace=False))
+        images = {k: a.reshape(h * w, -1)[idx] for k, a in images.items()}
+        images["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in images.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def timed_run(vpt, sharding, R, name, scene, pipeline, frames_in_flight, steps, warmup, scaling, dump_dir=None):
     """One workload on all ranks: W warm-up steps, then the timed region — barrier + sync, `steps` batches per rank (weak) or the fixed job
     split over the ranks (strong), the library's one gather of the row shards (N > 1), bloom + tonemap on the root for the workloads
     that have post, barrier + sync — and the max over ranks of its wall time.  Rows y % N == rank (RayGen.slang:16-25 along one axis)."""
@@ -307,6 +339,11 @@ def timed_run(vpt, sharding, R, name, scene, pipeline, frames_in_flight, steps, 
     R.sync()
     dt = R.max(time.perf_counter() - t0)
     st = pt.stats()
+    if dump_dir and R.rank == 0:   # after the gather the root holds the whole image
+        images = {"radiance": pt.radiance()}
+        if wl["post"]:
+            images["postprocessed"] = pt.output_to_host()
+        write_outputs(dump_dir, images)
     samples, closest, shadow = R.sums([st["samples"], st["closest_rays"], st["shadow_rays"]])
     rccl = None
     if comm:   # what RCCL itself says about the communicator the gather ran on (vpt_comm_get_info); host-staged: versions only
@@ -570,16 +607,12 @@ def main():
     scene = load_scene(vpt, name)
     params = vpt.default_params(max_depth=wl["depth"], base_seed=BASE_SEED, max_samples=0x7fffffff)
 
-    head = timed_run(vpt, sharding, R, name, scene, args.pipeline, args.frames_in_flight, args.steps, args.warmup, args.scaling)
+    head = timed_run(vpt, sharding, R, name, scene, args.pipeline, args.frames_in_flight, args.steps, args.warmup, args.scaling, dump_dir=args.dump_outputs)
     if args.pmc_child:
         return
 
     line = None
     if rank == 0:
-        prof = kernel_profile(vpt, name, scene, local_rank, rank, world, args.pipeline, args.frames_in_flight, 4)
-        live = None
-        if world == 1 and not args.no_live_pmc:   # the dominant kernel's counters, measured here and now (three short child runs of this script under rocprofv3 --pmc)
-            live = live_pmc(name, max(prof["kernels"], key=lambda k: prof["kernels"][k]["share"]), args.pipeline, args.frames_in_flight, steps=4)   # (1 + 4 launches of the whole-path kernel per pass)
         line = {
             "metric": "Msamples/s at %dx%d" % (wl["w"], wl["h"]), "value": head["value"], "unit": "Msamples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
@@ -590,18 +623,25 @@ def main():
                        "timed_samples_per_pixel": head["timed_samples_per_pixel"],
                        "note": "a rate metric: the timed region renders steps x frames_per_step frames (timed_samples_per_pixel; config 2 asks for 1024 spp, which the default 8 steps cover); bit-exact full-size runs: profiles/*_config*_full_parity.json",
                        "batches_per_gpu": head["batches_per_gpu"], "post_in_timed_region": wl["post"],
-                       "partition": "rows y % N == rank, one ncclGather at the end", "base_seed": BASE_SEED, "pipeline": prof["pipeline"]},
+                       "partition": "rows y % N == rank, one ncclGather at the end", "base_seed": BASE_SEED},
             "mrays_per_s": head["mrays_per_s"],
             "set_scene": {"wall_s": head["set_scene_s"], "bvh_build_ms": head["bvh_build_ms"], "set_scene_ms": head["set_scene_ms"]},
-            "roofline": roofline_for(name, prof, live),
         }
         if "post_ms_in_timed_region" in head:
             line["post_ms_in_timed_region"] = head["post_ms_in_timed_region"]
         if "rccl" in head:
             line["rccl"] = head["rccl"]
+    # a plain run ends here: everything below measures beyond the headline and runs with --full only
+    if args.full and rank == 0:
+        prof = kernel_profile(vpt, name, scene, local_rank, rank, world, args.pipeline, args.frames_in_flight, 4)
+        live = None
+        if world == 1 and not args.no_live_pmc:   # the dominant kernel's counters, measured here and now (three short child runs of this script under rocprofv3 --pmc)
+            live = live_pmc(name, max(prof["kernels"], key=lambda k: prof["kernels"][k]["share"]), args.pipeline, args.frames_in_flight, steps=4)   # (1 + 4 launches of the whole-path kernel per pass)
+        line["config"]["pipeline"] = prof["pipeline"]
+        line["roofline"] = roofline_for(name, prof, live)
         if world == 1 and not args.no_latency and name == "cornell_1080p_d8":
             line["latency"] = frame_latency(vpt, name, scene, params, local_rank)
-    if not args.no_extra_workloads:   # every rank takes part: the extra workloads run sharded like the headline one
+    if args.full and not args.no_extra_workloads:   # every rank takes part: the extra workloads run sharded like the headline one
         extra = {}
         for other in EXTRA_WORKLOADS:
             if other == name:
@@ -628,7 +668,7 @@ def main():
         if rank == 0:
             line["workloads"] = extra
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(vpt, name, scene, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:

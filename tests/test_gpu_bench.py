@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +21,7 @@ def run_bench(args, extra_env=None, timeout=600):
     return r, (json.loads(lines[-1]) if lines else None)
 
 
-QUICK = ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extra-workloads", "--no-latency", "--no-live-pmc", "--frames-in-flight", "2"]
+QUICK = ["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extra-workloads", "--no-latency", "--no-live-pmc", "--frames-in-flight", "2"]
 
 
 def test_gpus_2_without_a_launcher_runs_two_ranks():
@@ -44,7 +45,7 @@ def test_gpus_2_with_one_visible_device_fails_loudly():
 
 def test_strong_scaling_and_workloads_block_at_n_2():
     """The extra workloads run sharded on every rank (weak and strong) and the line keeps the block at N > 1."""
-    r, line = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--frames-in-flight", "2", "--scaling", "strong", "--extra-steps", "1"],
+    r, line = run_bench(["--gpus", "2", "--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--frames-in-flight", "2", "--scaling", "strong", "--extra-steps", "1"],
                         {"VPT_BENCH_DEVICE": "0"}, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
@@ -83,7 +84,7 @@ def test_headline_counters_are_measured_by_the_run_itself():
     import shutil
     if shutil.which("rocprofv3") is None and not os.path.exists("/opt/rocm/bin/rocprofv3"):
         pytest.skip("no rocprofv3 on this box")
-    r, line = run_bench(["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extra-workloads", "--no-latency", "--frames-in-flight", "16"], timeout=900)
+    r, line = run_bench(["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extra-workloads", "--no-latency", "--frames-in-flight", "16"], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     roof = line["roofline"]
     assert roof["pmc"]["source"].startswith("live"), roof["pmc"]
@@ -93,3 +94,25 @@ def test_headline_counters_are_measured_by_the_run_itself():
     assert 0.5 < roof["traffic"] / roof["record_bytes_per_launch"] < 8.0, (roof["traffic"], roof["record_bytes_per_launch"])
     assert 32.0 < roof["valu"]["active_lanes_of_64"] <= 64.0
     assert "committed_file" in roof["pmc"]
+
+
+def test_a_plain_run_times_the_headline_only_and_dumps_what_it_computed(tmp_path, vpt, scenes):
+    """No --full: the line carries the headline and none of the blocks --full adds; --steps sets the timed steps; --dump-outputs writes the
+    radiance image the timed path left, which equals the same frames rendered directly through the library."""
+    r, line = run_bench(["--steps", "3", "--warmup", "1", "--frames-in-flight", "2", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert line["metric"] == "Msamples/s at 1920x1080" and line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["config"]["batches_per_gpu"] == "3 x 2 frames"
+    assert abs(line["value"] - 3 * 2 * 1920 * 1080 / (3 * line["ms_per_step"] * 1e-3) / 1e6) < 0.01 * line["value"]   # value = samples / timed seconds
+    assert not {"roofline", "latency", "workloads", "cpu_baseline"} & set(line)
+    assert os.listdir(tmp_path / "out") == ["radiance.npy"]
+    img = np.load(tmp_path / "out" / "radiance.npy")
+    assert img.dtype == np.float32 and img.shape == (1080, 1920, 4) and np.isfinite(img).all() and img[..., :3].sum() > 0
+    g = vpt.PathTracer(1920, 1080, frames_in_flight=2)
+    g.set_scene(scenes("cornell_box"))
+    g.set_params(vpt.default_params(max_depth=8, base_seed=1, max_samples=0x7fffffff))
+    for _ in range(1 + 3):
+        g.render(2)
+    ref = g.radiance()
+    g.close()
+    assert np.array_equal(img, ref)

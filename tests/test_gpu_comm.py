@@ -146,7 +146,7 @@ def _free_port():
 def test_bench_two_ranks_on_one_device():
     env = dict(os.environ, VPT_BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames-in-flight", "2"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--frames-in-flight", "2"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -192,9 +192,9 @@ def test_bench_strong_scaling_splits_a_fixed_job():
 
 
 def test_bench_line_contract_single_gpu():
-    """`python bench.py` at N = 1 (short: 2 steps of 4 frames, CPU sample of ~1 s, no extra workloads): ONE JSON line with the driver's
+    """`python bench.py --full` at N = 1 (short: 2 steps of 4 frames, CPU sample of ~1 s, no extra workloads): ONE JSON line with the driver's
     fields, a roofline object whose fraction is a fraction, and the CPU baseline object."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames-in-flight", "4", "--no-extra-workloads", "--cpu-seconds", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--frames-in-flight", "4", "--no-extra-workloads", "--cpu-seconds", "1"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

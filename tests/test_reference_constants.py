@@ -15,7 +15,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/PathTracer/Shaders"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this machine")
 
 NUM = re.compile(r"(?<![\w.])(\d+\.\d*(?:[eE][-+]?\d+)?|\.\d+(?:[eE][-+]?\d+)?|\d+[eE][-+]?\d+|\d{5,})(?:[fFuU]|lf|LF)?(?![\w.])")
 
@@ -91,6 +90,7 @@ def targets():
     return {"oracle": {key(v) for v in literals(oracle)}, "product": {key(v) for v in literals(product)}}
 
 
+@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this machine")
 def test_every_constant_of_the_hot_path_shaders_is_in_both_restatements():
     have = targets()
     audited, missing = 0, []
