@@ -1,0 +1,85 @@
+// Host driver of vulkan-path-tracer_amd/csrc/path_plan.hpp for tests/test_path_plan_cpu.py: one modelled context whose device memory
+// is a fixed number of bytes.  The plan's allocations succeed when the buffers they ask for fit; batch_cap, grow and fit_batch are the
+// header's; pp_next_batch restates only the order in which vpt_api.hip's next_batch calls them.  Built as a shared library and driven through ctypes.
+#include <cstdint>
+
+#include "path_plan.hpp"
+
+using namespace vpt::plan;
+
+namespace {
+struct Model {
+    Policy p;
+    State s;
+    uint64_t avail = 0;          // device bytes the path buffers may take
+    bool sidx = false, media = false;            // per-sample words the next batch touches (samples_per_frame > 1, media)
+    bool has_sidx = false, has_media = false;    // ... and the ones the buffers hold
+    uint32_t alloc_calls = 0, alloc_failures = 0;
+    bool buffers_ok = true;
+};
+
+uint64_t model_bytes(const Model& m, uint64_t frames, uint64_t resident, bool sidx, bool media) {
+    return m.s.px * (frames * (kSampleBytes + (sidx ? 4u : 0u) + (media ? 8u : 0u)) + resident * kResidentBytes);
+}
+// alloc_path_buffers: frees what is held, then allocates (frames, resident) with the words the next batch touches
+int model_alloc(Model& m, uint32_t frames, uint32_t resident) {
+    m.alloc_calls++;
+    m.s.frames_alloc = m.s.resident_alloc = 0;
+    if (resident > frames) resident = frames;
+    if (m.s.px * frames >= (1ull << 31) || model_bytes(m, frames, resident, m.sidx, m.media) > m.avail) { m.alloc_failures++; return kAllocOutOfMemory; }
+    m.s.frames_alloc = frames; m.s.resident_alloc = resident;
+    m.has_sidx = m.sidx; m.has_media = m.media;
+    return kAllocOk;
+}
+bool words_ok(const Model& m) { return (!m.sidx || m.has_sidx) && (!m.media || m.has_media); }
+void fresh_buffers(Model& m, uint64_t px, uint64_t free_bytes) {   // alloc_render_buffers: the path buffers of ONE frame
+    m.s.px = px;
+    m.s.frames_in_flight = (uint32_t)frames_for_size(m.p.cfg_frames, px, true, free_bytes);
+    m.s.frames_cap = 0;
+    m.buffers_ok = model_alloc(m, 1, 1) == kAllocOk;
+}
+}  // namespace
+
+extern "C" {
+void* pp_create(uint64_t px, uint32_t cfg_frames, uint32_t cfg_resident, uint64_t free_bytes) {
+    Model* m = new Model;
+    m->p.cfg_frames = cfg_frames; m->p.cfg_resident = cfg_resident;
+    m->avail = free_bytes;
+    fresh_buffers(*m, px, free_bytes);
+    return m;
+}
+void pp_destroy(void* h) { delete (Model*)h; }
+// what scene, parameters and configuration allow (vpt_api.hip policy_of) and the per-sample words the next batch touches
+void pp_policy(void* h, int has_scene, int regen, uint32_t whole_frames, int sidx, int media) {
+    Model& m = *(Model*)h;
+    m.p.has_scene = has_scene != 0; m.p.regen = regen != 0; m.p.whole_frames = whole_frames;
+    m.sidx = sidx != 0; m.media = media != 0;
+}
+void pp_set_avail(void* h, uint64_t bytes) { ((Model*)h)->avail = bytes; }
+void pp_resize(void* h, uint64_t px, uint64_t free_bytes) { Model& m = *(Model*)h; m.avail = free_bytes; fresh_buffers(m, px, free_bytes); }
+uint32_t pp_batch_cap(void* h) { Model& m = *(Model*)h; return batch_cap(m.p, m.s); }
+uint32_t pp_resident_for(void* h, uint32_t frames) { Model& m = *(Model*)h; return resident_frames_for(m.p, m.s.frames_in_flight, frames); }
+// vpt_api.hip next_batch: *nf frames of `left`, buffers grown for them; returns 0 or the failed allocation's AllocResult
+int pp_next_batch(void* h, uint32_t left, uint32_t* nf) {
+    Model& m = *(Model*)h;
+    *nf = 0;
+    if (!m.buffers_ok) return kAllocFailed;
+    uint32_t n = left < batch_cap(m.p, m.s) ? left : batch_cap(m.p, m.s);
+    if (!holds(m.p, m.s, n) || !words_ok(m)) {
+        const Grown g = grow(m.p, m.s, n, [&](uint32_t f, uint32_t r) { return model_alloc(m, f, r); });
+        if (g.result != kAllocOk) {
+            if (model_alloc(m, g.frames, g.resident) != kAllocOk) { m.s.frames_alloc = m.s.resident_alloc = 0; m.buffers_ok = false; }
+            return g.result;
+        }
+    }
+    *nf = fit_batch(m.p, m.s, n);
+    return kAllocOk;
+}
+// frames_in_flight, batch_cap, long_factor, frames_alloc, resident_alloc, frames_cap, alloc calls, failed allocs
+void pp_state(void* h, uint32_t* out) {
+    Model& m = *(Model*)h;
+    out[0] = m.s.frames_in_flight; out[1] = batch_cap(m.p, m.s); out[2] = m.s.long_factor; out[3] = m.s.frames_alloc;
+    out[4] = m.s.resident_alloc; out[5] = m.s.frames_cap; out[6] = m.alloc_calls; out[7] = m.alloc_failures;
+}
+uint64_t pp_plan_bytes(uint64_t px, uint64_t frames, uint64_t resident) { return plan_bytes(px, frames, resident); }
+}

@@ -15,14 +15,10 @@
 
 #include "bvh_build.hpp"
 #include "kernels.hpp"
+#include "path_plan.hpp"
 
 using namespace vpt;
 
-constexpr uint64_t kBytesPerPath = 380;          // core slot records 68 + stream records ~290 (slack included) + queues 8 + image share
-constexpr uint32_t kMaxFramesInFlight = 8192;   // frames of one batch.  A 1/8 shard of 1080p holds ~448M paths at 1728 frames and its default batch is four times that
-                                                // (6912 frames = 1.79 G samples, what a whole 1080p image renders per batch at 904 frames): with round 5's bound of 2048 a rank of an 8-GPU
-                                                // job rendered 3.5 x shorter batches than a 1-GPU job, i.e. bench.py's "weak" scaling did not keep the per-rank work fixed
-constexpr uint64_t kResidentPaths = 448ull << 20;   // samples of a batch by default (see check_render_size)
 // The rest of a streams batch goes to k_finish (kernels_path.hip) — one launch instead of seven per bounce —
 //  * after kFinishAfterBounces (3) bounces when the batch is small from the start (a frame or two per call: its launches never fill the chip for long), and
 //  * as soon as the host sees fewer than kFinishBelowPaths paths alive in a large one (the last of depth-32 paths: 20 bounce-sets on nearly empty queues).
@@ -224,13 +220,21 @@ namespace {
 
 int fail(vpt_ctx* c, int code, const char* msg) { c->err = msg; return code; }
 
+// hipMemset is asynchronous to the host and runs on the null stream, which the context's non-blocking streams do not wait for: a kernel
+// enqueued after it may run before the clear has landed (a batch behind vpt_set_scene's image clear lost pixels that way).  Every clear of
+// memory the kernels touch goes through here instead: on the stream that uses the memory, waited for.
+hipError_t memset_now(hipStream_t s, void* p, int v, size_t n) {
+    hipError_t e = hipMemsetAsync(p, v, n, s);
+    return e == hipSuccess ? hipStreamSynchronize(s) : e;
+}
+
 template <class T>
 int upload(vpt_ctx* c, const std::vector<T>& v, const T** out, size_t min_elems = 1) {
     size_t n = std::max(v.size(), min_elems);
     void* d = nullptr;
     HIPCHK(c, hipMalloc(&d, n * sizeof(T)));
     c->scene_allocs.push_back(d);
-    HIPCHK(c, hipMemset(d, 0, n * sizeof(T)));
+    HIPCHK(c, memset_now(c->stream, d, 0, n * sizeof(T)));
     if (!v.empty()) HIPCHK(c, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     *out = (const T*)d;
     return VPT_OK;
@@ -288,19 +292,9 @@ int check_render_size(vpt_ctx* c, uint32_t width, uint32_t height, uint32_t* fra
     const uint64_t px = rows * width;
     if (px == 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "empty shard");
     if (px >= (1ull << 31) || (uint64_t)width * height >= (1ull << 31)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "image too large");
-    uint64_t F = c->cfg.frames_in_flight;
-    // ~448M resident paths whatever the shard size (226 frames at 1080p; kBytesPerPath x 448M = ~170 GB of the 288 GB, and never more
-    // than 60 % of the memory that is free right now): the last bounces of a batch are short launches that cannot fill 256 CUs, and
-    // a larger batch makes them longer for the same fixed cost.  Msamples/s from 32M to 128M paths: Cornell +8 %, atrium +16 %, glass
-    // bust (depth 32) +78 %; 128M to 256M: +0 / +2 / +18 %; 256M to 512M: +0 / +2.4 / +9.1 % (profiles/r03_frames_sweep.json).
-    // This is the CAP of a batch; the buffers hold what has actually been asked for (ensure_path_buffers).
-    if (F == 0) {
-        uint64_t paths = kResidentPaths;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) paths = std::min<uint64_t>(paths, (uint64_t)(free_b * 0.6) / kBytesPerPath);
-        F = paths / px;
-    }
-    F = std::max<uint64_t>(1, std::min<uint64_t>(F, kMaxFramesInFlight));
+    size_t free_b = 0, total_b = 0;
+    const bool free_known = c->cfg.frames_in_flight == 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    const uint64_t F = plan::frames_for_size(c->cfg.frames_in_flight, px, free_known, free_b);   // the CAP of a batch (path_plan.hpp)
     if (px * F >= (1ull << 31)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "too many paths in flight");
     *frames_out = (uint32_t)F;
     return VPT_OK;
@@ -393,10 +387,10 @@ int alloc_render_buffers(vpt_ctx* c) {
         // padded to the largest shard's row count (vpt_shard_floats): the buffer is handed to ncclGather as it is
         const size_t image_bytes = (size_t)shard_rows_of(P.height, 0, P.shard_count) * P.width * 16;
         HIPCHK(c, hipMalloc((void**)&c->image, image_bytes));
-        HIPCHK(c, hipMemset(c->image, 0, image_bytes));
+        HIPCHK(c, memset_now(c->stream, c->image, 0, image_bytes));
         if (P.shard_count > 1) {
             HIPCHK(c, hipMalloc((void**)&c->full_image, (size_t)P.width * P.height * 16));
-            HIPCHK(c, hipMemset(c->full_image, 0, (size_t)P.width * P.height * 16));
+            HIPCHK(c, memset_now(c->stream, c->full_image, 0, (size_t)P.width * P.height * 16));
         }
         return VPT_OK;
     };
@@ -420,22 +414,11 @@ bool whole_possible(const vpt_ctx* c) {
     const bool vol = !c->volumes.empty() || c->dsc.atm_on;
     return c->has_scene && c->lds_scene && c->whole_blocks > 0 && !vol && c->P.samples_per_frame == 1u;
 }
-// ... as far as scene, parameters and configuration go (the buffers are the callers' business)
-bool whole_policy(const vpt_ctx* c, uint32_t frames) {
-    if (!whole_possible(c)) return false;
-    return c->cfg.pipeline == VPT_PIPELINE_WHOLE || (c->cfg.pipeline == VPT_PIPELINE_AUTO && frames <= c->lab_whole_frames);
-}
-// Does a batch of `frames` frames need only its per-sample buffers (36 B per sample: frame sum, medium state), not the ~290 B of records per
-// resident path?  A whole-path launch keeps its paths in registers (vpt_config.resident_frames means nothing to it: no path of it is resident in memory).
-bool whole_without_records(const vpt_ctx* c, uint32_t frames) { return whole_policy(c, frames); }
-bool whole_applies(const vpt_ctx* c, uint32_t frames) { return whole_policy(c, frames) && frames <= c->frames_alloc; }
-
-// Frames of paths a batch of `frames` frames keeps resident.  Paths are regenerated — the next ray queue refilled with fresh camera rays
-// behind every shade stage, kernels_stream.hip k_refill_plan — on the STREAMS pipeline (scenes whose BVH lives in memory, no media, whole-frame
-// dispatches).  Everything else keeps every sample of a batch resident: the fused per-bounce kernels (scenes that ride in LDS run whole-path
-// launches, which hold no records at all; what is left for k_bounce — media, several samples per frame — is not worth a second mechanism),
-// round 1's stage kernels (records by slot), media batches (per-entry media streams), split-screen dispatches (launch indices map to
-// pixels per dispatch).
+// Frames of paths a batch keeps resident: paths are regenerated — the next ray queue refilled with fresh camera rays behind every shade
+// stage, kernels_stream.hip k_refill_plan — on the STREAMS pipeline (scenes whose BVH lives in memory, no media, whole-frame dispatches).
+// Everything else keeps every sample of a batch resident: the fused per-bounce kernels (scenes that ride in LDS run whole-path launches,
+// which hold no records at all; what is left for k_bounce — media, several samples per frame — is not worth a second mechanism), round 1's
+// stage kernels (records by slot), media batches (per-entry media streams), split-screen dispatches (launch indices map to pixels per dispatch).
 bool regen_allowed(const vpt_ctx* c) {
     if (!c->has_scene) return false;
     const bool vol = !c->volumes.empty() || c->dsc.atm_on;
@@ -443,59 +426,56 @@ bool regen_allowed(const vpt_ctx* c) {
     if (c->cfg.pipeline == VPT_PIPELINE_STAGED || c->cfg.pipeline == VPT_PIPELINE_STAGED_SORTED) return true;   // the stream kernels, whatever the scene's size
     return c->cfg.pipeline == VPT_PIPELINE_AUTO && !c->lds_scene;
 }
-// Default schedule of a context that regenerates (profiles/r05_frames_sweep.json, 1080p): batches of 4 x frames_in_flight frames with HALF of
-// frames_in_flight frames of paths resident — 904 / 113 frames: 126 GB instead of 142 GB for 226 / 226, glass bust (depth 32) 3272 against 3088
-// Msamples/s (the tail of a batch, ~max_depth bounce-sets on emptying queues, is paid once per 1.9 G samples instead of once per 469 M), atrium
-// 1477 against 1485.  vpt_config.resident_frames != 0: as asked (a value >= the batch keeps every sample resident).
-uint32_t resident_frames_for(const vpt_ctx* c, uint32_t frames) {
-    if (whole_without_records(c, frames)) return 1u;   // (one frame of records stays: what the context would need for a per-bounce batch of one frame)
-    if (!regen_allowed(c)) return frames;
-    uint64_t k = c->cfg.resident_frames;
-    if (k == 0) k = c->cfg.frames_in_flight != 0 ? frames : std::max(1u, c->frames_in_flight / 2u);   // (an explicit batch size without an explicit residency: all resident, as before)
-    return (uint32_t)std::min<uint64_t>(frames, k);
+// The sizing of the path buffers is path_plan.hpp's: what it needs to know of this context.
+plan::Policy policy_of(const vpt_ctx* c) {
+    plan::Policy p;
+    p.has_scene = c->has_scene;
+    p.regen = regen_allowed(c);
+    p.whole_frames = !whole_possible(c) ? 0u : c->cfg.pipeline == VPT_PIPELINE_WHOLE ? 0xffffffffu : c->cfg.pipeline == VPT_PIPELINE_AUTO ? c->lab_whole_frames : 0u;
+    p.cfg_frames = c->cfg.frames_in_flight; p.cfg_resident = c->cfg.resident_frames;
+    return p;
 }
-// The largest batch this context renders at once.  frames_in_flight is what fits with EVERY sample resident (380 B per sample; or what the caller
-// asked for).  A context whose batches keep half of that many frames of paths resident (regeneration by refill: 36 B per sample + 290 B per
-// resident path) — or none at all (whole-path launches: 36 B per sample) — takes batches long_factor (4) times as long, in less memory.
-uint32_t batch_cap(const vpt_ctx* c) {
-    const uint32_t F = c->frames_in_flight;
-    if (c->cfg.frames_in_flight != 0 || c->cfg.resident_frames != 0 || !c->has_scene) return F;
-    const uint64_t by_slots = ((1ull << 31) - 1ull) / std::max<uint64_t>(1, c->P.shard_pixels);
-    const uint32_t cap = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((uint64_t)F * c->long_factor, kMaxFramesInFlight), by_slots));
-    return (regen_allowed(c) || whole_policy(c, cap)) ? cap : F;
+plan::State plan_state(const vpt_ctx* c) {
+    plan::State s;
+    s.px = c->P.shard_pixels; s.frames_in_flight = c->frames_in_flight; s.frames_cap = c->frames_cap; s.long_factor = c->long_factor;
+    s.frames_alloc = c->frames_alloc; s.resident_alloc = c->resident_alloc;
+    return s;
 }
+// ... as far as scene, parameters and configuration go (the buffers are the callers' business)
+bool whole_policy(const vpt_ctx* c, uint32_t frames) { return plan::whole_policy(policy_of(c), frames); }
+// Does a batch of `frames` frames need only its per-sample buffers (36 B per sample: frame sum, medium state), not the ~290 B of records per
+// resident path?  A whole-path launch keeps its paths in registers (vpt_config.resident_frames means nothing to it: no path of it is resident in memory).
+bool whole_without_records(const vpt_ctx* c, uint32_t frames) { return whole_policy(c, frames); }
+bool whole_applies(const vpt_ctx* c, uint32_t frames) { return whole_policy(c, frames) && frames <= c->frames_alloc; }
+uint32_t resident_frames_for(const vpt_ctx* c, uint32_t frames) { return plan::resident_frames_for(policy_of(c), c->frames_in_flight, frames); }
+uint32_t batch_cap(const vpt_ctx* c) { return plan::batch_cap(policy_of(c), plan_state(c)); }
 
-// Grows the buffers so that a batch of `want` frames (<= frames_in_flight) fits; the caller has drained the streams.  A size the
-// library chose itself (vpt_config.frames_in_flight == 0) is halved and tried again when the device runs out of memory after all
-// (another process, fragmentation) — frames_in_flight then drops to what was obtained and the caller renders in smaller batches;
-// an explicit size fails as it is and the context keeps the buffers it had.
 // Do the per-sample word arrays allocated cover what the next batch touches (samples_per_frame / media may have changed since)?
 bool path_words_ok(const vpt_ctx* c) {
     const bool want_sidx = c->P.samples_per_frame > 1u, want_media = !c->volumes.empty() || c->dsc.atm_on;
     return (!want_sidx || c->ps_has_sidx) && (!want_media || c->ps_has_media);
 }
+bool path_buffers_hold(const vpt_ctx* c, uint32_t frames) { return plan::holds(policy_of(c), plan_state(c), frames) && path_words_ok(c); }
+// Grows the buffers so that a batch of `want` frames (<= batch_cap) fits, by plan::grow; the caller has drained the streams.  On failure the
+// context keeps the buffers it had (or none: buffers_ok == false) and the error of the allocation that failed.
 int ensure_path_buffers(vpt_ctx* c, uint32_t want) {
-    if (want <= c->frames_alloc && resident_frames_for(c, want) <= c->resident_alloc && path_words_ok(c)) return VPT_OK;
-    const uint32_t old = std::max(c->frames_alloc, 1u), old_res = std::max(c->resident_alloc, 1u);
-    uint32_t tryf = std::max(want, old);
-    while (true) {
-        // (a long batch — tryf beyond frames_in_flight — is sized for resident_frames_for(tryf) resident frames: keeping a larger old residency there would exceed the budget F was chosen for)
-        const uint32_t keep_res = tryf > c->frames_in_flight ? resident_frames_for(c, tryf) : std::max(resident_frames_for(c, tryf), std::min(old_res, tryf));
-        int rc = alloc_path_buffers(c, tryf, keep_res);
-        if (rc == VPT_OK) break;
-        std::string keep = c->err;
+    if (path_buffers_hold(c, want)) return VPT_OK;
+    int rc = VPT_OK;
+    std::string keep;
+    plan::State s = plan_state(c);
+    const plan::Grown g = plan::grow(policy_of(c), s, want, [&](uint32_t frames, uint32_t resident) {
+        rc = alloc_path_buffers(c, frames, resident);
+        if (rc == VPT_OK) return (int)plan::kAllocOk;
+        keep = c->err;
         free_path_buffers(c);
         (void)hipGetLastError();
-        const bool oom = rc == VPT_ERR_OUT_OF_MEMORY || rc == VPT_ERR_DEVICE;
-        if (!oom || c->cfg.frames_in_flight != 0 || tryf <= old) {
-            if (alloc_path_buffers(c, old, old_res) != VPT_OK) { free_path_buffers(c); (void)hipGetLastError(); c->buffers_ok = false; }
-            c->err = keep;
-            return rc;
-        }
-        if (tryf > c->frames_in_flight && c->long_factor > 1u) c->long_factor /= 2u;   // a long batch did not fit: shorter long batches from now on
-        tryf = std::max(tryf / 2, old);
-        c->frames_cap = tryf;
-        c->frames_in_flight = std::min(c->frames_in_flight, tryf);
+        return (int)(rc == VPT_ERR_OUT_OF_MEMORY || rc == VPT_ERR_DEVICE ? plan::kAllocOutOfMemory : plan::kAllocFailed);
+    });
+    c->frames_in_flight = s.frames_in_flight; c->frames_cap = s.frames_cap; c->long_factor = s.long_factor;
+    if (g.result != plan::kAllocOk) {
+        if (alloc_path_buffers(c, g.frames, g.resident) != VPT_OK) { free_path_buffers(c); (void)hipGetLastError(); c->buffers_ok = false; }
+        c->err = keep;
+        return rc;
     }
     return check_stream_slack(c);
 }
@@ -1089,10 +1069,10 @@ int init_ctx_resources(vpt_ctx* c) {
         hipEventCreateWithFlags(&c->ev_shade, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_resolved, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_post, hipEventDisableTiming) != hipSuccess ||
         hipMalloc((void**)&c->ctr, sizeof(Counters)) != hipSuccess) return VPT_ERR_DEVICE;
-    (void)hipMemset(c->ctr, 0, sizeof(Counters));
+    (void)memset_now(c->stream, c->ctr, 0, sizeof(Counters));
     if (hipMalloc((void**)&c->sctr, sizeof(StreamCounters)) != hipSuccess) return VPT_ERR_DEVICE;
-    (void)hipMemset(c->sctr, 0, sizeof(StreamCounters));
-    if (hipMalloc((void**)&c->d_launch_off, (kMaxFramesInFlight + 1) * 4) != hipSuccess) return VPT_ERR_DEVICE;
+    (void)memset_now(c->stream, c->sctr, 0, sizeof(StreamCounters));
+    if (hipMalloc((void**)&c->d_launch_off, (plan::kMaxFramesInFlight + 1) * 4) != hipSuccess) return VPT_ERR_DEVICE;
     for (int k = 0; k < kTickets; k++)
         if (hipEventCreateWithFlags(&c->tick_ev[k], hipEventDisableTiming) != hipSuccess) { c->tick_ev[k] = nullptr; return VPT_ERR_DEVICE; }
     if (hipHostMalloc((void**)&c->h_ctr, sizeof(HostCounters), hipHostMallocDefault) != hipSuccess) { c->h_ctr = nullptr; return VPT_ERR_DEVICE; }
@@ -1111,7 +1091,7 @@ vpt_ctx* get_lane(vpt_ctx* c, int k) {
     bool ok = init_ctx_resources(L) == VPT_OK && alloc_path_buffers(L, 1, 1) == VPT_OK;
     if (ok) {
         const size_t bytes = stack_overflow_bytes((uint32_t)std::max(std::max(std::max(c->primary_blocks_general, c->primary_blocks_plain), c->whole_blocks), c->max_blocks));   // (the stream kernels' grids included)
-        ok = hipMalloc(&L->lane_spill, bytes) == hipSuccess && hipMemset(L->lane_spill, 0x7f, bytes) == hipSuccess;   // (kSpillPatternByte: vpt_get_stats counts what was spilled)
+        ok = hipMalloc(&L->lane_spill, bytes) == hipSuccess && memset_now(L->stream, L->lane_spill, 0x7f, bytes) == hipSuccess;   // (kSpillPatternByte: vpt_get_stats counts what was spilled)
         L->stack_overflow_words = (uint32_t)(bytes / 4);
     }
     if (!ok) { (void)hipGetLastError(); destroy_lane(L); return nullptr; }
@@ -1458,7 +1438,7 @@ int vpt_set_scene(vpt_ctx* c, const vpt_scene_desc* sd) {
         D.stack_overflow = (uint32_t*)d;
         c->stack_overflow2 = (uint32_t*)((char*)d + region);
         // preset to a word no stack entry can be (a node index of 2.1e9; leaf codes are negative): vpt_get_stats counts what was spilled
-        HIPCHK(c, hipMemset(d, kSpillPatternByte, 2 * region));
+        HIPCHK(c, memset_now(c->stream, d, kSpillPatternByte, 2 * region));
         c->stack_overflow_words = (uint32_t)(region / 4);
         c->spill_dirty = true;
     }
@@ -1472,7 +1452,7 @@ int vpt_set_scene(vpt_ctx* c, const vpt_scene_desc* sd) {
     c->has_scene = true;
     update_depth_bounded(c);
     // (after a failed vpt_resize there is no image to clear: the scene is installed all the same, rendering needs a successful resize first)
-    if (c->buffers_ok) HIPCHK(c, hipMemset(c->image, 0, (size_t)c->P.shard_pixels * 16));
+    if (c->buffers_ok) HIPCHK(c, memset_now(c->stream, c->image, 0, (size_t)c->P.shard_pixels * 16));
     c->set_scene_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scene0).count();
     return check_stream_slack(c);
 }
@@ -1675,13 +1655,12 @@ int next_batch(vpt_ctx* c, uint32_t left, uint32_t* nf) {
     const uint64_t frames_needed = ((uint64_t)c->params.max_samples + c->params.samples_per_frame - 1) / c->params.samples_per_frame;
     const uint64_t disp_left = frames_needed * S2 - c->dispatch_count;
     uint32_t n = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(left, batch_cap(c)), disp_left);
-    if (n > c->frames_alloc || resident_frames_for(c, n) > c->resident_alloc || !path_words_ok(c)) {   // the buffers grow to the largest batch asked for (and to the words it touches); nothing may be in flight while they are replaced
+    if (!path_buffers_hold(c, n)) {   // the buffers grow to the largest batch asked for (and to the words it touches); nothing may be in flight while they are replaced
         int rc = drain(c);
         if (rc) return rc;
         if ((rc = ensure_path_buffers(c, n))) return rc;
-        n = std::min(n, c->frames_alloc);   // (a size the library chose itself may have been halved)
     }
-    if (!regen_allowed(c) && !whole_without_records(c, n)) n = std::min(n, c->resident_alloc);
+    n = plan::fit_batch(policy_of(c), plan_state(c), n);
     if (media_on_streams(c)) {   // media on the streams: the batch is what the media streams hold
         int rm = ensure_media_buffers(c);
         if (rm) return rm;
@@ -2056,9 +2035,9 @@ int vpt_reset_stats(vpt_ctx* c) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
     c->stats = vpt_stats{};
-    HIPCHK(c, hipMemset(c->ctr, 0, sizeof(Counters)));
+    HIPCHK(c, memset_now(c->stream, c->ctr, 0, sizeof(Counters)));
     memset(c->h_ctr, 0, sizeof(HostCounters));
-    for (vpt_ctx* L : c->lanes) if (L) { HIPCHK(c, hipMemset(L->ctr, 0, sizeof(Counters))); memset(L->h_ctr, 0, sizeof(HostCounters)); L->stats = vpt_stats{}; }
+    for (vpt_ctx* L : c->lanes) if (L) { HIPCHK(c, memset_now(L->stream, L->ctr, 0, sizeof(Counters))); memset(L->h_ctr, 0, sizeof(HostCounters)); L->stats = vpt_stats{}; }
     return VPT_OK;
 }
 
@@ -2302,7 +2281,7 @@ int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t
         }
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIPCHK(c, hipMemset(c->ctr, 0, sizeof(Counters)));
+    HIPCHK(c, memset_now(c->stream, c->ctr, 0, sizeof(Counters)));
     if (best_ms) *best_ms = best;
     if (hits) {
         std::vector<float4> h4(n); std::vector<uint32_t> hi(n, 0xffffffffu);
