@@ -527,7 +527,7 @@ def sample_emissive(S, position, rng):
     to_light = _norm(tp - position)
     ln = _norm(np.cross(a2 - a0, a1 - a0))
     area = float(np.linalg.norm(np.cross(a1 - a0, a2 - a0))) * 0.5
-    d2 = float(np.dot(tp - position, tp - position)); ct = abs(float(np.dot(ln, to_light)))
+    d2 = np.float64(np.dot(tp - position, tp - position)); ct = np.abs(np.float64(np.dot(ln, to_light)))   # IEEE: a point in the light's plane gets pdf inf
     with np.errstate(all="ignore"):
         pdf = d2 / (float(ne) * float(ntri) * area * ct)
     t0, t1, t2 = (ev["texcoord"][int(k)].astype(np.float64) for k in tri)
@@ -850,7 +850,7 @@ def closest_hit(S, luts, pay, rd, hit, rng, P):
         w1, w2_, w3 = (M[:3, :3] @ q + M[:3, 3] for q in (P1, P2, P3))
         area = float(np.linalg.norm(np.cross(w2_ - w1, w3 - w1))) * 0.5
         d2 = float(np.dot(pos - pay["origin"], pos - pay["origin"]))
-        ct = abs(float(np.dot(N, _norm(pay["origin"] - pos))))
+        ct = np.abs(np.float64(np.dot(N, _norm(pay["origin"] - pos))))
         ntri = len(idx) // 3
         with np.errstate(all="ignore"):
             lp = (1.0 / len(S.emissive)) * (1.0 / ntri) * (1.0 / area) * (d2 / ct)

@@ -14,11 +14,14 @@ from test_oracle_bsdf import mat, sphere_grid
 
 
 def lut64(table, u, v, layer):
-    """uLookupTableSampler on an R32F 2D array (PathTracer.cpp:93-94): bilinear, clamp to edge, nearest layer (ties to even)."""
+    """uLookupTableSampler on an R32F 2D array (PathTracer.cpp:93-94): bilinear, clamp to edge, nearest layer (ties to even).
+    A NaN coordinate (sqrt(V.z) of a view direction that a strong normal map has put below the shading plane) is left to the
+    implementation by Vulkan; the project pins it as texel-space 0 (include/vpt_fp32.h texel_coords, lut_layer)."""
     sz, sy, sx = table.shape
-    l = int(np.rint(np.clip(layer, 0, sz - 1)))
+    l = 0 if np.isnan(layer) else int(np.rint(np.clip(layer, 0, sz - 1)))
     def axis(c, n):
         x = np.asarray(c, np.float64) * n - 0.5
+        x = np.where(np.abs(x) < 1e9, x, 0.0)
         f = np.floor(x)
         return np.clip(f, 0, n - 1).astype(int), np.clip(f + 1, 0, n - 1).astype(int), x - f
     x0, x1, fx = axis(u, sx); y0, y1, fy = axis(v, sy)
