@@ -18,28 +18,16 @@
 #include "path_plan.hpp"
 
 using namespace vpt;
-
-// The rest of a streams batch goes to k_finish (kernels_path.hip) — one launch instead of seven per bounce —
-//  * after kFinishAfterBounces (3) bounces when the batch is small from the start (a frame or two per call: its launches never fill the chip for long), and
-//  * as soon as the host sees fewer than kFinishBelowPaths paths alive in a large one (the last of depth-32 paths: 20 bounce-sets on nearly empty queues).
-#ifndef VPT_FINISH_AFTER   // (-D overrides: the A/B builds of tests/tools/ab_variants.sh)
-#define VPT_FINISH_AFTER 3
-#endif
-#ifndef VPT_FINISH_BELOW
-#define VPT_FINISH_BELOW (1u << 18)
-#endif
-constexpr uint32_t kFinishSmallBatchPaths = 6u << 20, kFinishAfterBounces = VPT_FINISH_AFTER, kFinishBelowPaths = VPT_FINISH_BELOW;
+using plan::Kind;
 
 // One wavefront batch in progress: what render_batch's stages hand to each other (and what an asynchronous batch leaves behind for
 // the call that finishes it).
 struct BatchState {
     uint32_t frames = 0, dispatch_base = 0, n_slots = 0;
     uint32_t n_first = 0;   // slots the camera-ray launch starts (n_slots, or the resident part of it when paths are regenerated)
-    bool fused = false, stream = false, media_stream = false, sorted = false, overlap = false, count = false;
-    bool whole = false;     // the whole batch is ONE launch of k_whole (kernels_path.hip): no bounces follow
-    bool regen = false;     // only n_first of the batch's n_slots samples start with the camera-ray launch; refills start the rest (kernels_stream.hip k_refill_plan)
-    uint32_t finish_at = 0; // streams: once this many bounces have run, ONE launch of k_finish runs what is left of the batch to its end (0: never)
-    bool finished = false;  // ... and it has been enqueued: no bounce follows
+    plan::Schedule sd;      // how it runs (path_plan.hpp decide); sd.finish_at is set late when the host sees few paths alive (batch_finish)
+    bool count = false;
+    bool finished = false;  // k_finish has been enqueued: no bounce follows
     uint32_t parity = 0, k3 = 0;
     bool join_pending = false;
     uint64_t iter = 0, iter_cap = 0, min_bounces = 0;
@@ -126,7 +114,6 @@ struct vpt_ctx {
     uint64_t graph_streak_gen = 0;
     uint64_t graph_kernel_launches[VPT_KERNEL_COUNT] = {};
     bool graph_broken = false;       // a capture failed once on this context: stay on plain launches
-    bool capturing = false;          // a batch is being captured into a hipGraph: one stream only (no shadow / join overlap on stream2)
     // Pipelined 1-frame batches (vpt_render_async): a frame of the fused fixed schedule is a chain of ~9 dependent launches, each bounded
     // below by the latency of one bounce (~60-90 us on nearly empty queues), so one frame at a time leaves most of the chip idle
     // (profiles/r04_latency_probe.json: 0.95 ms of kernels per 1080p frame against 0.33 ms per frame in 16-frame batches).  Consecutive
@@ -219,6 +206,21 @@ namespace {
     } while (0)
 
 int fail(vpt_ctx* c, int code, const char* msg) { c->err = msg; return code; }
+
+// Media: homogeneous box volumes or the atmosphere.
+bool media_on(const vpt_ctx* c) { return !c->volumes.empty() || c->dsc.atm_on; }
+// What path_plan.hpp decides from: how a batch runs and how the path buffers are sized.  A handful of loads — every batch asks.
+plan::Facts facts_of(const vpt_ctx* c) {
+    plan::Facts f;
+    f.pipeline = c->cfg.pipeline; f.build_flags = c->cfg.build_flags; f.lab_build = VPT_LAB != 0;
+    f.has_scene = c->has_scene; f.lds_scene = c->lds_scene; f.whole_grid = c->whole_blocks > 0; f.media = media_on(c);
+    f.samples_per_frame = c->P.samples_per_frame; f.split = c->P.split; f.max_depth = c->P.max_depth; f.depth_bounded = c->depth_bounded;
+    f.whole_frames_bound = c->lab_whole_frames;
+    f.profile = c->cfg.profile != 0; f.count_traversal = c->cfg.count_traversal != 0;
+    f.shard_pixels = c->P.shard_pixels;
+    f.cfg_frames = c->cfg.frames_in_flight; f.cfg_resident = c->cfg.resident_frames;
+    return f;
+}
 
 // hipMemset is asynchronous to the host and runs on the null stream, which the context's non-blocking streams do not wait for: a kernel
 // enqueued after it may run before the clear has landed (a batch behind vpt_set_scene's image clear lost pixels that way).  Every clear of
@@ -314,7 +316,7 @@ int alloc_path_buffers(vpt_ctx* c, uint32_t frames, uint32_t resident) {
     // anisotropy always; the sample index only for samples_per_frame > 1, VolumeDepth / ColorChannel only with media — 36 B per sample of
     // a plain batch (the kernels touch those words under exactly these conditions; path_words_ok() replaces the buffers when a batch needs more).
     // The records of round 1's stage kernels come with ensure_legacy_buffers()
-    const bool want_sidx = P.samples_per_frame > 1u, want_media = !c->volumes.empty() || c->dsc.atm_on;
+    const bool want_sidx = P.samples_per_frame > 1u, want_media = media_on(c);
     const size_t kRecords = 2, kWords = 1u + (want_sidx ? 1u : 0u) + (want_media ? 2u : 0u);
     size_t stride = ((size_t)samples + 63) & ~(size_t)63;
     HIPCHK(c, hipMalloc(&c->ps_block, stride * (16 * kRecords + 4 * kWords)));
@@ -408,51 +410,19 @@ int alloc_render_buffers(vpt_ctx* c) {
     return check_stream_slack(c);
 }
 
-// One launch per batch (kernels_path.hip k_whole): the scene rides in LDS, no media, one sample per pixel and frame.
-// VPT_PIPELINE_WHOLE asks for it; AUTO takes it wherever it applies (lab_whole_frames bounds the batch size, for the A/B).
-bool whole_possible(const vpt_ctx* c) {
-    const bool vol = !c->volumes.empty() || c->dsc.atm_on;
-    return c->has_scene && c->lds_scene && c->whole_blocks > 0 && !vol && c->P.samples_per_frame == 1u;
-}
-// Frames of paths a batch keeps resident: paths are regenerated — the next ray queue refilled with fresh camera rays behind every shade
-// stage, kernels_stream.hip k_refill_plan — on the STREAMS pipeline (scenes whose BVH lives in memory, no media, whole-frame dispatches).
-// Everything else keeps every sample of a batch resident: the fused per-bounce kernels (scenes that ride in LDS run whole-path launches,
-// which hold no records at all; what is left for k_bounce — media, several samples per frame — is not worth a second mechanism), round 1's
-// stage kernels (records by slot), media batches (per-entry media streams), split-screen dispatches (launch indices map to pixels per dispatch).
-bool regen_allowed(const vpt_ctx* c) {
-    if (!c->has_scene) return false;
-    const bool vol = !c->volumes.empty() || c->dsc.atm_on;
-    if (vol || c->P.split != 1u) return false;
-    if (c->cfg.pipeline == VPT_PIPELINE_STAGED || c->cfg.pipeline == VPT_PIPELINE_STAGED_SORTED) return true;   // the stream kernels, whatever the scene's size
-    return c->cfg.pipeline == VPT_PIPELINE_AUTO && !c->lds_scene;
-}
 // The sizing of the path buffers is path_plan.hpp's: what it needs to know of this context.
-plan::Policy policy_of(const vpt_ctx* c) {
-    plan::Policy p;
-    p.has_scene = c->has_scene;
-    p.regen = regen_allowed(c);
-    p.whole_frames = !whole_possible(c) ? 0u : c->cfg.pipeline == VPT_PIPELINE_WHOLE ? 0xffffffffu : c->cfg.pipeline == VPT_PIPELINE_AUTO ? c->lab_whole_frames : 0u;
-    p.cfg_frames = c->cfg.frames_in_flight; p.cfg_resident = c->cfg.resident_frames;
-    return p;
-}
+plan::Policy policy_of(const vpt_ctx* c) { return plan::policy_of(facts_of(c)); }
 plan::State plan_state(const vpt_ctx* c) {
     plan::State s;
     s.px = c->P.shard_pixels; s.frames_in_flight = c->frames_in_flight; s.frames_cap = c->frames_cap; s.long_factor = c->long_factor;
     s.frames_alloc = c->frames_alloc; s.resident_alloc = c->resident_alloc;
     return s;
 }
-// ... as far as scene, parameters and configuration go (the buffers are the callers' business)
-bool whole_policy(const vpt_ctx* c, uint32_t frames) { return plan::whole_policy(policy_of(c), frames); }
-// Does a batch of `frames` frames need only its per-sample buffers (36 B per sample: frame sum, medium state), not the ~290 B of records per
-// resident path?  A whole-path launch keeps its paths in registers (vpt_config.resident_frames means nothing to it: no path of it is resident in memory).
-bool whole_without_records(const vpt_ctx* c, uint32_t frames) { return whole_policy(c, frames); }
-bool whole_applies(const vpt_ctx* c, uint32_t frames) { return whole_policy(c, frames) && frames <= c->frames_alloc; }
-uint32_t resident_frames_for(const vpt_ctx* c, uint32_t frames) { return plan::resident_frames_for(policy_of(c), c->frames_in_flight, frames); }
 uint32_t batch_cap(const vpt_ctx* c) { return plan::batch_cap(policy_of(c), plan_state(c)); }
 
 // Do the per-sample word arrays allocated cover what the next batch touches (samples_per_frame / media may have changed since)?
 bool path_words_ok(const vpt_ctx* c) {
-    const bool want_sidx = c->P.samples_per_frame > 1u, want_media = !c->volumes.empty() || c->dsc.atm_on;
+    const bool want_sidx = c->P.samples_per_frame > 1u, want_media = media_on(c);
     return (!want_sidx || c->ps_has_sidx) && (!want_media || c->ps_has_media);
 }
 bool path_buffers_hold(const vpt_ctx* c, uint32_t frames) { return plan::holds(policy_of(c), plan_state(c), frames) && path_words_ok(c); }
@@ -480,7 +450,7 @@ int ensure_path_buffers(vpt_ctx* c, uint32_t want) {
     return check_stream_slack(c);
 }
 
-// Round 1's stage kernels (VPT_PIPELINE_STAGED_R1, VPT_FLAG_LOCAL_HITS, an LDS-sized scene forced into the staged pipeline)
+// Round 1's stage kernels (VPT_PIPELINE_STAGED_R1 only: laboratory build)
 // keep a path's records by slot: 13 more float4 records (pathLight among them), the hit instance and the two-ended connect queue, 216 bytes per path,
 // allocated when such a batch is first rendered and kept until the next resize.
 // The class queues of VPT_PIPELINE_STAGED_SORTED (21 bytes per path), likewise on first use.
@@ -689,75 +659,54 @@ void collect_timing(vpt_ctx* c) {  // call after a stream sync
 // batch_check (host synchronisation: how many paths are still alive).  The bounce loop runs without host round-trips: every stage
 // reads its queue size from device memory, so the host only looks at the counters every few bounces (render_batch) or not at all
 // until somebody waits (vpt_render_async).
-bool media_on_streams(const vpt_ctx* c) {
-    const bool vol = !c->volumes.empty() || c->dsc.atm_on;
-    return vol && !c->lds_scene && (c->cfg.pipeline == VPT_PIPELINE_AUTO || c->cfg.pipeline == VPT_PIPELINE_STAGED);
+
+// Split-screen dispatch (split S > 1): RayTrace(ceil(W/S), ceil(H/S)) per dispatch, in-bounds part only (PathTracer.cpp:145-150, RayGen.slang:24).
+uint32_t split_dispatch_slots(const RenderParams& P, uint32_t dispatch) {
+    const uint32_t S = P.split, ch = dispatch % (S * S), cx = ch % S, cy = ch / S;
+    const uint32_t lw = cx < P.width ? (P.width - cx + S - 1) / S : 0, lh = cy < P.height ? (P.height - cy + S - 1) / S : 0;
+    return lw * lh;
 }
-int batch_begin(vpt_ctx* c, uint32_t frames, uint32_t dispatch_base, BatchState& b) {
+// Samples of a batch.
+uint32_t batch_slots(const RenderParams& P, uint32_t frames, uint32_t dispatch_base) {
+    if (P.split <= 1) return frames * P.shard_pixels;
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < frames; k++) n += split_dispatch_slots(P, dispatch_base + k);
+    return n;
+}
+// How a batch of `frames` frames runs on X — the context itself or one of its lanes — by path_plan.hpp: the facts are the OWNER's `f`, the
+// buffers X's.  A refused batch leaves its reason in X->err.
+int decide_batch(vpt_ctx* X, const plan::Facts& f, uint32_t frames, uint32_t dispatch_base, bool capturing, plan::Schedule& sd) {
+    if (frames == 0 || frames > X->frames_alloc) return fail(X, VPT_ERR_DEVICE, "internal: batch larger than the path buffers");
+    sd = plan::decide(f, frames, X->frames_alloc, X->resident_alloc, batch_slots(X->P, frames, dispatch_base), X->owner != nullptr, capturing);
+    return sd.err != VPT_OK ? fail(X, sd.err, sd.msg) : VPT_OK;
+}
+// Turns the decided schedule into buffers and launches.
+int batch_begin(vpt_ctx* c, const plan::Schedule& sd, uint32_t frames, uint32_t dispatch_base, BatchState& b) {
     hipStream_t s = c->stream;
     b = BatchState{};
-    b.frames = frames; b.dispatch_base = dispatch_base;
+    b.frames = frames; b.dispatch_base = dispatch_base; b.sd = sd;
     (c->owner ? c->owner : c)->spill_dirty = true;
-    if (frames == 0 || frames > c->frames_alloc) return fail(c, VPT_ERR_DEVICE, "internal: batch larger than the path buffers");
-    // path regeneration: only `resident` frames of the batch's samples are in flight; the room ended paths leave in the next ray queue is
-    // refilled with the batch's next unstarted samples behind every shade stage (kernels_stream.hip k_refill_plan), until they are used up
-    const bool whole = whole_applies(c, frames);   // (keeps its paths in registers: no records, nothing to regenerate)
-    const uint32_t resident = whole ? frames : std::min(frames, c->resident_alloc);
-    const bool regen = resident < frames;
-    if (regen && !regen_allowed(c)) return fail(c, VPT_ERR_DEVICE, "internal: this batch needs all of its samples resident");
-    uint32_t n_slots = frames * c->P.shard_pixels;  // samples of the batch
-    const uint32_t S = c->P.split;
-    if (S > 1) {  // RayTrace(ceil(W/S), ceil(H/S)) per dispatch, in-bounds part only (PathTracer.cpp:145-150, RayGen.slang:24)
+    const uint32_t n_slots = batch_slots(c->P, frames, dispatch_base);
+    if (c->P.split > 1) {   // launch-grid prefix sums of the batch's dispatches
         std::vector<uint32_t> off(frames + 1, 0u);
-        for (uint32_t k = 0; k < frames; k++) {
-            uint32_t ch = (dispatch_base + k) % (S * S), cx = ch % S, cy = ch / S;
-            uint32_t lw = cx < c->P.width ? (c->P.width - cx + S - 1) / S : 0, lh = cy < c->P.height ? (c->P.height - cy + S - 1) / S : 0;
-            off[k + 1] = off[k] + lw * lh;
-        }
-        n_slots = off[frames];
+        for (uint32_t k = 0; k < frames; k++) off[k + 1] = off[k] + split_dispatch_slots(c->P, dispatch_base + k);
         HIPCHK(c, hipMemcpyAsync(c->d_launch_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipStreamSynchronize(s));  // `off` is a stack-lifetime staging buffer
     }
     b.n_slots = n_slots;
-    b.regen = regen;
-    b.n_first = regen ? resident * c->P.shard_pixels : n_slots;   // launch-grid size of the camera-ray kernel = the most paths ever resident
+    b.n_first = sd.regen ? sd.resident * c->P.shard_pixels : n_slots;   // launch-grid size of the camera-ray kernel = the most paths ever resident
     b.count = c->cfg.count_traversal != 0;
-    // fused (one kernel per bounce, bounce 0 included) when the BVH rides in LDS; staged otherwise
-    const bool vol = !c->volumes.empty() || c->dsc.atm_on;
-    // AUTO: fused for LDS-resident scenes, the stream pipeline otherwise (atrium 1150 vs 575, glass bust 2410 vs 1290, Cornell box with
-    // the 960-triangle glass sphere 2880 vs 2600 Msamples/s: no scene measured prefers the fused kernel once its BVH lives in memory)
-    // Media (volumes / atmosphere): on the streams when the BVH lives in memory (kernels_media.hip: the traversal then runs on the
-    // vote-scheduled kernels), in the fused per-bounce kernel when it rides in LDS or when the fused pipeline is asked for.
-    b.media_stream = media_on_streams(c);
-    b.fused = (vol && !b.media_stream) || c->cfg.pipeline == VPT_PIPELINE_FUSED || (c->cfg.pipeline == VPT_PIPELINE_AUTO && c->lds_scene) || c->cfg.pipeline == VPT_PIPELINE_WHOLE;
-    b.whole = whole;
-    if (c->cfg.pipeline == VPT_PIPELINE_WHOLE && !b.whole)
-        return fail(c, VPT_ERR_UNSUPPORTED, "VPT_PIPELINE_WHOLE needs a scene whose BVH rides in LDS, no media, samples_per_frame == 1 and every sample of a batch resident");
-    b.stream = !b.fused && c->cfg.pipeline != VPT_PIPELINE_STAGED_R1;   // (a scene that rides in LDS and is forced into the staged pipeline runs the stream kernels on its tree in memory; round 1's stage kernels: laboratory build, VPT_PIPELINE_STAGED_R1)
-    if (vol && c->cfg.pipeline == VPT_PIPELINE_STAGED && c->lds_scene)
-        return fail(c, VPT_ERR_UNSUPPORTED, "media with VPT_PIPELINE_STAGED need a scene whose BVH lives in memory (this one rides in LDS: use VPT_PIPELINE_AUTO or _FUSED)");
-    if (b.media_stream) {
+    if (sd.kind == Kind::MediaStreams) {
         int rl = ensure_media_buffers(c); if (rl != VPT_OK) return rl;
         if (frames > c->media_frames) return fail(c, VPT_ERR_DEVICE, "internal: media batch larger than the media streams");
     }
-#if VPT_LAB
-    if (!b.fused && !b.stream) { int rl = ensure_legacy_buffers(c); if (rl != VPT_OK) return rl; }
-#else
-    if (!b.fused && !b.stream) return fail(c, VPT_ERR_UNSUPPORTED, "VPT_PIPELINE_STAGED_R1 needs the laboratory build");
-#endif
-    if (b.stream && c->cfg.pipeline == VPT_PIPELINE_STAGED_SORTED) { int rl = ensure_sorted_buffers(c); if (rl != VPT_OK) return rl; }
+    if (sd.kind == Kind::StagedR1) { int rl = ensure_legacy_buffers(c); if (rl != VPT_OK) return rl; }
+    if (sd.kind == Kind::StreamsSorted) { int rl = ensure_sorted_buffers(c); if (rl != VPT_OK) return rl; }
     b.min_bounces = (uint64_t)c->P.max_depth * c->P.samples_per_frame;
-    b.iter_cap = (b.min_bounces * 4ull + 1024ull) * ((frames + resident - 1) / resident);
-    b.sorted = c->cfg.pipeline == VPT_PIPELINE_STAGED_SORTED;
-    // Two streams: the shadow-ray kernels and the join of bounce k run beside the extend of bounce k + 1 (which needs only the ray
-    // queue shade k wrote), so the tail of one persistent traversal kernel is filled by the next one's first blocks.  Off while
-    // kernels are timed or visits counted (one kernel at a time then) and in the sorted pipeline.
-    b.overlap = b.stream && !b.sorted && !c->cfg.profile && !b.count && !b.media_stream && !c->capturing && !c->owner;   // (a lane's batch stays on its one stream: the lanes overlap each other)
-    const bool finisher = !(c->cfg.build_flags & VPT_BUILD_STREAMS_ONLY);
-    if (finisher && b.stream && !b.media_stream && !b.regen && n_slots <= kFinishSmallBatchPaths) b.finish_at = kFinishAfterBounces;
+    b.iter_cap = (b.min_bounces * 4ull + 1024ull) * ((frames + sd.resident - 1) / sd.resident);
     if (n_slots == 0) return VPT_OK;
     HIPCHK(c, hipMemsetAsync(c->ctr, 0, offsetof(Counters, stat_closest), s));  // queue words only, stat_* keep running
-    if (b.whole) {  // the batch's paths from camera ray to their end in one launch; no queue is written, alive3[] stays 0 for the resolve's guard
+    if (sd.kind == Kind::Whole) {  // the batch's paths from camera ray to their end in one launch; no queue is written, alive3[] stays 0 for the resolve's guard
         const uint32_t grid = std::max(1u, std::min<uint32_t>((uint32_t)std::min(c->whole_blocks, c->primary_blocks), (n_slots + 255u) / 256u));   // (blocks of 256 lanes)
         // tiles of 64 samples: `rounds` per wave; mode 0: the first round static, mode 1: all but the last, mode 2: half of them; the rest through the counter
         const uint32_t n_waves = grid * 4u, rounds = ((n_slots + 63u) / 64u) / n_waves, mode = c->lab_whole_sched >> 4;
@@ -765,11 +714,11 @@ int batch_begin(vpt_ctx* c, uint32_t frames, uint32_t dispatch_base, BatchState&
         // (mode 3: mode 0 with guided chunks — at most the given tiles per atomic, fewer towards the end of the batch)
         TIMED(c, VPT_K_PRIMARY, launch_whole(s, grid, b.count, c->dsc, c->P, c->ps, c->ctr, n_slots, dispatch_base, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u)));
         b.parity = 1; b.k3 = 1; b.iter = 1;
-    } else if (b.fused) {  // bounce 0 of every slot needs no input records; survivors land in queue[1]
+    } else if (sd.kind == Kind::Fused) {  // bounce 0 of every slot needs no input records; survivors land in queue[1]
         TIMED(c, VPT_K_PRIMARY, launch_bounce(s, (uint32_t)c->primary_blocks, c->lds_scene, b.count, true, c->dsc, c->P, c->ps, c->ss, nullptr, c->queue[1], c->ctr, 0u, b.n_first, dispatch_base, 0u, c->scene_plain));
         b.parity = 1; b.k3 = 1; b.iter = 1;
-    } else if (b.stream) {
-        TIMED(c, VPT_K_PRIMARY, launch_raygen_stream(s, c->P, c->ps, c->ss, c->queue[0], b.n_first, dispatch_base, b.media_stream));
+    } else if (plan::runs_streams(sd.kind)) {
+        TIMED(c, VPT_K_PRIMARY, launch_raygen_stream(s, c->P, c->ps, c->ss, c->queue[0], b.n_first, dispatch_base, sd.kind == Kind::MediaStreams));
         launch_stream_begin(s, c->sctr, b.n_first, n_slots);
         b.parity = 0;
     } else {
@@ -783,22 +732,23 @@ int batch_begin(vpt_ctx* c, uint32_t frames, uint32_t dispatch_base, BatchState&
 
 int batch_bounces(vpt_ctx* c, BatchState& b, uint32_t bounces) {
     hipStream_t s = c->stream;
-    const bool count = b.count, sorted = b.sorted, overlap = b.overlap;
+    const Kind kind = b.sd.kind;
+    const bool count = b.count, sorted = kind == Kind::StreamsSorted, overlap = b.sd.overlap, stream = plan::runs_streams(kind);
     uint32_t& parity = b.parity;
     const uint32_t n_slots = b.n_first;   // (upper bound of a queue's live entries)
-    if (n_slots == 0 || b.whole) return VPT_OK;   // (a whole-path batch has no bounces left to launch)
+    if (n_slots == 0 || kind == Kind::Whole) return VPT_OK;   // (a whole-path batch has no bounces left to launch)
     for (uint32_t j = 0; j < bounces; j++) {
         b.iter++;
-        if (b.fused) {  // no reset kernel in between: the bounce kernels rotate three queue-size words
+        if (kind == Kind::Fused) {  // no reset kernel in between: the bounce kernels rotate three queue-size words
             const int grid = (c->tail_blocks > 0 && b.iter >= 3) ? c->tail_blocks : c->primary_blocks;   // (b.iter counts bounce 0)
             TIMED(c, VPT_K_BOUNCE, launch_bounce(s, (uint32_t)grid, c->lds_scene, count, false, c->dsc, c->P, c->ps, c->ss, c->queue[parity], c->queue[parity ^ 1u], c->ctr, parity, 0u, 0u, b.k3, c->scene_plain));
             parity ^= 1u; b.k3 = (b.k3 + 1u) % 3u;
             continue;
         }
         // a memory-resident BVH runs the staged pipeline on the vote-scheduled traversal kernels and compact streams
-        // (kernels_trace.hip, kernels_stream.hip); round 1's stage kernels serve LDS-resident scenes forced into the staged
-        // pipeline and VPT_PIPELINE_STAGED_R1
-        if (b.media_stream) {   // distance -> scatter -> extend -> shade -> sky rays, light rays -> tail (kernels_media.hip), one stream
+        // (kernels_trace.hip, kernels_stream.hip) — a scene that rides in LDS and is forced into the staged pipeline too; round 1's
+        // stage kernels serve VPT_PIPELINE_STAGED_R1 only
+        if (kind == Kind::MediaStreams) {   // distance -> scatter -> extend -> shade -> sky rays, light rays -> tail (kernels_media.hip), one stream
             launch_prepare_stream(s, c->sctr, parity);
             TraceArgs a{};
             a.ro = c->ss.RA[parity]; a.rd = c->ss.RB[parity]; a.order = nullptr; a.valid = c->queue[parity]; a.hit = c->ss.SH; a.hinst = c->ss.SHI; a.cls = nullptr;
@@ -818,14 +768,14 @@ int batch_bounces(vpt_ctx* c, BatchState& b, uint32_t bounces) {
             parity ^= 1u;
             continue;
         }
-        if (b.stream && b.finished) continue;   // k_finish has been enqueued: nothing is alive behind it
-        if (b.stream && b.finish_at != 0u && b.iter > b.finish_at) {   // (b.iter counts this bounce): the rest of the batch in one launch
+        if (stream && b.finished) continue;   // k_finish has been enqueued: nothing is alive behind it
+        if (stream && b.sd.finish_at != 0u && b.iter > b.sd.finish_at) {   // (b.iter counts this bounce): the rest of the batch in one launch
             if (b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0)); b.join_pending = false; }   // pathLight of the queue's entries is final behind the previous join
             TIMED(c, VPT_K_BOUNCE, launch_finish(s, (uint32_t)c->finish_blocks, count, c->dsc, c->P, c->ps, c->ss, c->queue[parity], c->sctr, c->ctr, parity));
             b.finished = true;
             continue;
         }
-        if (b.stream) {   // stream pipeline: extend -> classify -> shade per class (streams out) -> sky rays, light rays -> join
+        if (stream) {   // stream pipeline: extend -> classify -> shade per class (streams out) -> sky rays, light rays -> join
             launch_prepare_stream(s, c->sctr, parity);
             TraceArgs a{};
             a.ro = c->ss.RA[parity]; a.rd = c->ss.RB[parity]; a.order = nullptr; a.valid = c->queue[parity]; a.hit = c->ss.SH; a.hinst = c->ss.SHI; a.cls = c->cls_q;
@@ -855,7 +805,7 @@ int batch_bounces(vpt_ctx* c, BatchState& b, uint32_t bounces) {
             }
             // regeneration: fresh camera rays into the room the ended paths left in the next queue (entries behind the ones the join of this
             // bounce addresses, so it may run beside the shadow kernels and the join)
-            if (b.regen) TIMED(c, VPT_K_PRIMARY, launch_refill(s, 2048u, c->P, c->ps, c->ss, c->queue[parity ^ 1u], c->sctr, parity ^ 1u, b.n_first, b.dispatch_base));
+            if (b.sd.regen) TIMED(c, VPT_K_PRIMARY, launch_refill(s, 2048u, c->P, c->ps, c->ss, c->queue[parity ^ 1u], c->sctr, parity ^ 1u, b.n_first, b.dispatch_base));
             TIMED(c, VPT_K_SHADOW, launch_trace_shadow(sb, (uint32_t)c->shadow_blocks, false, count, dsc_shadow, c->ss, c->ctr, c->sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
             TIMED(c, VPT_K_SHADOW, launch_trace_shadow(sb, (uint32_t)c->shadow_blocks, true, count, dsc_shadow, c->ss, c->ctr, c->sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
             TIMED(c, VPT_K_JOIN, launch_join(sb, (uint32_t)c->join_blocks, c->P, c->ps, c->ss, c->sctr, c->queue[parity], c->queue[parity ^ 1u], parity));
@@ -881,13 +831,14 @@ int batch_resolve(vpt_ctx* c, BatchState& b) {
     hipStream_t s = c->stream;
     if (b.n_slots == 0) return VPT_OK;
 #if VPT_LAB
-    if (!b.fused && !b.stream) launch_fold(s, c->ctr);
+    if (b.sd.kind == Kind::StagedR1) launch_fold(s, c->ctr);
 #endif
-    if (b.overlap && b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0)); b.join_pending = false; }   // the resolve reads the frame sums the join writes
-    const uint32_t* guard = b.fused ? &c->ctr->alive3[b.k3] : b.stream ? &c->sctr->alive[b.parity].v : &c->ctr->ray_count[b.parity];
+    if (b.sd.overlap && b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0)); b.join_pending = false; }   // the resolve reads the frame sums the join writes
+    const bool stream = plan::runs_streams(b.sd.kind);
+    const uint32_t* guard = plan::runs_fused(b.sd.kind) ? &c->ctr->alive3[b.k3] : stream ? &c->sctr->alive[b.parity].v : &c->ctr->ray_count[b.parity];
     TIMED(c, VPT_K_RESOLVE, launch_resolve(s, c->P, c->ps, c->image, b.frames, b.dispatch_base, guard));
     HIPCHK(c, hipMemcpyAsync(&c->h_ctr->ctr, c->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-    if (b.stream) {  // the exact number of live paths, and the queue length (holes included), which must fit the queue allocation
+    if (stream) {  // the exact number of live paths, and the queue length (holes included), which must fit the queue allocation
         HIPCHK(c, hipMemcpyAsync(&c->h_ctr->alive[0], &c->sctr->alive[b.parity].v, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(&c->h_ctr->queue_len[0], &c->sctr->queue_len[b.parity].v, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(&c->h_ctr->refill_next, &c->sctr->refill_next, 4, hipMemcpyDeviceToHost, s));
@@ -924,11 +875,11 @@ int batch_check(vpt_ctx* c, BatchState& b, uint32_t* alive) {
     c->stats.tris_tested = counted ? h.stat_tris : 0;
     c->stats.shadow_nodes_visited = counted ? h.stat_shadow_nodes : 0;
     c->stats.shadow_tris_tested = counted ? h.stat_shadow_tris : 0;
-    uint32_t n = b.fused ? h.alive3[b.k3] : h.ray_count[b.parity];
-    if (b.stream) {
+    uint32_t n = plan::runs_fused(b.sd.kind) ? h.alive3[b.k3] : h.ray_count[b.parity];
+    if (plan::runs_streams(b.sd.kind)) {
         n = c->h_ctr->alive[0];
         const uint64_t len = c->h_ctr->queue_len[0];
-        const uint64_t room = b.media_stream ? (uint64_t)c->media_frames * c->P.shard_pixels + c->stream_slack : (uint64_t)c->ps.capacity + c->stream_slack;
+        const uint64_t room = b.sd.kind == Kind::MediaStreams ? (uint64_t)c->media_frames * c->P.shard_pixels + c->stream_slack : (uint64_t)c->ps.capacity + c->stream_slack;
         if (len > room || len > (uint64_t)c->ps.capacity + c->stream_slack) { (void)hipStreamSynchronize(c->stream2); return fail(c, VPT_ERR_DEVICE, "internal: stream overflow"); }
     }
     if (n > b.n_first) { (void)hipStreamSynchronize(c->stream2); return fail(c, VPT_ERR_DEVICE, "internal: queue overflow"); }
@@ -947,8 +898,8 @@ int batch_finish(vpt_ctx* c, BatchState& b, bool resolve_enqueued) {
         if (rc) return rc;
         if (n == 0) break;
         // few paths left — and, in a regenerating batch, no sample left to start: the next launch finishes them
-        if (!(c->cfg.build_flags & VPT_BUILD_STREAMS_ONLY) && b.stream && !b.media_stream && (!b.regen || c->h_ctr->refill_next >= b.n_slots) && !b.finished && b.finish_at == 0u && n < kFinishBelowPaths) b.finish_at = (uint32_t)b.iter;
-        rc = batch_bounces(c, b, b.regen ? 8u : 4u);   // (a regenerating batch runs many more launches than max_depth: fewer host round trips)
+        if (b.sd.finisher && (!b.sd.regen || c->h_ctr->refill_next >= b.n_slots) && !b.finished && b.sd.finish_at == 0u && n < plan::kFinishBelowPaths) b.sd.finish_at = (uint32_t)b.iter;
+        rc = batch_bounces(c, b, b.sd.regen ? 8u : 4u);   // (a regenerating batch runs many more launches than max_depth: fewer host round trips)
         if (rc) return rc;
     }
     HIPCHK(c, hipGetLastError());
@@ -956,12 +907,15 @@ int batch_finish(vpt_ctx* c, BatchState& b, bool resolve_enqueued) {
 }
 
 int render_batch(vpt_ctx* c, uint32_t frames, uint32_t dispatch_base) {
+    plan::Schedule sd;
+    int rc = decide_batch(c, facts_of(c), frames, dispatch_base, false, sd);
+    if (rc) return rc;
     BatchState b;
-    int rc = batch_begin(c, frames, dispatch_base, b);
+    rc = batch_begin(c, sd, frames, dispatch_base, b);
     if (rc) return rc;
     if (b.n_slots == 0) return VPT_OK;
     // the host looks at the queue after max_depth bounces (when a surface-only batch is done) or after eight, whichever comes first
-    const uint32_t first = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(b.min_bounces - (b.fused ? 1 : 0), 1), 8);
+    const uint32_t first = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(b.min_bounces - (plan::runs_fused(sd.kind) ? 1 : 0), 1), 8);
     rc = batch_bounces(c, b, first);
     if (rc) return rc;
     rc = batch_finish(c, b, false);
@@ -992,7 +946,7 @@ int drain(vpt_ctx* c) {
     for (vpt_ctx* L : c->lanes)
         if (L) {
             HIPCHK(c, hipStreamSynchronize(L->stream));
-            if (L->last_fixed_valid && (L->last_fixed.stream ? L->h_ctr->alive[0] : L->h_ctr->ctr.alive3[L->last_fixed.k3]) != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
+            if (L->last_fixed_valid && (plan::runs_streams(L->last_fixed.sd.kind) ? L->h_ctr->alive[0] : L->h_ctr->ctr.alive3[L->last_fixed.k3]) != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
             L->last_fixed_valid = false;
             for (int k = 0; k < VPT_KERNEL_COUNT; k++) { c->stats.kernel_launches[k] += L->stats.kernel_launches[k]; L->stats.kernel_launches[k] = 0; }
             c->stats.graph_launches += L->stats.graph_launches; L->stats.graph_launches = 0;
@@ -1003,10 +957,10 @@ int drain(vpt_ctx* c) {
     if (c->last_fixed_valid) {   // a fixed-schedule batch on the main lane: nothing may have outlived it either (its guarded resolve would have been a no-op)
         c->last_fixed_valid = false;
         const BatchState& f = c->last_fixed;
-        if (f.stream) {
+        if (plan::runs_streams(f.sd.kind)) {
             if (c->h_ctr->alive[0] != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
             if ((uint64_t)c->h_ctr->queue_len[0] > (uint64_t)c->ps.capacity + c->stream_slack) return fail(c, VPT_ERR_DEVICE, "internal: stream overflow");
-        } else if (f.fused && c->h_ctr->ctr.alive3[f.k3] != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
+        } else if (plan::runs_fused(f.sd.kind) && c->h_ctr->ctr.alive3[f.k3] != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
     }
     collect_timing(c);
     update_ray_stats(c);   // fixed-schedule batches copy their counters to pinned memory too
@@ -1018,15 +972,16 @@ void destroy_graph(vpt_ctx* c) {
     c->graph = nullptr; c->graph_gen = 0;
 }
 // A whole batch as a fixed schedule: bounce 0 (or the camera rays) and `bounces_total` bounces in all; the guarded resolve is the caller's.
-int enqueue_fixed(vpt_ctx* c, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, BatchState& b) {
-    int rc = batch_begin(c, frames, dispatch_base, b);
+int enqueue_fixed(vpt_ctx* c, const plan::Schedule& sd, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, BatchState& b) {
+    int rc = batch_begin(c, sd, frames, dispatch_base, b);
     if (rc) return rc;
     if (b.n_slots == 0) return VPT_OK;
-    return batch_bounces(c, b, b.fused ? bounces_total - 1u : bounces_total);
+    return batch_bounces(c, b, plan::runs_fused(sd.kind) ? bounces_total - 1u : bounces_total);
 }
 // The same through a captured hipGraph: the fused pipeline's batch (memset, bounce 0, bounces) with the first dispatch index read from
-// device memory, captured once per (state, frames, bounces) and replayed.  b: the batch as it stands before its resolve.
-int enqueue_graph(vpt_ctx* c, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, bool* used, BatchState& b) {
+// device memory, captured once per (state, frames, bounces) and replayed.  b: the batch as it stands before its resolve.  f: the owner's
+// facts — the captured batch is decided for ONE stream (no shadow / join overlap on stream2).
+int enqueue_graph(vpt_ctx* c, const plan::Facts& f, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, bool* used, BatchState& b) {
     *used = false;
     if (c->graph_broken) return VPT_OK;
     if (!c->graph || c->graph_gen != c->state_gen || c->graph_frames != frames || c->graph_bounces != bounces_total) {
@@ -1036,9 +991,9 @@ int enqueue_graph(vpt_ctx* c, uint32_t frames, uint32_t dispatch_base, uint32_t 
         c->P.dispatch_base_dev = c->d_dispatch_base;
         hipGraph_t g = nullptr;
         bool ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        c->capturing = true;
-        int rc = ok ? enqueue_fixed(c, frames, 0u, bounces_total, c->graph_batch) : VPT_ERR_DEVICE;
-        c->capturing = false;
+        plan::Schedule sd;
+        int rc = ok ? decide_batch(c, f, frames, 0u, true, sd) : VPT_ERR_DEVICE;
+        if (rc == VPT_OK) rc = enqueue_fixed(c, sd, frames, 0u, bounces_total, c->graph_batch);
         if (ok && hipStreamEndCapture(c->stream, &g) != hipSuccess) { ok = false; g = nullptr; }
         c->P.dispatch_base_dev = nullptr;
         for (int k = 0; k < VPT_KERNEL_COUNT; k++) { c->graph_kernel_launches[k] = c->stats.kernel_launches[k] - before[k]; c->stats.kernel_launches[k] = before[k]; }
@@ -1099,13 +1054,14 @@ vpt_ctx* get_lane(vpt_ctx* c, int k) {
     c->lanes[k] = L;
     return L;
 }
-// What a lane borrows from its owner, refreshed before every use: scene tables, parameters, camera, the accumulation image.
+// What a lane borrows from its owner, refreshed before every use: scene tables, parameters, camera, the accumulation image — what its
+// LAUNCHES read.  How its batch runs is decided from the owner's facts (decide_batch), not from copies kept here.
 int sync_lane(vpt_ctx* c, vpt_ctx* L) {
     L->P = c->P; L->P.dispatch_base_dev = nullptr;
     L->dsc = c->dsc; L->dsc.stack_overflow = (uint32_t*)L->lane_spill;
     L->params = c->params;
-    L->lds_scene = c->lds_scene; L->scene_plain = c->scene_plain; L->depth_bounded = c->depth_bounded; L->has_scene = true;
-    L->primary_blocks = c->primary_blocks; L->whole_blocks = c->whole_blocks; L->lab_whole_frames = c->lab_whole_frames; L->lab_whole_sched = c->lab_whole_sched;
+    L->lds_scene = c->lds_scene; L->scene_plain = c->scene_plain;
+    L->primary_blocks = c->primary_blocks; L->whole_blocks = c->whole_blocks; L->lab_whole_sched = c->lab_whole_sched;
     L->vote_blocks = c->vote_blocks; L->shadow_blocks = c->shadow_blocks; L->shade_stream_blocks = c->shade_stream_blocks; L->join_blocks = c->join_blocks; L->finish_blocks = c->finish_blocks;
     L->max_blocks = c->max_blocks; L->vote_param = c->vote_param; L->class_present = c->class_present; L->stack_overflow2 = (uint32_t*)L->lane_spill;   // (a lane's batches run on one stream: no second region in use)
     L->image = c->image;
@@ -1525,7 +1481,7 @@ int vpt_set_params(vpt_ctx* c, const vpt_params* p) {
 int vpt_set_volumes(vpt_ctx* c, const vpt_volume* v, uint32_t count) {
     if (!c || (count && !v)) return VPT_ERR_INVALID_ARGUMENT;
     if (count > VPT_MAX_VOLUMES) return fail(c, VPT_ERR_LIMIT, "more than VPT_MAX_VOLUMES volumes");
-    if (count && (c->cfg.pipeline > VPT_PIPELINE_STAGED || (c->cfg.pipeline == VPT_PIPELINE_STAGED && c->has_scene && c->lds_scene)))
+    if (count && !plan::media_supported(facts_of(c)))
         return fail(c, VPT_ERR_UNSUPPORTED, "volumes run on the fused pipeline or, for a scene whose BVH lives in memory, on the streams (VPT_PIPELINE_AUTO, _FUSED, _STAGED)");
     for (uint32_t i = 0; i < count; i++) {
         if (v[i].density_data_index < -1 || v[i].density_data_index >= (int)c->grids.size())
@@ -1607,7 +1563,7 @@ void vpt_default_atmosphere(vpt_atmosphere* a) {  // PathTracer.h:222-232
 }
 int vpt_set_atmosphere(vpt_ctx* c, const vpt_atmosphere* a) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
-    if (a && (c->cfg.pipeline > VPT_PIPELINE_STAGED || (c->cfg.pipeline == VPT_PIPELINE_STAGED && c->has_scene && c->lds_scene)))
+    if (a && !plan::media_supported(facts_of(c)))
         return fail(c, VPT_ERR_UNSUPPORTED, "the atmosphere runs on the fused pipeline or, for a scene whose BVH lives in memory, on the streams (VPT_PIPELINE_AUTO, _FUSED, _STAGED)");
     if (a && (!(a->planet_radius > 0.0f) || !(a->atmosphere_height > 0.0f) || !(a->rayleigh_density_falloff > 0.0f) || !(a->mie_density_falloff > 0.0f) ||
               !(a->ozone_density_falloff > 0.0f)))
@@ -1661,7 +1617,7 @@ int next_batch(vpt_ctx* c, uint32_t left, uint32_t* nf) {
         if ((rc = ensure_path_buffers(c, n))) return rc;
     }
     n = plan::fit_batch(policy_of(c), plan_state(c), n);
-    if (media_on_streams(c)) {   // media on the streams: the batch is what the media streams hold
+    if (plan::media_on_streams(facts_of(c))) {   // media on the streams: the batch is what the media streams hold
         int rm = ensure_media_buffers(c);
         if (rm) return rm;
         n = std::min(n, c->media_frames);
@@ -1712,27 +1668,18 @@ int vpt_render_async(vpt_ctx* c, uint32_t dispatches, int* done, uint64_t* ticke
         uint32_t nf = 0;
         if ((rc = next_batch(c, left, &nf))) return rc;
         if (nf == 0) { if (done) *done = 1; break; }
-        const uint64_t bounds = (uint64_t)c->P.max_depth * c->P.samples_per_frame;
-        const bool vol = !c->volumes.empty() || c->dsc.atm_on;
-        // a fixed schedule: every path has ended after `bounds` bounces, whatever the random numbers say
-        // ... or the batch is ONE launch that runs every path to its end (k_whole), whatever max_depth is
-        const bool whole = whole_applies(c, nf);
-        const bool fused_auto = (whole || c->cfg.pipeline == VPT_PIPELINE_FUSED || (c->cfg.pipeline == VPT_PIPELINE_AUTO && c->lds_scene)) && !vol;
-        const bool streams_pipe = !vol && !fused_auto && (c->cfg.pipeline == VPT_PIPELINE_AUTO || c->cfg.pipeline == VPT_PIPELINE_STAGED || c->cfg.pipeline == VPT_PIPELINE_STAGED_SORTED);
-        // a small batch of the streams pipeline ends in ONE launch that runs every path to its end (k_finish): a fixed schedule whatever max_depth is
-        const bool stream_finish = streams_pipe && !(c->cfg.build_flags & VPT_BUILD_STREAMS_ONLY) && nf <= c->resident_alloc && (uint64_t)nf * c->P.shard_pixels <= kFinishSmallBatchPaths;
-        const bool fixed = whole || stream_finish || (c->depth_bounded && !vol && bounds <= VPT_ASYNC_MAX_BOUNCES && nf <= c->resident_alloc);   // (a regenerating batch has no fixed length)
-        const uint32_t enq = stream_finish ? kFinishAfterBounces + 1u : (uint32_t)std::min<uint64_t>(bounds, VPT_ASYNC_MAX_BOUNCES);
         const uint32_t base = (uint32_t)c->dispatch_count;
-        const bool plain_launches = c->cfg.profile || c->cfg.count_traversal || c->P.split != 1u;
-        // the streams pipeline's fixed batch (a frame per call on a scene whose BVH lives in memory: seven launches per bounce, every one of them short)
-        // goes over the lanes and is replayed from a captured graph too — each lane's batch on ONE stream
-        const bool stream_fixed = fixed && streams_pipe && c->cfg.pipeline != VPT_PIPELINE_STAGED_SORTED;
         if (c->graph_streak_gen == c->state_gen) c->graph_streak++; else { c->graph_streak = 0; c->graph_streak_gen = c->state_gen; }
-        // the fused pipeline's fixed 1-frame batch goes to the next lane (vpt_ctx::lanes); asked for again with nothing changed since the
-        // last two calls it is replayed from the lane's captured graph
+        const plan::Facts f = facts_of(c);
+        plan::Schedule sd;
+        if ((rc = decide_batch(c, f, nf, base, false, sd))) return rc;
+        const plan::AsyncShape shape = plan::async_shape(f, sd, nf, c->resident_alloc, c->graph_streak);
+        const bool fixed = shape.fixed;
+        const uint32_t enq = shape.bounces_to_enqueue;
+        // the fixed 1-frame batch goes to the next lane (vpt_ctx::lanes); asked for again with nothing changed since the last two calls it
+        // is replayed from the lane's captured graph
         vpt_ctx* X = c;
-        if (fixed && (fused_auto || stream_fixed) && !plain_launches && nf == 1u) {
+        if (shape.lanes_ok) {
             const uint32_t max_lanes = std::max(1u, std::min(c->lab_lanes, 3u));
             vpt_ctx* idle = nullptr;
             uint32_t have = 1;
@@ -1749,29 +1696,31 @@ int vpt_render_async(vpt_ctx* c, uint32_t dispatches, int* done, uint64_t* ticke
                 idle = k == 0u ? c : c->lanes[k - 1];
             }
             X = idle;
-            if (X != c) { const int rc_lane = sync_lane(c, X); if (rc_lane != VPT_OK) return rc_lane; }
+            if (X != c) {   // the lane runs the schedule its owner decides: the owner's facts, the lane's buffers
+                const int rc_lane = sync_lane(c, X); if (rc_lane != VPT_OK) return rc_lane;
+                if ((rc = decide_batch(X, f, nf, base, false, sd))) { c->err = X->err; return rc; }
+            }
         }
         // a batch on the main lane behind pipelined frames: their resolves come first (frame order), and the records it overwrites are the main lane's own
         if (X == c && c->order_lane && c->order_lane != c) HIPCHK(c, hipStreamWaitEvent(c->stream, c->order_lane->ev_resolved, 0));
         BatchState b;
         bool graphed = false;
-        const bool pipelined = fixed && fused_auto && !plain_launches && nf == 1u && c->graph_streak >= 2u;
         // Frames in steady accumulation share the chip: each lane's kernels take a third of the persistent grid (one block per CU of the
         // three the fused kernel's LDS allows), so that the three lanes' chains are co-resident and the tail of one frame — launches that are
         // bounded by one bounce's latency, not by throughput — runs beside the first bounces of the next two.  (A full-size grid fills every
         // CU's LDS and keeps the other lanes' blocks out until it retires.)
         const int full_grid = X->primary_blocks;
         auto part = [&](uint32_t div) { return std::max(c->cu_count, (c->primary_blocks / (int)std::max(1u, div) / std::max(c->cu_count, 1)) * c->cu_count); };
-        if (pipelined) {
+        if (shape.partial_grids) {
             X->primary_blocks = part(std::max(1u, c->lab_lane_grid));
             X->tail_blocks = c->lab_tail_grid > 1u ? std::min(X->primary_blocks, part(c->lab_tail_grid)) : 0;
         }
-        if (fixed && (fused_auto || stream_fixed) && !plain_launches && c->graph_streak >= 2u) {
-            rc = enqueue_graph(X, nf, base, enq, &graphed, b);
+        if (shape.graph_ok) {
+            rc = enqueue_graph(X, f, nf, base, enq, &graphed, b);
             if (rc) { X->primary_blocks = full_grid; X->tail_blocks = 0; if (X != c) c->err = X->err; return rc; }
         }
         if (!graphed) {
-            rc = enqueue_fixed(X, nf, base, enq, b);
+            rc = enqueue_fixed(X, sd, nf, base, enq, b);
             if (rc) { X->primary_blocks = full_grid; X->tail_blocks = 0; if (X != c) c->err = X->err; return rc; }
         }
         X->primary_blocks = full_grid; X->tail_blocks = 0;
