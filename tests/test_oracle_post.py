@@ -2,18 +2,7 @@
 import numpy as np
 import pytest
 
-
-def mip_sizes(w, h):
-    out = []
-    for _ in range(10):  # PostProcessor.cpp:136-157
-        out.append((w, h))
-        w -= w % 2
-        h -= h % 2
-        w //= 2
-        h //= 2
-        if w < 2 or h < 2:
-            break
-    return out
+from post_plan import mip_sizes
 
 
 def test_mip_chain_matches_survey():
