@@ -302,6 +302,15 @@ struct Builder {
 inline int32_t leaf_code(int first, int count) { return ~(int32_t)(((uint32_t)first << 3) | (uint32_t)(count - 1)); }
 }  // namespace
 
+float bvh_max_abs_coord(const std::vector<BvhTri>& tris_in) {
+    float maxabs = 0.0f;
+    for (const BvhTri& t : tris_in)
+        for (int a = 0; a < 3; a++) {   // the three vertices as the builder's boxes hold them: v0, v0 + e1, v0 + e2
+            const float p0 = t.v0[a], p1 = t.v0[a] + t.e1[a], p2 = t.v0[a] + t.e2[a];
+            maxabs = std::max(maxabs, std::max(std::fabs(p0), std::max(std::fabs(p1), std::fabs(p2))));
+        }
+    return maxabs;
+}
 void build_bvh(const std::vector<BvhTri>& tris_in, std::vector<BvhNode>& nodes_out, std::vector<BvhNodeWide>& wide_out, std::vector<BvhTri>& tris_out, int* depth_out,
                std::vector<BvhNode8>* nodes8_out, bool spatial_splits, bool parallel) {
     BvhBuildOptions opt; opt.spatial_splits = spatial_splits; opt.parallel = parallel; opt.nodes8 = nodes8_out;
@@ -318,14 +327,14 @@ void build_bvh_ex(const std::vector<BvhTri>& tris_in, std::vector<BvhNode>& node
     b.parallel = opt.parallel;
     b.bins = opt.bins < 2 ? 2 : (opt.bins > kMaxBins ? kMaxBins : opt.bins);
     b.refs.resize(tris_in.size());
-    float maxabs = 0.0f;
+    const float maxabs = bvh_max_abs_coord(tris_in);
     for (size_t i = 0; i < tris_in.size(); i++) {
         const BvhTri& t = tris_in[i];
         float p[3][3];
         for (int a = 0; a < 3; a++) { p[0][a] = t.v0[a]; p[1][a] = t.v0[a] + t.e1[a]; p[2][a] = t.v0[a] + t.e2[a]; }
         Ref& r = b.refs[i];
         r.b.reset(); r.b.grow(p[0]); r.b.grow(p[1]); r.b.grow(p[2]);
-        for (int a = 0; a < 3; a++) { r.c[a] = 0.5f * (r.b.lo[a] + r.b.hi[a]); maxabs = std::max(maxabs, std::max(std::fabs(r.b.lo[a]), std::fabs(r.b.hi[a]))); }
+        for (int a = 0; a < 3; a++) { r.c[a] = 0.5f * (r.b.lo[a] + r.b.hi[a]); }
         r.tri = (uint32_t)i;
     }
     // Conservative padding so a box test can never cull a triangle the shared ray_triangle() accepts.

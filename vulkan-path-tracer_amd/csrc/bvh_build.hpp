@@ -13,6 +13,9 @@ namespace vpt {
 // nodes8_out (optional): the same binary tree collapsed eight-wide with octant-ordered slots, over the same tris_out.
 void build_bvh(const std::vector<BvhTri>& tris_in, std::vector<BvhNode>& nodes_out, std::vector<BvhNodeWide>& wide_out, std::vector<BvhTri>& tris_out, int* depth_out,
                std::vector<BvhNode8>* nodes8_out = nullptr, bool spatial_splits = false, bool parallel = true);
+// Largest |coordinate| of the triangles' boxes, as the builder computes it: the boxes are padded by 2e-5 x this + 1e-6, and the guard of the
+// fma box test (slab.hpp, DeviceScene::scene_extent) is stated in terms of the same number.  0 for no triangles.
+float bvh_max_abs_coord(const std::vector<BvhTri>& tris_in);
 // The same with every knob of the builder study (tests/tools/vote_sim.cpp, profiles/r06_builder_study.md) and the trace lab's trees:
 struct BvhBuildOptions {
     bool spatial_splits = false, parallel = true;

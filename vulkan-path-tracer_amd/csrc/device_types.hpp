@@ -150,6 +150,8 @@ struct DeviceScene {
     const BvhNode* nodes4s;         // split-order four-wide tree over the same triangles (trace lab VPT_TRACE_VOTE4S only; nullptr unless built)
     const BvhTri* tris;
     uint32_t node_count, tri_count;
+    float scene_extent;             // largest |coordinate| of the scene's triangles (bvh_max_abs_coord: what the builder sizes the boxes' padding by);
+                                    // origins within kSlabFmaReach times it take the one-fma-per-plane box test on a tree in LDS (slab.hpp)
     const vpt_vertex* vertices;
     const uint32_t* indices;
     const MeshDesc* meshes;

@@ -59,7 +59,7 @@ __device__ inline void stage_scene(const DeviceScene& sc, float4* lds_nodes, flo
 template <bool LDS_SCENE, bool COUNT>
 __device__ inline bool trace_any(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, float tmin,
                                  float tmax, const TravStack& stack, HitRec& h, TravStats& st) {
-    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
+    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
     GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
     return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st);
 }
@@ -70,7 +70,7 @@ template <bool LDS_SCENE, bool COUNT>
 __device__ inline bool sky_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const TravStack& stack, TravStats& st, bool rq) {
     const float tmin = rq ? 0.0001f : 0.00001f, tmax = rq ? 1000000.0f : 1000.0f;
     if (!rq) d = normalize(d);
-    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
+    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
     GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
     return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st);
 }
@@ -78,7 +78,7 @@ template <bool LDS_SCENE, bool COUNT>
 __device__ inline bool light_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const TravStack& stack, TravStats& st) {
     uint32_t slot = sc.tri_slot_of_gid[gid];
     if (slot == 0xffffffffu) return false;  // the sampled light triangle is a sliver: nothing can hit it
-    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
+    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
     GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
     return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st);
 }
@@ -784,7 +784,7 @@ template <bool COUNT>
 __device__ __forceinline__ bool lds_closest_vote(const LdsSceneSrc& src, V3 o, V3 d, float tmin, float tmax, TravStack stack, HitRec& best, TravStats& st) {
     best.t = tmax; best.u = 0.0f; best.v = 0.0f; best.prim = 0xffffffffu; best.inst = 0xffffffffu; best.gid = 0xffffffffu; best.slot = 0;
     bool found = false;
-    const RaySlab slab = make_slab(o, d);
+    const RaySlabWide slab = make_slab<false>(src, o, d);
     stack.sp = 0;
     int cur = 0;   // root is inner node 0
     while (true) {
@@ -831,7 +831,7 @@ __device__ __forceinline__ bool lds_closest_vote(const LdsSceneSrc& src, V3 o, V
 template <bool COUNT, bool LIGHT>
 __device__ __forceinline__ bool lds_occluded_vote(const LdsSceneSrc& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, TravStack stack, TravStats& st) {
     const float tlimit = LIGHT ? t_e : tmax;
-    const RaySlab slab = make_slab(o, d);
+    const RaySlabWide slab = make_slab<false>(src, o, d);
     stack.sp = 0;
     int cur = 0;
     bool occluded = false;
@@ -872,17 +872,17 @@ __device__ __forceinline__ bool lds_occluded_vote(const LdsSceneSrc& src, V3 o, 
 }
 // sky_visible / light_visible of k_whole's non-validating instantiations (the interval and direction rules of sky_visible above)
 template <bool COUNT>
-__device__ __forceinline__ bool sky_visible_vote(const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const TravStack& stack, TravStats& st, bool rq) {
+__device__ __forceinline__ bool sky_visible_vote(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const TravStack& stack, TravStats& st, bool rq) {
     const float tmin = rq ? 0.0001f : 0.00001f, tmax = rq ? 1000000.0f : 1000.0f;
     if (!rq) d = normalize(d);
-    LdsSceneSrc src{lds_nodes, lds_tris, false};
+    LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * sc.scene_extent};
     return !lds_occluded_vote<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st);
 }
 template <bool COUNT>
 __device__ __forceinline__ bool light_visible_vote(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const TravStack& stack, TravStats& st) {
     const uint32_t slot = sc.tri_slot_of_gid[gid];
     if (slot == 0xffffffffu) return false;  // the sampled light triangle is a sliver: nothing can hit it
-    LdsSceneSrc src{lds_nodes, lds_tris, false};
+    LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * sc.scene_extent};
     float4 a, b, c;
     src.tri((int)slot, a, b, c);   // traverse.hpp closest_is: the sampled triangle by its own record first, then the search for anything that beats it
     if (COUNT) st.tris++;
@@ -987,7 +987,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                 constexpr bool kVote = VPT_WHOLE_VOTE != 0 && !STRICT;   // vote-scheduled searches on the tree in LDS (above); the validating instantiations keep the per-lane loops
                 if (o.want_sky) {
                     bool vis;
-                    if constexpr (kVote) vis = sky_visible_vote<COUNT>(lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq);
+                    if constexpr (kVote) vis = sky_visible_vote<COUNT>(sc, lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq);
                     else vis = sky_visible<true, COUNT>(sc, lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq);
                     if (vis) E = E + o.csky;
                     nrays++;
@@ -1063,7 +1063,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
             HitRec hr;
             bool hit = false;
             if (has_ray) {
-                if constexpr (VPT_WHOLE_VOTE != 0 && !STRICT) { LdsSceneSrc src{lds_nodes, lds_tris, false}; hit = lds_closest_vote<COUNT>(src, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st); }
+                if constexpr (VPT_WHOLE_VOTE != 0 && !STRICT) { LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * sc.scene_extent}; hit = lds_closest_vote<COUNT>(src, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st); }
                 else hit = trace_any<true, COUNT>(sc, lds_nodes, lds_tris, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st);
             }
             const unsigned long long mh = __ballot(has_ray && hit);

@@ -14,6 +14,7 @@
 //   carries a 4-ulp slack) — a box test only ever prunes, it never decides a hit.
 #pragma once
 #include "device_types.hpp"
+#include "slab.hpp"
 
 namespace vpt {
 
@@ -90,6 +91,7 @@ struct LdsSceneSrc {
     const float4* nodes;  // LDS, BvhNodeWide
     const float4* tris;   // LDS
     bool strict;          // DeviceScene::strict_hits
+    float reach;          // kSlabFmaReach * DeviceScene::scene_extent: origins within it may take the fma form of the box test (slab.hpp)
     __device__ inline void node(int i, NodeDataWide& n) const {
         const float4* p = nodes + i * 8;
         n.minx = p[0]; n.miny = p[1]; n.minz = p[2]; n.maxx = p[3]; n.maxy = p[4]; n.maxz = p[5];
@@ -102,28 +104,32 @@ struct LdsSceneSrc {
     }
 };
 
-__device__ inline float fmin_(float a, float b) { return __builtin_fminf(a, b); }
-__device__ inline float fmax_(float a, float b) { return __builtin_fmaxf(a, b); }
-constexpr float kMissT = 3.0e38f;
+// (fmin_, fmax_, kMissT, safe_inverse and the slab test of an fp32 box: slab.hpp)
 
-__device__ inline V3 safe_inverse(V3 d) {
-    // a zero component would give 0*inf = NaN in the slab test: clamp its reciprocal to +-1e30
-    V3 inv;
-    inv.x = (vptfp::fabs_(d.x) > 1e-30f) ? 1.0f / d.x : (vptfp::f2u(d.x) >> 31 ? -1e30f : 1e30f);
-    inv.y = (vptfp::fabs_(d.y) > 1e-30f) ? 1.0f / d.y : (vptfp::f2u(d.y) >> 31 ? -1e30f : 1e30f);
-    inv.z = (vptfp::fabs_(d.z) > 1e-30f) ? 1.0f / d.z : (vptfp::f2u(d.z) >> 31 ? -1e30f : 1e30f);
-    return inv;
-}
-
-// Per-ray constants of the slab test: reciprocal direction and which plane byte is the near one per axis.
+// Per-ray constants of the slab test on quantised nodes: reciprocal direction and which plane byte is the near one per axis.
 struct RaySlab {
     V3 o, inv;
     bool negx, negy, negz;
 };
-__device__ inline RaySlab make_slab(V3 o, V3 d) {
+template <bool STRICT> __device__ inline RaySlab make_slab(const GlobalSceneSrc&, V3 o, V3 d) {
     RaySlab r;
     r.o = o; r.inv = safe_inverse(d);
     r.negx = r.inv.x < 0.0f; r.negy = r.inv.y < 0.0f; r.negz = r.inv.z < 0.0f;
+    return r;
+}
+// ... and on the fp32 nodes of a tree in LDS: oi = o * inv for the one-fma-per-plane form of the box test, and whether this search uses it.
+// `fused` is decided for the WAVE — every lane in the search has an origin the guard admits (slab.hpp slab_fma_ok) — so the choice is a
+// scalar branch per node step; either form is conservative, so a ray's hits do not depend on its neighbours' origins.  The validating (STRICT)
+// instantiations keep the subtract form and carry no guard: they are not where the time goes, and the library stays under its size bound.
+struct RaySlabWide {
+    V3 o, inv, oi;
+    bool fused;
+};
+template <bool STRICT> __device__ inline RaySlabWide make_slab(const LdsSceneSrc& src, V3 o, V3 d) {
+    RaySlabWide r;
+    r.o = o; r.inv = safe_inverse(d); r.oi = slab_oi(o, r.inv);
+    r.fused = !STRICT && __ballot(!slab_fma_ok(o, r.oi, src.reach)) == 0ull;
+    if (!r.fused) r.oi = vptfp::v3(0.0f, 0.0f, 0.0f);   // the subtract form: planes moved to the origin per node, then the same code (slab.hpp box_entry)
     return r;
 }
 template <int K> __device__ inline float byte_f(uint32_t w) { return (float)((w >> (8 * K)) & 0xffu); }  // v_cvt_f32_ubyteK
@@ -174,20 +180,18 @@ __device__ inline void node_entries_pk(const NodeData& n, const RaySlab& r, floa
     const vpt_f2 s01 = tf01 * slack, s23 = tf23 * slack;
     t0 = (tn0 <= s01.x) ? tn0 : kMissT; t1 = (tn1 <= s01.y) ? tn1 : kMissT; t2 = (tn2 <= s23.x) ? tn2 : kMissT; t3 = (tn3 <= s23.y) ? tn3 : kMissT;
 }
-// fp32 nodes: the plain slab test.
-__device__ inline float box_entry(float bx0, float by0, float bz0, float bx1, float by1, float bz1, V3 o, V3 inv, float tmin, float tlimit) {
-    float t0x = (bx0 - o.x) * inv.x, t1x = (bx1 - o.x) * inv.x;
-    float t0y = (by0 - o.y) * inv.y, t1y = (by1 - o.y) * inv.y;
-    float t0z = (bz0 - o.z) * inv.z, t1z = (bz1 - o.z) * inv.z;
-    float tn = fmax_(fmax_(fmin_(t0x, t1x), fmin_(t0y, t1y)), fmax_(fmin_(t0z, t1z), tmin));
-    float tf = fmin_(fmin_(fmax_(t0x, t1x), fmax_(t0y, t1y)), fmin_(fmax_(t0z, t1z), tlimit));
-    return (tn <= tf * 1.0000005f) ? tn : kMissT;
-}
-__device__ inline void node_entries(const NodeDataWide& n, const RaySlab& r, float tmin, float tlimit, float& t0, float& t1, float& t2, float& t3) {
-    t0 = box_entry(n.minx.x, n.miny.x, n.minz.x, n.maxx.x, n.maxy.x, n.maxz.x, r.o, r.inv, tmin, tlimit);
-    t1 = box_entry(n.minx.y, n.miny.y, n.minz.y, n.maxx.y, n.maxy.y, n.maxz.y, r.o, r.inv, tmin, tlimit);
-    t2 = box_entry(n.minx.z, n.miny.z, n.minz.z, n.maxx.z, n.maxy.z, n.maxz.z, r.o, r.inv, tmin, tlimit);
-    t3 = box_entry(n.minx.w, n.miny.w, n.minz.w, n.maxx.w, n.maxy.w, n.maxz.w, r.o, r.inv, tmin, tlimit);
+// fp32 nodes: the plain slab test (slab.hpp), one fma per plane (24 instead of 48 fp32 operations per node step) when the wave's origins allow it.
+__device__ inline void node_entries(const NodeDataWide& n, const RaySlabWide& r, float tmin, float tlimit, float& t0, float& t1, float& t2, float& t3) {
+    float4 minx = n.minx, miny = n.miny, minz = n.minz, maxx = n.maxx, maxy = n.maxy, maxz = n.maxz;
+    if (!r.fused) {   // box_entry(): the 24 subtractions here, oi == 0 behind them
+        minx.x -= r.o.x; minx.y -= r.o.x; minx.z -= r.o.x; minx.w -= r.o.x; maxx.x -= r.o.x; maxx.y -= r.o.x; maxx.z -= r.o.x; maxx.w -= r.o.x;
+        miny.x -= r.o.y; miny.y -= r.o.y; miny.z -= r.o.y; miny.w -= r.o.y; maxy.x -= r.o.y; maxy.y -= r.o.y; maxy.z -= r.o.y; maxy.w -= r.o.y;
+        minz.x -= r.o.z; minz.y -= r.o.z; minz.z -= r.o.z; minz.w -= r.o.z; maxz.x -= r.o.z; maxz.y -= r.o.z; maxz.z -= r.o.z; maxz.w -= r.o.z;
+    }
+    t0 = box_entry_fma(minx.x, miny.x, minz.x, maxx.x, maxy.x, maxz.x, r.oi, r.inv, tmin, tlimit);
+    t1 = box_entry_fma(minx.y, miny.y, minz.y, maxx.y, maxy.y, maxz.y, r.oi, r.inv, tmin, tlimit);
+    t2 = box_entry_fma(minx.z, miny.z, minz.z, maxx.z, maxy.z, maxz.z, r.oi, r.inv, tmin, tlimit);
+    t3 = box_entry_fma(minx.w, miny.w, minz.w, maxx.w, maxy.w, maxz.w, r.oi, r.inv, tmin, tlimit);
 }
 __device__ inline void cswap(float& ta, int& ca, float& tb, int& cb) {
     bool sw = tb < ta;
@@ -202,7 +206,7 @@ __device__ inline bool trace_closest_pass(const Src& src, V3 o, V3 d, float tmin
                                           uint32_t ex0, uint32_t ex1) {
     best.t = tmax; best.u = 0.0f; best.v = 0.0f; best.prim = 0xffffffffu; best.inst = 0xffffffffu; best.gid = 0xffffffffu; best.slot = 0;
     bool found = false;
-    const RaySlab slab = make_slab(o, d);
+    const auto slab = make_slab<STRICT>(src, o, d);
     stack.sp = 0;
     int cur = 0;  // root is inner node 0
     while (true) {
@@ -291,7 +295,7 @@ template <bool COUNT, bool LIGHT, bool STRICT, class Src>
 __device__ inline bool trace_occluded_pass(const Src& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, TravStack stack,
                                            TravStats& st, uint32_t ex0, uint32_t ex1, int& cand_slot, float& cand_t, uint32_t& cand_gid) {
     const float tlimit = LIGHT ? t_e : tmax;
-    const RaySlab slab = make_slab(o, d);
+    const auto slab = make_slab<STRICT>(src, o, d);
     stack.sp = 0;
     int cur = 0;
     while (true) {

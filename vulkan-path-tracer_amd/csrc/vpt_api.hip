@@ -1318,6 +1318,7 @@ int vpt_set_scene(vpt_ctx* c, const vpt_scene_desc* sd) {
     if (c->lds_scene && (rc = upload(c, wide, &D.nodes_wide))) return rc;
     if ((rc = upload(c, leaf_tris, &D.tris))) return rc;
     D.node_count = (uint32_t)nodes.size(); D.tri_count = (uint32_t)leaf_tris.size();
+    D.scene_extent = bvh_max_abs_coord(tris);   // the number the builder padded the boxes by (slab.hpp: the reach of the fma box test)
     {
         std::vector<uint32_t> slot_of(total_tris, 0xffffffffu);  // 0xffffffff: a sliver, in no leaf
         for (size_t i = 0; i < leaf_tris.size(); i++) slot_of[leaf_tris[i].gid] = (uint32_t)i;
