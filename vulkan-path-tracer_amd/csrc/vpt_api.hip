@@ -26,12 +26,16 @@ struct BatchState {
     uint32_t frames = 0, dispatch_base = 0, n_slots = 0;
     uint32_t n_first = 0;   // slots the camera-ray launch starts (n_slots, or the resident part of it when paths are regenerated)
     plan::Schedule sd;      // how it runs (path_plan.hpp decide); sd.finish_at is set late when the host sees few paths alive (batch_finish)
+    int primary_grid = 0;   // grid of the fused / whole-path kernels: the context's, or the part of it a pipelined frame takes (vpt_render_async)
+    int tail_grid = 0;      // > 0: grid of the fused bounces >= 2 (pipelined 1-frame batches)
     bool count = false;
     bool finished = false;  // k_finish has been enqueued: no bounce follows
     uint32_t parity = 0, k3 = 0;
     bool join_pending = false;
     uint64_t iter = 0, iter_cap = 0, min_bounces = 0;
 };
+// The fused / whole-path kernels' grids of one batch: the context's (`primary`, every bounce: tail == 0), or the part of it a pipelined frame takes.
+struct Grids { int primary, tail; };
 // Counter words a finished batch copies to pinned host memory (asynchronously, behind its resolve).
 struct HostCounters {
     Counters ctr;
@@ -39,12 +43,54 @@ struct HostCounters {
     uint32_t refill_next;   // regenerating batches: samples started so far (StreamCounters::refill_next)
 };
 constexpr int kTickets = 16;
+constexpr int kLanes = 3;
 
-struct vpt_ctx {
-    vpt_config cfg{};
+// What ONE batch in flight owns: streams, counters, path buffers, spill regions, its captured graph.  Everything a batch only reads — scene
+// tables, parameters, grids, the accumulation image — is the context's and exists once.  The context renders on its main lane; pipelined
+// 1-frame batches (vpt_ctx::extra) go over up to two more.
+struct Lane {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;             // staged pipeline: the shadow-ray kernels and the join of bounce k run here, beside the extend of bounce k + 1
     hipEvent_t ev_shade = nullptr, ev_join = nullptr;
+    hipEvent_t ev_resolved = nullptr;          // recorded behind this lane's latest resolve
+    Counters* ctr = nullptr;
+    StreamCounters* sctr = nullptr;            // stream pipeline: lengths, exact live counts and work cursors, one cache line each
+    HostCounters* h_ctr = nullptr;             // pinned
+    uint32_t* d_dispatch_base = nullptr;       // graph replays read the batch's first dispatch index from here (RenderParams::dispatch_base_dev)
+    uint32_t* spill = nullptr;                 // spill region of the traversal kernels (DeviceScene::stack_overflow of this lane's launches: lane_scene)
+    uint32_t* spill2 = nullptr;                // ... of those launched on stream2; == spill in a lane whose batches stay on one stream
+    uint32_t stack_overflow_words = 0;         // words per spill region
+
+    uint32_t frames_alloc = 0;   // frames of SAMPLES the slot-addressed buffers hold now: they grow to the largest batch actually requested (ensure_path_buffers)
+    uint32_t resident_alloc = 0; // frames of PATHS the queues and stream records hold (<= frames_alloc; less when paths are regenerated)
+    bool ps_has_sidx = false, ps_has_media = false;   // the per-sample words only some batches touch are allocated only for them: sample index (samples_per_frame > 1), VolumeDepth / ColorChannel (media)
+    uint32_t stream_slack = 0;   // entries a stream may hold beyond its true count: unwritten chunk tails (vote.hpp WaveAppender)
+    void* ps_block = nullptr;    // slot-addressed records every pipeline uses (L, ACC, M + the dword arrays)
+    PathState ps{};
+    uint32_t* queue[2] = {nullptr, nullptr};
+    void* ss_block = nullptr;    // stream records of the staged pipeline (kernels_stream.hip)
+    StreamState ss{};
+    // (only the main lane ever fills these)
+    void* ps_legacy = nullptr;   // round 1's stage kernels only (A, B, T, H, C*, hinst): allocated on their first use
+    uint32_t* cqueue = nullptr;  // connect queue (two-ended)
+    uint32_t* class_queue[kShadeClasses] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the shade queue sorted by class
+    unsigned char* cls_q = nullptr;          // shade class per ray-queue entry, written by the extend stage
+    void* media_block = nullptr; // streams of the media variant of the staged pipeline (kernels_media.hip): allocated on first use
+    MediaState ms{};
+    uint32_t media_frames = 0;   // frames a media batch on the streams can hold (ensure_media_buffers)
+
+    hipGraphExec_t graph = nullptr;  // the fixed batch captured on this lane; current while graph_gen == vpt_ctx::state_gen
+    uint64_t graph_gen = 0;
+    uint32_t graph_frames = 0, graph_bounces = 0;
+    uint64_t graph_kernel_launches[VPT_KERNEL_COUNT] = {};
+    bool graph_broken = false;       // a capture failed once on this lane: stay on plain launches
+    BatchState graph_batch;          // the captured batch as it stands before its resolve
+    BatchState last_fixed;           // the latest fixed-schedule batch enqueued on this lane (drain checks that nothing outlived it)
+    bool last_fixed_valid = false;
+};
+
+struct vpt_ctx {
+    vpt_config cfg{};
     std::string err;
     int cu_count = 256;
 
@@ -82,7 +128,6 @@ struct vpt_ctx {
     bool scene_plain = false;    // every material's five textures are 1x1 and the environment is black: the fused kernel's PLAIN instantiation serves it
     std::vector<unsigned char> tex_1x1;   // per texture of the scene
     bool sbvh = false;
-    uint32_t* stack_overflow2 = nullptr;   // spill region of the traversal kernels launched on stream2
     int trav_blocks = 1024;
 
     vpt_params params{};
@@ -90,9 +135,6 @@ struct vpt_ctx {
     uint32_t frames_in_flight = 1;   // largest batch the context will render at once (the cap; vpt_config.frames_in_flight)
     uint32_t frames_cap = 0;     // upper bound of frames_in_flight after an out-of-memory failure of a size the library chose itself
     uint32_t long_factor = 4;    // batch_cap(): contexts that keep only part (or none) of a batch's paths resident take batches this many times frames_in_flight
-    uint32_t frames_alloc = 0;   // frames of SAMPLES the slot-addressed buffers hold now: they grow to the largest batch actually requested (ensure_path_buffers)
-    uint32_t resident_alloc = 0; // frames of PATHS the queues and stream records hold (<= frames_alloc; less when paths are regenerated)
-    bool ps_has_sidx = false, ps_has_media = false;   // the per-sample words only some batches touch are allocated only for them: sample index (samples_per_frame > 1), VolumeDepth / ColorChannel (media)
     int whole_blocks = 0;        // persistent grid of the whole-path kernel (kernels_path.hip k_whole), 0: the scene does not ride in LDS
     uint32_t lab_whole_sched = 4u;   // how k_whole's waves get their tiles (VPT_LAB_WHOLE_SCHED): tiles per atomic | static-rounds mode << 4
     uint32_t lab_whole_frames = 0xffffffffu;   // VPT_PIPELINE_AUTO runs batches of at most this many frames as ONE whole-path launch (VPT_LAB_WHOLE_FRAMES); default: every batch
@@ -102,30 +144,24 @@ struct vpt_ctx {
     // asynchronous batches (vpt_render_async / vpt_postprocess_device / vpt_wait)
     hipEvent_t tick_ev[kTickets] = {};
     uint64_t tick_issued = 0;
-    HostCounters* h_ctr = nullptr;   // pinned
     bool async_dirty = false;        // work has been enqueued without a host synchronisation behind it
     bool out_active = false;         // an enqueued batch whose paths may outlive the bounces enqueued so far: the next call finishes it
     BatchState out_batch;
     uint64_t out_ticket = 0;
-    uint32_t* d_dispatch_base = nullptr;   // graph replays read the batch's first dispatch index from here (RenderParams::dispatch_base_dev)
-    hipGraphExec_t graph = nullptr;
-    uint64_t graph_gen = 0, state_gen = 1;   // state_gen: bumped by everything a captured batch bakes in (scene tables' addresses, params, camera, buffers)
-    uint32_t graph_frames = 0, graph_bounces = 0, graph_streak = 0;
+    uint64_t state_gen = 1;          // bumped by everything a captured batch bakes in (scene tables' addresses, params, camera, grids)
+    uint32_t graph_streak = 0;       // asynchronous batches asked for since state_gen last changed
     uint64_t graph_streak_gen = 0;
-    uint64_t graph_kernel_launches[VPT_KERNEL_COUNT] = {};
-    bool graph_broken = false;       // a capture failed once on this context: stay on plain launches
     // Pipelined 1-frame batches (vpt_render_async): a frame of the fused fixed schedule is a chain of ~9 dependent launches, each bounded
     // below by the latency of one bounce (~60-90 us on nearly empty queues), so one frame at a time leaves most of the chip idle
     // (profiles/r04_latency_probe.json: 0.95 ms of kernels per 1080p frame against 0.33 ms per frame in 16-frame batches).  Consecutive
-    // frames are independent until their resolve, so they go round-robin over kLanes lanes — the context itself and kLanes - 1 lane
-    // contexts with a stream, counters, 1-frame path buffers and a spill region of their own, sharing the scene tables and the
-    // accumulation image — and only the resolves are ordered (frame k's waits for frame k - 1's: the running mean is applied in frame order).
-    vpt_ctx* lanes[2] = {nullptr, nullptr};
-    vpt_ctx* owner = nullptr;        // set in a lane: the context whose scene and image it borrows
-    void* lane_spill = nullptr;      // a lane's own traversal spill region
-    hipEvent_t ev_resolved = nullptr;    // recorded behind this lane's latest resolve
-    vpt_ctx* order_lane = nullptr;   // owner only: the lane the latest resolve was enqueued on (nullptr: nothing pipelined since the last drain)
-    hipEvent_t ev_post = nullptr;    // owner only: recorded behind the latest vpt_postprocess_device — the next frame's resolve must not touch the image before
+    // frames are independent until their resolve, so they go round-robin over kLanes lanes — the main one and kLanes - 1 more, created on
+    // first use with a stream, counters, 1-frame path buffers and a spill region of their own (struct Lane) — and only the resolves are
+    // ordered (frame k's waits for frame k - 1's: the running mean is applied in frame order).
+    Lane main;
+    Lane* extra[kLanes - 1] = {};
+    Lane* lane(int k) { return k == 0 ? &main : extra[k - 1]; }   // lane k, nullptr: not created yet
+    Lane* order_lane = nullptr;      // the lane the latest resolve was enqueued on (nullptr: nothing pipelined since the last drain)
+    hipEvent_t ev_post = nullptr;    // recorded behind the latest vpt_postprocess_device — the next frame's resolve must not touch the image before
     bool post_pending = false;
     uint32_t lane_rr = 0;
     // vpt_lab_set; defaults = what tests/tools/latency_probe.py measured best (profiles/r04_latency_probe.json): a frame goes to the first
@@ -133,31 +169,13 @@ struct vpt_ctx {
     // uses all three), every lane launches the full persistent grid, and the bounces >= 2 of a 1-frame batch — queues of a quarter of
     // the frame's paths and less — a third of it, which leaves room for the other lanes' blocks
     uint32_t lab_lanes = 3, lab_lane_grid = 1, lab_tail_grid = 3;
-    int tail_blocks = 0;             // > 0: grid of the bounces >= 2 of the batch being enqueued (pipelined 1-frame batches)
-    BatchState graph_batch;          // the captured batch as it stands before its resolve
-    BatchState last_fixed;           // the latest fixed-schedule batch enqueued on this lane (drain checks that nothing outlived it)
-    bool last_fixed_valid = false;
-    uint32_t stack_overflow_words = 0;   // words per spill region
     unsigned long long* d_spill_count = nullptr;
     bool spill_dirty = true;         // traversal kernels have run since the spill regions were last counted (vpt_get_stats counts lazily)
     uint64_t spill_cached[2] = {0, 0};
     double set_scene_ms = 0.0, bvh_build_ms = 0.0;
 
-    void* ps_block = nullptr;    // slot-addressed records every pipeline uses (L, ACC, M + the dword arrays)
-    void* ps_legacy = nullptr;   // round 1's stage kernels only (A, B, T, H, C*, hinst): allocated on their first use
-    PathState ps{};
-    uint32_t* queue[2] = {nullptr, nullptr};
-    uint32_t* cqueue = nullptr;  // connect queue (two-ended)
-    void* ss_block = nullptr;    // stream records of the staged pipeline (kernels_stream.hip)
-    uint32_t* class_queue[kShadeClasses] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the shade queue sorted by class
-    unsigned char* cls_q = nullptr;          // shade class per ray-queue entry, written by the extend stage
-    StreamState ss{};
-    void* media_block = nullptr; // streams of the media variant of the staged pipeline (kernels_media.hip): allocated on first use
-    MediaState ms{};
     int shade_media_blocks = 768, media_tail_blocks = 768;
-    uint32_t media_frames = 0;   // frames a media batch on the streams can hold (ensure_media_buffers)
     uint32_t class_present = 0x1fu;   // shade classes some instance of the scene belongs to (bit kShadeMiss always set): the others get no launch
-    uint32_t stream_slack = 0;   // entries a stream may hold beyond its true count: unwritten chunk tails (vote.hpp WaveAppender)
     int shade_stream_blocks = 768, shadow_blocks = 2048, finish_blocks = 768;
     std::vector<vpt_volume> volumes;       // homogeneous box volumes (vpt_set_volumes)
     vpt_volume* d_volumes = nullptr;
@@ -169,8 +187,6 @@ struct vpt_ctx {
     int primary_blocks_general = 768, primary_blocks_plain = 768;   // grids of the fused kernel's two instantiations (primary_blocks = the one scene_plain picks)
     int vote_blocks = 2048;   // persistent grid of the vote-scheduled traversal kernels
     uint32_t vote_param = 256u + 16u;  // weighted vote, fetch step at 16 idle lanes (profiles/r02_trace_lab_*.json)
-    Counters* ctr = nullptr;
-    StreamCounters* sctr = nullptr;   // stream pipeline: lengths, exact live counts and work cursors, one cache line each
     float* image = nullptr;       // this shard's rows, RGBA32F
     float* full_image = nullptr;  // whole image when shard_count > 1 (after vpt_assemble_shards)
     bool full_valid = false;
@@ -236,15 +252,20 @@ int upload(vpt_ctx* c, const std::vector<T>& v, const T** out, size_t min_elems 
     void* d = nullptr;
     HIPCHK(c, hipMalloc(&d, n * sizeof(T)));
     c->scene_allocs.push_back(d);
-    HIPCHK(c, memset_now(c->stream, d, 0, n * sizeof(T)));
+    HIPCHK(c, memset_now(c->main.stream, d, 0, n * sizeof(T)));
     if (!v.empty()) HIPCHK(c, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     *out = (const T*)d;
     return VPT_OK;
 }
 
+void free_spill(Lane& L) {
+    if (L.spill) (void)hipFree(L.spill);
+    L.spill = L.spill2 = nullptr; L.stack_overflow_words = 0;
+}
 void free_scene(vpt_ctx* c) {
     for (void* p : c->scene_allocs) (void)hipFree(p);
     c->scene_allocs.clear();
+    free_spill(c->main);   // (sized by the scene's grids)
     c->has_scene = false;
     c->d_materials = nullptr; c->d_emissive = nullptr;
 }
@@ -252,28 +273,32 @@ void free_lab(vpt_ctx* c) {
     for (void* p : {(void*)c->lab_ro, (void*)c->lab_rd, (void*)c->lab_hit, (void*)c->lab_hinst, (void*)c->lab_order}) if (p) (void)hipFree(p);
     c->lab_ro = c->lab_rd = c->lab_hit = nullptr; c->lab_hinst = c->lab_order = nullptr; c->lab_n = 0;
 }
+void destroy_graph(Lane& L) {
+    if (L.graph) (void)hipGraphExecDestroy(L.graph);
+    L.graph = nullptr; L.graph_gen = 0;
+}
 // Everything sized by (frames held) x (shard pixels): path records, queues, streams.
-void free_path_buffers(vpt_ctx* c) {
-    if (c->ps_block) (void)hipFree(c->ps_block);
-    c->ps_block = nullptr;
-    if (c->ps_legacy) (void)hipFree(c->ps_legacy);
-    c->ps_legacy = nullptr;
-    for (int i = 0; i < 2; i++) { if (c->queue[i]) (void)hipFree(c->queue[i]); c->queue[i] = nullptr; }
-    if (c->cqueue) (void)hipFree(c->cqueue);
-    c->cqueue = nullptr;
-    if (c->ss_block) (void)hipFree(c->ss_block);
-    c->ss_block = nullptr;
-    if (c->media_block) (void)hipFree(c->media_block);
-    c->media_block = nullptr; c->ms = MediaState{}; c->media_frames = 0;
-    for (uint32_t k = 0; k < kShadeClasses; k++) { if (c->class_queue[k]) (void)hipFree(c->class_queue[k]); c->class_queue[k] = nullptr; }
-    if (c->cls_q) (void)hipFree(c->cls_q);
-    c->cls_q = nullptr;
-    c->ps = PathState{}; c->ss = StreamState{};
-    c->frames_alloc = 0; c->resident_alloc = 0;
-    c->state_gen++;   // a captured batch holds these addresses
+void free_path_buffers(Lane& L) {
+    destroy_graph(L);   // the captured batch holds these addresses
+    if (L.ps_block) (void)hipFree(L.ps_block);
+    L.ps_block = nullptr;
+    if (L.ps_legacy) (void)hipFree(L.ps_legacy);
+    L.ps_legacy = nullptr;
+    for (int i = 0; i < 2; i++) { if (L.queue[i]) (void)hipFree(L.queue[i]); L.queue[i] = nullptr; }
+    if (L.cqueue) (void)hipFree(L.cqueue);
+    L.cqueue = nullptr;
+    if (L.ss_block) (void)hipFree(L.ss_block);
+    L.ss_block = nullptr;
+    if (L.media_block) (void)hipFree(L.media_block);
+    L.media_block = nullptr; L.ms = MediaState{}; L.media_frames = 0;
+    for (uint32_t k = 0; k < kShadeClasses; k++) { if (L.class_queue[k]) (void)hipFree(L.class_queue[k]); L.class_queue[k] = nullptr; }
+    if (L.cls_q) (void)hipFree(L.cls_q);
+    L.cls_q = nullptr;
+    L.ps = PathState{}; L.ss = StreamState{};
+    L.frames_alloc = 0; L.resident_alloc = 0;
 }
 void free_render_buffers(vpt_ctx* c) {
-    free_path_buffers(c);
+    free_path_buffers(c->main);
     if (c->image) (void)hipFree(c->image);
     c->image = nullptr;
     if (c->full_image) (void)hipFree(c->full_image);
@@ -305,8 +330,8 @@ int check_render_size(vpt_ctx* c, uint32_t width, uint32_t height, uint32_t* fra
 // Buffers for batches of up to `frames` frames of this shard of which `resident` frames of paths are in flight at a time (the caller
 // has drained the streams): slot-addressed records (frame sum, medium, per-sample words: 36 B per SAMPLE of the batch) and the queues
 // and stream records (~290 B per RESIDENT path).
-int alloc_path_buffers(vpt_ctx* c, uint32_t frames, uint32_t resident) {
-    free_path_buffers(c);
+int alloc_path_buffers(vpt_ctx* c, Lane& L, uint32_t frames, uint32_t resident) {
+    free_path_buffers(L);
     const RenderParams& P = c->P;
     resident = std::min(resident, frames);
     if ((uint64_t)P.shard_pixels * frames >= (1ull << 31)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "too many paths in flight");
@@ -319,9 +344,9 @@ int alloc_path_buffers(vpt_ctx* c, uint32_t frames, uint32_t resident) {
     const bool want_sidx = P.samples_per_frame > 1u, want_media = media_on(c);
     const size_t kRecords = 2, kWords = 1u + (want_sidx ? 1u : 0u) + (want_media ? 2u : 0u);
     size_t stride = ((size_t)samples + 63) & ~(size_t)63;
-    HIPCHK(c, hipMalloc(&c->ps_block, stride * (16 * kRecords + 4 * kWords)));
-    float4* rb = (float4*)c->ps_block;
-    PathState& s = c->ps;
+    HIPCHK(c, hipMalloc(&L.ps_block, stride * (16 * kRecords + 4 * kWords)));
+    float4* rb = (float4*)L.ps_block;
+    PathState& s = L.ps;
     s = PathState{};
     s.capacity = cap;
     s.ACC = rb; s.M = rb + stride;
@@ -329,7 +354,7 @@ int alloc_path_buffers(vpt_ctx* c, uint32_t frames, uint32_t resident) {
     s.maniso = (float*)wb; wb += stride;
     if (want_sidx) { s.sidx = wb; wb += stride; }
     if (want_media) { s.vdepth = wb; s.cchan = (int32_t*)(wb + stride); }
-    c->ps_has_sidx = want_sidx; c->ps_has_media = want_media;
+    L.ps_has_sidx = want_sidx; L.ps_has_media = want_media;
     // streams written by chunked appends hold up to one unwritten chunk tail per wave that appended to them: at most
     // 256 entries per 64 items processed, and never more than one per resident wave of the largest persistent grid.  A launch
     // appends in chunks only when its queue holds >= kFusedExactBelow (fused kernel) / kAppendExactBelow (streams) entries, holes
@@ -339,14 +364,14 @@ int alloc_path_buffers(vpt_ctx* c, uint32_t frames, uint32_t resident) {
     const int fused_per_cu = (std::max(c->primary_blocks_general, c->primary_blocks_plain) + std::max(c->cu_count, 1) - 1) / std::max(c->cu_count, 1);   // (the scene's, once one is set)
     const int per_cu = std::max(std::max(4, fused_per_cu), std::max(shade_stream_blocks_per_cu(), std::max(shade_media_blocks_per_cu(), media_tail_blocks_per_cu())));
     const uint64_t max_tails = (uint64_t)c->cu_count * (uint64_t)per_cu * 4u * kAppendChunk;
-    c->stream_slack = cap < kFusedExactBelow ? 256u : (uint32_t)std::min<uint64_t>((uint64_t)cap * 4 + 256, max_tails);
-    const size_t scap = (size_t)cap + c->stream_slack;
-    for (int i = 0; i < 2; i++) HIPCHK(c, hipMalloc((void**)&c->queue[i], scap * 4));
+    L.stream_slack = cap < kFusedExactBelow ? 256u : (uint32_t)std::min<uint64_t>((uint64_t)cap * 4 + 256, max_tails);
+    const size_t scap = (size_t)cap + L.stream_slack;
+    for (int i = 0; i < 2; i++) HIPCHK(c, hipMalloc((void**)&L.queue[i], scap * 4));
     {
         const size_t sst = (scap + 63) & ~(size_t)63;
-        HIPCHK(c, hipMalloc(&c->ss_block, sst * (16 * 17 + 4 + 2)));
-        float4* q = (float4*)c->ss_block;
-        StreamState& t = c->ss;
+        HIPCHK(c, hipMalloc(&L.ss_block, sst * (16 * 17 + 4 + 2)));
+        float4* q = (float4*)L.ss_block;
+        StreamState& t = L.ss;
         t.PE = q; t.PS = q + sst; t.PL = q + 2 * sst; t.PT = q + 3 * sst; t.SKO = q + 4 * sst; t.SKD = q + 5 * sst; t.LTO = q + 6 * sst; t.LTD = q + 7 * sst;
         t.RA[0] = q + 8 * sst; t.RA[1] = q + 9 * sst; t.RB[0] = q + 10 * sst; t.RB[1] = q + 11 * sst; t.RT[0] = q + 12 * sst; t.RT[1] = q + 13 * sst;
         t.RL[0] = q + 14 * sst; t.RL[1] = q + 15 * sst;
@@ -354,7 +379,7 @@ int alloc_path_buffers(vpt_ctx* c, uint32_t frames, uint32_t resident) {
         t.vis_sky = (unsigned char*)(t.SHI + sst); t.vis_light = t.vis_sky + sst;
         t.cap = (uint32_t)scap;
     }
-    c->frames_alloc = frames; c->resident_alloc = resident;
+    L.frames_alloc = frames; L.resident_alloc = resident;
     return VPT_OK;
 }
 
@@ -362,9 +387,9 @@ int alloc_path_buffers(vpt_ctx* c, uint32_t frames, uint32_t resident) {
 // allocated with room for stream_slack such entries.  Refuse — not after a kernel has written past a stream — if a device with more
 // CUs / other occupancy than the allocation assumed ever needs more.  Called wherever the grids (vpt_set_scene) or the buffers change.
 int check_stream_slack(vpt_ctx* c) {
-    if (!c->has_scene || c->frames_alloc == 0 || c->ps.capacity < kFusedExactBelow) return VPT_OK;   // short streams are appended to exactly: no tails
+    if (!c->has_scene || c->main.frames_alloc == 0 || c->main.ps.capacity < kFusedExactBelow) return VPT_OK;   // short streams are appended to exactly: no tails
     const uint64_t appending_waves = 4ull * (uint64_t)std::max(std::max(c->shade_stream_blocks, c->primary_blocks), std::max(c->shade_media_blocks, c->media_tail_blocks));
-    if (appending_waves * kAppendChunk > (uint64_t)c->stream_slack && (uint64_t)c->ps.capacity * 4 + 256 > (uint64_t)c->stream_slack)
+    if (appending_waves * kAppendChunk > (uint64_t)c->main.stream_slack && (uint64_t)c->main.ps.capacity * 4 + 256 > (uint64_t)c->main.stream_slack)
         return fail(c, VPT_ERR_DEVICE, "internal: the stream slack allocated for chunk tails is smaller than one chunk per appending wave of this device");
     return VPT_OK;
 }
@@ -389,15 +414,15 @@ int alloc_render_buffers(vpt_ctx* c) {
         // padded to the largest shard's row count (vpt_shard_floats): the buffer is handed to ncclGather as it is
         const size_t image_bytes = (size_t)shard_rows_of(P.height, 0, P.shard_count) * P.width * 16;
         HIPCHK(c, hipMalloc((void**)&c->image, image_bytes));
-        HIPCHK(c, memset_now(c->stream, c->image, 0, image_bytes));
+        HIPCHK(c, memset_now(c->main.stream, c->image, 0, image_bytes));
         if (P.shard_count > 1) {
             HIPCHK(c, hipMalloc((void**)&c->full_image, (size_t)P.width * P.height * 16));
-            HIPCHK(c, memset_now(c->stream, c->full_image, 0, (size_t)P.width * P.height * 16));
+            HIPCHK(c, memset_now(c->main.stream, c->full_image, 0, (size_t)P.width * P.height * 16));
         }
         return VPT_OK;
     };
     rc = images();
-    if (rc == VPT_OK) rc = alloc_path_buffers(c, 1, 1);
+    if (rc == VPT_OK) rc = alloc_path_buffers(c, c->main, 1, 1);
     if (rc != VPT_OK) {
         std::string keep = c->err;
         free_render_buffers(c);
@@ -415,35 +440,36 @@ plan::Policy policy_of(const vpt_ctx* c) { return plan::policy_of(facts_of(c)); 
 plan::State plan_state(const vpt_ctx* c) {
     plan::State s;
     s.px = c->P.shard_pixels; s.frames_in_flight = c->frames_in_flight; s.frames_cap = c->frames_cap; s.long_factor = c->long_factor;
-    s.frames_alloc = c->frames_alloc; s.resident_alloc = c->resident_alloc;
+    s.frames_alloc = c->main.frames_alloc; s.resident_alloc = c->main.resident_alloc;
     return s;
 }
 uint32_t batch_cap(const vpt_ctx* c) { return plan::batch_cap(policy_of(c), plan_state(c)); }
 
 // Do the per-sample word arrays allocated cover what the next batch touches (samples_per_frame / media may have changed since)?
-bool path_words_ok(const vpt_ctx* c) {
+bool path_words_ok(const vpt_ctx* c, const Lane& L) {
     const bool want_sidx = c->P.samples_per_frame > 1u, want_media = media_on(c);
-    return (!want_sidx || c->ps_has_sidx) && (!want_media || c->ps_has_media);
+    return (!want_sidx || L.ps_has_sidx) && (!want_media || L.ps_has_media);
 }
-bool path_buffers_hold(const vpt_ctx* c, uint32_t frames) { return plan::holds(policy_of(c), plan_state(c), frames) && path_words_ok(c); }
-// Grows the buffers so that a batch of `want` frames (<= batch_cap) fits, by plan::grow; the caller has drained the streams.  On failure the
-// context keeps the buffers it had (or none: buffers_ok == false) and the error of the allocation that failed.
+bool path_buffers_hold(const vpt_ctx* c, uint32_t frames) { return plan::holds(policy_of(c), plan_state(c), frames) && path_words_ok(c, c->main); }
+// Grows the main lane's buffers so that a batch of `want` frames (<= batch_cap) fits, by plan::grow; the caller has drained the streams.  On
+// failure the context keeps the buffers it had (or none: buffers_ok == false) and the error of the allocation that failed.
 int ensure_path_buffers(vpt_ctx* c, uint32_t want) {
     if (path_buffers_hold(c, want)) return VPT_OK;
+    c->state_gen++;   // (batches of another shape from here on: the count of unchanged calls behind a graph replay starts again)
     int rc = VPT_OK;
     std::string keep;
     plan::State s = plan_state(c);
     const plan::Grown g = plan::grow(policy_of(c), s, want, [&](uint32_t frames, uint32_t resident) {
-        rc = alloc_path_buffers(c, frames, resident);
+        rc = alloc_path_buffers(c, c->main, frames, resident);
         if (rc == VPT_OK) return (int)plan::kAllocOk;
         keep = c->err;
-        free_path_buffers(c);
+        free_path_buffers(c->main);
         (void)hipGetLastError();
         return (int)(rc == VPT_ERR_OUT_OF_MEMORY || rc == VPT_ERR_DEVICE ? plan::kAllocOutOfMemory : plan::kAllocFailed);
     });
     c->frames_in_flight = s.frames_in_flight; c->frames_cap = s.frames_cap; c->long_factor = s.long_factor;
     if (g.result != plan::kAllocOk) {
-        if (alloc_path_buffers(c, g.frames, g.resident) != VPT_OK) { free_path_buffers(c); (void)hipGetLastError(); c->buffers_ok = false; }
+        if (alloc_path_buffers(c, c->main, g.frames, g.resident) != VPT_OK) { free_path_buffers(c->main); (void)hipGetLastError(); c->buffers_ok = false; }
         c->err = keep;
         return rc;
     }
@@ -458,50 +484,50 @@ int ensure_path_buffers(vpt_ctx* c, uint32_t want) {
 // rendered and kept until the next resize.  They are sized to what is free then (at most 85 % of it): a media batch holds
 // media_frames frames, which may be fewer than frames_in_flight (vpt_render then renders in more, smaller batches; the image is
 // the same for any batch size).
-int ensure_media_buffers(vpt_ctx* c) {
-    if (c->media_block) return VPT_OK;
+int ensure_media_buffers(vpt_ctx* c, Lane& L) {
+    if (L.media_block) return VPT_OK;
     const uint64_t px = c->P.shard_pixels;
-    uint64_t frames = c->resident_alloc;   // what the queues and streams hold now (free_path_buffers drops this block with them)
+    uint64_t frames = L.resident_alloc;   // what the queues and streams hold now (free_path_buffers drops this block with them)
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         const uint64_t fit = (uint64_t)(free_b * 0.85) / (16ull * 11ull);
-        const uint64_t fit_frames = fit > c->stream_slack ? (fit - c->stream_slack) / px : 0;
+        const uint64_t fit_frames = fit > L.stream_slack ? (fit - L.stream_slack) / px : 0;
         frames = std::min<uint64_t>(frames, fit_frames);
     }
     if (frames == 0) return fail(c, VPT_ERR_DEVICE, "out of device memory for the media streams (176 bytes per resident path)");
-    const size_t sst = (((size_t)frames * px + c->stream_slack) + 63) & ~(size_t)63;
-    if (hipMalloc(&c->media_block, sst * 16 * 11) != hipSuccess) {
+    const size_t sst = (((size_t)frames * px + L.stream_slack) + 63) & ~(size_t)63;
+    if (hipMalloc(&L.media_block, sst * 16 * 11) != hipSuccess) {
         (void)hipGetLastError();
-        c->media_block = nullptr;
+        L.media_block = nullptr;
         return fail(c, VPT_ERR_DEVICE, "out of device memory for the media streams (176 bytes per resident path): lower vpt_config.frames_in_flight");
     }
-    c->media_frames = (uint32_t)frames;
-    float4* q = (float4*)c->media_block;
-    c->ms.MS = q;
-    for (int k = 0; k < 10; k++) c->ms.MP[k] = q + (size_t)(k + 1) * sst;
+    L.media_frames = (uint32_t)frames;
+    float4* q = (float4*)L.media_block;
+    L.ms.MS = q;
+    for (int k = 0; k < 10; k++) L.ms.MP[k] = q + (size_t)(k + 1) * sst;
     return VPT_OK;
 }
 
-int ensure_sorted_buffers(vpt_ctx* c) {
-    if (c->cls_q) return VPT_OK;
-    const size_t scap = c->ss.cap;
-    for (uint32_t k = 0; k < kShadeClasses; k++) if (!c->class_queue[k]) HIPCHK(c, hipMalloc((void**)&c->class_queue[k], scap * 4));
-    HIPCHK(c, hipMalloc((void**)&c->cls_q, scap));
+int ensure_sorted_buffers(vpt_ctx* c, Lane& L) {
+    if (L.cls_q) return VPT_OK;
+    const size_t scap = L.ss.cap;
+    for (uint32_t k = 0; k < kShadeClasses; k++) if (!L.class_queue[k]) HIPCHK(c, hipMalloc((void**)&L.class_queue[k], scap * 4));
+    HIPCHK(c, hipMalloc((void**)&L.cls_q, scap));
     return VPT_OK;
 }
 
-int ensure_legacy_buffers(vpt_ctx* c) {
-    const size_t cap = c->ps.capacity, stride = (cap + 63) & ~(size_t)63;
-    if (!c->ps_legacy) {
-        HIPCHK(c, hipMalloc(&c->ps_legacy, stride * (16 * 13 + 4)));
-        float4* q = (float4*)c->ps_legacy;
-        PathState& s = c->ps;
+int ensure_legacy_buffers(vpt_ctx* c, Lane& L) {
+    const size_t cap = L.ps.capacity, stride = (cap + 63) & ~(size_t)63;
+    if (!L.ps_legacy) {
+        HIPCHK(c, hipMalloc(&L.ps_legacy, stride * (16 * 13 + 4)));
+        float4* q = (float4*)L.ps_legacy;
+        PathState& s = L.ps;
         s.L = q + stride * 12;
         s.A = q; s.B = q + stride; s.T[0] = q + stride * 2; s.T[1] = q + stride * 3; s.H = q + stride * 4;
         s.CE = q + stride * 5; s.CS = q + stride * 6; s.CSO = q + stride * 7; s.CSD = q + stride * 8; s.CL = q + stride * 9; s.CLO = q + stride * 10; s.CLD = q + stride * 11;
         s.hinst = (uint32_t*)(q + stride * 13);
     }
-    if (!c->cqueue) HIPCHK(c, hipMalloc((void**)&c->cqueue, cap * 4));   // (a failed call leaves what it got; the next one completes it)
+    if (!L.cqueue) HIPCHK(c, hipMalloc((void**)&L.cqueue, cap * 4));   // (a failed call leaves what it got; the next one completes it)
     return VPT_OK;
 }
 
@@ -549,8 +575,8 @@ int upload_emissive(vpt_ctx* c) {
     uint32_t total = 0;
     for (size_t k = 0; k < c->emissive.size(); k++) { off[k] = total; total += c->emissive[k].tri_count; }
     HIPCHK(c, hipMemcpy(c->d_emissive_tri_offset, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    launch_precompute_emissive(c->stream, c->dsc, c->d_emissive_tri, total);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    launch_precompute_emissive(c->main.stream, c->dsc, c->d_emissive_tri, total);
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return VPT_OK;
 }
 
@@ -630,7 +656,7 @@ int update_class_present(vpt_ctx* c) {
     return VPT_OK;
 }
 
-void begin_timing(vpt_ctx* c, int kernel, hipEvent_t* a, hipEvent_t* b) {
+void begin_timing(vpt_ctx* c, hipStream_t s, int kernel, hipEvent_t* a, hipEvent_t* b) {
     *a = *b = nullptr;
     c->stats.kernel_launches[kernel]++;
     if (!c->cfg.profile) return;
@@ -638,20 +664,20 @@ void begin_timing(vpt_ctx* c, int kernel, hipEvent_t* a, hipEvent_t* b) {
         for (int i = 0; i < 64; i++) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
     }
     *a = c->ev_pool[c->ev_next++]; *b = c->ev_pool[c->ev_next++];
-    (void)hipEventRecord(*a, c->stream);
+    (void)hipEventRecord(*a, s);
     c->pending.push_back({kernel, *a, *b});
 }
-void end_timing(vpt_ctx* c, hipEvent_t b) { if (b) (void)hipEventRecord(b, c->stream); }
+void end_timing(hipStream_t s, hipEvent_t b) { if (b) (void)hipEventRecord(b, s); }
 void collect_timing(vpt_ctx* c) {  // call after a stream sync
     for (auto& p : c->pending) { float ms = 0.0f; if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) c->stats.kernel_ms[p.kernel] += ms; }
     c->pending.clear(); c->ev_next = 0;
 }
-#define TIMED(ctx, kid, launch_expr)            \
+#define TIMED(ctx, s, kid, launch_expr)         \
     do {                                        \
         hipEvent_t ea_, eb_;                    \
-        begin_timing(ctx, kid, &ea_, &eb_);     \
+        begin_timing(ctx, s, kid, &ea_, &eb_);  \
         launch_expr;                            \
-        end_timing(ctx, eb_);                   \
+        end_timing(s, eb_);                     \
     } while (0)
 
 // ---- One batch of `frames` consecutive dispatches starting at dispatch index `dispatch_base`, in stages: batch_begin (camera rays /
@@ -673,19 +699,25 @@ uint32_t batch_slots(const RenderParams& P, uint32_t frames, uint32_t dispatch_b
     for (uint32_t k = 0; k < frames; k++) n += split_dispatch_slots(P, dispatch_base + k);
     return n;
 }
-// How a batch of `frames` frames runs on X — the context itself or one of its lanes — by path_plan.hpp: the facts are the OWNER's `f`, the
-// buffers X's.  A refused batch leaves its reason in X->err.
-int decide_batch(vpt_ctx* X, const plan::Facts& f, uint32_t frames, uint32_t dispatch_base, bool capturing, plan::Schedule& sd) {
-    if (frames == 0 || frames > X->frames_alloc) return fail(X, VPT_ERR_DEVICE, "internal: batch larger than the path buffers");
-    sd = plan::decide(f, frames, X->frames_alloc, X->resident_alloc, batch_slots(X->P, frames, dispatch_base), X->owner != nullptr, capturing);
-    return sd.err != VPT_OK ? fail(X, sd.err, sd.msg) : VPT_OK;
+// The scene as a launch on lane L reads it: the context's tables, the lane's own spill region.
+DeviceScene lane_scene(const vpt_ctx* c, const Lane& L) {
+    DeviceScene d = c->dsc;
+    d.stack_overflow = L.spill;
+    return d;
+}
+// How a batch of `frames` frames runs on lane L, by path_plan.hpp: the context's facts `f`, the lane's buffers.
+int decide_batch(vpt_ctx* c, const Lane& L, const plan::Facts& f, uint32_t frames, uint32_t dispatch_base, bool capturing, plan::Schedule& sd) {
+    if (frames == 0 || frames > L.frames_alloc) return fail(c, VPT_ERR_DEVICE, "internal: batch larger than the path buffers");
+    sd = plan::decide(f, frames, L.frames_alloc, L.resident_alloc, batch_slots(c->P, frames, dispatch_base), &L != &c->main, capturing);
+    return sd.err != VPT_OK ? fail(c, sd.err, sd.msg) : VPT_OK;
 }
 // Turns the decided schedule into buffers and launches.
-int batch_begin(vpt_ctx* c, const plan::Schedule& sd, uint32_t frames, uint32_t dispatch_base, BatchState& b) {
-    hipStream_t s = c->stream;
+int batch_begin(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, uint32_t dispatch_base, Grids grids, BatchState& b) {
+    hipStream_t s = L.stream;
     b = BatchState{};
     b.frames = frames; b.dispatch_base = dispatch_base; b.sd = sd;
-    (c->owner ? c->owner : c)->spill_dirty = true;
+    b.primary_grid = grids.primary; b.tail_grid = grids.tail;
+    c->spill_dirty = true;
     const uint32_t n_slots = batch_slots(c->P, frames, dispatch_base);
     if (c->P.split > 1) {   // launch-grid prefix sums of the batch's dispatches
         std::vector<uint32_t> off(frames + 1, 0u);
@@ -697,51 +729,53 @@ int batch_begin(vpt_ctx* c, const plan::Schedule& sd, uint32_t frames, uint32_t 
     b.n_first = sd.regen ? sd.resident * c->P.shard_pixels : n_slots;   // launch-grid size of the camera-ray kernel = the most paths ever resident
     b.count = c->cfg.count_traversal != 0;
     if (sd.kind == Kind::MediaStreams) {
-        int rl = ensure_media_buffers(c); if (rl != VPT_OK) return rl;
-        if (frames > c->media_frames) return fail(c, VPT_ERR_DEVICE, "internal: media batch larger than the media streams");
+        int rl = ensure_media_buffers(c, L); if (rl != VPT_OK) return rl;
+        if (frames > L.media_frames) return fail(c, VPT_ERR_DEVICE, "internal: media batch larger than the media streams");
     }
-    if (sd.kind == Kind::StagedR1) { int rl = ensure_legacy_buffers(c); if (rl != VPT_OK) return rl; }
-    if (sd.kind == Kind::StreamsSorted) { int rl = ensure_sorted_buffers(c); if (rl != VPT_OK) return rl; }
+    if (sd.kind == Kind::StagedR1) { int rl = ensure_legacy_buffers(c, L); if (rl != VPT_OK) return rl; }
+    if (sd.kind == Kind::StreamsSorted) { int rl = ensure_sorted_buffers(c, L); if (rl != VPT_OK) return rl; }
     b.min_bounces = (uint64_t)c->P.max_depth * c->P.samples_per_frame;
     b.iter_cap = (b.min_bounces * 4ull + 1024ull) * ((frames + sd.resident - 1) / sd.resident);
     if (n_slots == 0) return VPT_OK;
-    HIPCHK(c, hipMemsetAsync(c->ctr, 0, offsetof(Counters, stat_closest), s));  // queue words only, stat_* keep running
+    HIPCHK(c, hipMemsetAsync(L.ctr, 0, offsetof(Counters, stat_closest), s));  // queue words only, stat_* keep running
+    const DeviceScene dsc = lane_scene(c, L);
     if (sd.kind == Kind::Whole) {  // the batch's paths from camera ray to their end in one launch; no queue is written, alive3[] stays 0 for the resolve's guard
-        const uint32_t grid = std::max(1u, std::min<uint32_t>((uint32_t)std::min(c->whole_blocks, c->primary_blocks), (n_slots + 255u) / 256u));   // (blocks of 256 lanes)
+        const uint32_t grid = std::max(1u, std::min<uint32_t>((uint32_t)std::min(c->whole_blocks, b.primary_grid), (n_slots + 255u) / 256u));   // (blocks of 256 lanes)
         // tiles of 64 samples: `rounds` per wave; mode 0: the first round static, mode 1: all but the last, mode 2: half of them; the rest through the counter
         const uint32_t n_waves = grid * 4u, rounds = ((n_slots + 63u) / 64u) / n_waves, mode = c->lab_whole_sched >> 4;
         const uint32_t static_rounds = (mode == 0u || mode == 3u) ? std::min(rounds, 1u) : mode == 1u ? (rounds >= 2u ? rounds - 1u : 0u) : rounds / 2u;
         // (mode 3: mode 0 with guided chunks — at most the given tiles per atomic, fewer towards the end of the batch)
-        TIMED(c, VPT_K_PRIMARY, launch_whole(s, grid, b.count, c->dsc, c->P, c->ps, c->ctr, n_slots, dispatch_base, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u)));
+        TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, L.ps, L.ctr, n_slots, dispatch_base, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u)));
         b.parity = 1; b.k3 = 1; b.iter = 1;
     } else if (sd.kind == Kind::Fused) {  // bounce 0 of every slot needs no input records; survivors land in queue[1]
-        TIMED(c, VPT_K_PRIMARY, launch_bounce(s, (uint32_t)c->primary_blocks, c->lds_scene, b.count, true, c->dsc, c->P, c->ps, c->ss, nullptr, c->queue[1], c->ctr, 0u, b.n_first, dispatch_base, 0u, c->scene_plain));
+        TIMED(c, s, VPT_K_PRIMARY, launch_bounce(s, (uint32_t)b.primary_grid, c->lds_scene, b.count, true, dsc, c->P, L.ps, L.ss, nullptr, L.queue[1], L.ctr, 0u, b.n_first, dispatch_base, 0u, c->scene_plain));
         b.parity = 1; b.k3 = 1; b.iter = 1;
     } else if (plan::runs_streams(sd.kind)) {
-        TIMED(c, VPT_K_PRIMARY, launch_raygen_stream(s, c->P, c->ps, c->ss, c->queue[0], b.n_first, dispatch_base, sd.kind == Kind::MediaStreams));
-        launch_stream_begin(s, c->sctr, b.n_first, n_slots);
+        TIMED(c, s, VPT_K_PRIMARY, launch_raygen_stream(s, c->P, L.ps, L.ss, L.queue[0], b.n_first, dispatch_base, sd.kind == Kind::MediaStreams));
+        launch_stream_begin(s, L.sctr, b.n_first, n_slots);
         b.parity = 0;
     } else {
 #if VPT_LAB
-        TIMED(c, VPT_K_PRIMARY, launch_raygen(s, c->P, c->ps, c->queue[0], c->ctr, n_slots, dispatch_base));
+        TIMED(c, s, VPT_K_PRIMARY, launch_raygen(s, c->P, L.ps, L.queue[0], L.ctr, n_slots, dispatch_base));
 #endif
         b.parity = 0;
     }
     return VPT_OK;
 }
 
-int batch_bounces(vpt_ctx* c, BatchState& b, uint32_t bounces) {
-    hipStream_t s = c->stream;
+int batch_bounces(vpt_ctx* c, Lane& L, BatchState& b, uint32_t bounces) {
+    hipStream_t s = L.stream;
     const Kind kind = b.sd.kind;
     const bool count = b.count, sorted = kind == Kind::StreamsSorted, overlap = b.sd.overlap, stream = plan::runs_streams(kind);
     uint32_t& parity = b.parity;
     const uint32_t n_slots = b.n_first;   // (upper bound of a queue's live entries)
     if (n_slots == 0 || kind == Kind::Whole) return VPT_OK;   // (a whole-path batch has no bounces left to launch)
+    const DeviceScene dsc = lane_scene(c, L);
     for (uint32_t j = 0; j < bounces; j++) {
         b.iter++;
         if (kind == Kind::Fused) {  // no reset kernel in between: the bounce kernels rotate three queue-size words
-            const int grid = (c->tail_blocks > 0 && b.iter >= 3) ? c->tail_blocks : c->primary_blocks;   // (b.iter counts bounce 0)
-            TIMED(c, VPT_K_BOUNCE, launch_bounce(s, (uint32_t)grid, c->lds_scene, count, false, c->dsc, c->P, c->ps, c->ss, c->queue[parity], c->queue[parity ^ 1u], c->ctr, parity, 0u, 0u, b.k3, c->scene_plain));
+            const int grid = (b.tail_grid > 0 && b.iter >= 3) ? b.tail_grid : b.primary_grid;   // (b.iter counts bounce 0)
+            TIMED(c, s, VPT_K_BOUNCE, launch_bounce(s, (uint32_t)grid, c->lds_scene, count, false, dsc, c->P, L.ps, L.ss, L.queue[parity], L.queue[parity ^ 1u], L.ctr, parity, 0u, 0u, b.k3, c->scene_plain));
             parity ^= 1u; b.k3 = (b.k3 + 1u) % 3u;
             continue;
         }
@@ -749,75 +783,75 @@ int batch_bounces(vpt_ctx* c, BatchState& b, uint32_t bounces) {
         // (kernels_trace.hip, kernels_stream.hip) — a scene that rides in LDS and is forced into the staged pipeline too; round 1's
         // stage kernels serve VPT_PIPELINE_STAGED_R1 only
         if (kind == Kind::MediaStreams) {   // distance -> scatter -> extend -> shade -> sky rays, light rays -> tail (kernels_media.hip), one stream
-            launch_prepare_stream(s, c->sctr, parity);
+            launch_prepare_stream(s, L.sctr, parity);
             TraceArgs a{};
-            a.ro = c->ss.RA[parity]; a.rd = c->ss.RB[parity]; a.order = nullptr; a.valid = c->queue[parity]; a.hit = c->ss.SH; a.hinst = c->ss.SHI; a.cls = nullptr;
-            a.n = 0; a.n_dev = &c->sctr->queue_len[parity].v; a.store_gid = 1u; a.param = c->vote_param;
+            a.ro = L.ss.RA[parity]; a.rd = L.ss.RB[parity]; a.order = nullptr; a.valid = L.queue[parity]; a.hit = L.ss.SH; a.hinst = L.ss.SHI; a.cls = nullptr;
+            a.n = 0; a.n_dev = &L.sctr->queue_len[parity].v; a.store_gid = 1u; a.param = c->vote_param;
             // GetDistanceToGeometry (RTCommon.slang:86-101): the payload direction as it is, TMin 1e-5, TMax 1e6
-            a.head = &c->sctr->shade_head.v; a.tmin = 0.00001f; a.tmax = 1000000.0f; a.normalize_dir = 0u;
+            a.head = &L.sctr->shade_head.v; a.tmin = 0.00001f; a.tmax = 1000000.0f; a.normalize_dir = 0u;
             if (!(c->P.flags & VPT_FLAG_RAY_QUERIES)) { a.tmax = 1000.0f; a.normalize_dir = 1u; }   // RTCommon.slang:103-117
-            TIMED(c, VPT_K_EXTEND, launch_trace(s, (uint32_t)c->vote_blocks, VPT_TRACE_VOTE, false, count, c->dsc, a, c->ctr));
-            TIMED(c, VPT_K_SHADE, launch_media_scatter(s, (uint32_t)c->shade_blocks, c->dsc, c->ps, c->ss, c->ms, c->queue[parity], c->sctr, parity));
-            a.head = &c->sctr->extend_head.v; a.tmin = 0.01f; a.tmax = 100000.0f; a.normalize_dir = 1u;
-            TIMED(c, VPT_K_EXTEND, launch_trace(s, (uint32_t)c->vote_blocks, VPT_TRACE_VOTE, false, count, c->dsc, a, c->ctr));
-            launch_layout_media(s, c->sctr, parity, (uint32_t)c->shade_media_blocks * 4u, (uint32_t)c->media_tail_blocks * 4u);
-            TIMED(c, VPT_K_SHADE, launch_shade_media(s, (uint32_t)c->shade_media_blocks, c->dsc, c->P, c->ps, c->ss, c->ms, c->queue[parity], c->ctr, c->sctr, parity));
-            TIMED(c, VPT_K_SHADOW, launch_trace_shadow(s, (uint32_t)c->shadow_blocks, false, count, c->dsc, c->ss, c->ctr, c->sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
-            TIMED(c, VPT_K_SHADOW, launch_trace_shadow(s, (uint32_t)c->shadow_blocks, true, count, c->dsc, c->ss, c->ctr, c->sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
-            TIMED(c, VPT_K_JOIN, launch_media_tail(s, (uint32_t)c->media_tail_blocks, c->dsc, c->P, c->ps, c->ss, c->ms, c->queue[parity], c->queue[parity ^ 1u], c->ctr, c->sctr, parity));
+            TIMED(c, s, VPT_K_EXTEND, launch_trace(s, (uint32_t)c->vote_blocks, VPT_TRACE_VOTE, false, count, dsc, a, L.ctr));
+            TIMED(c, s, VPT_K_SHADE, launch_media_scatter(s, (uint32_t)c->shade_blocks, dsc, L.ps, L.ss, L.ms, L.queue[parity], L.sctr, parity));
+            a.head = &L.sctr->extend_head.v; a.tmin = 0.01f; a.tmax = 100000.0f; a.normalize_dir = 1u;
+            TIMED(c, s, VPT_K_EXTEND, launch_trace(s, (uint32_t)c->vote_blocks, VPT_TRACE_VOTE, false, count, dsc, a, L.ctr));
+            launch_layout_media(s, L.sctr, parity, (uint32_t)c->shade_media_blocks * 4u, (uint32_t)c->media_tail_blocks * 4u);
+            TIMED(c, s, VPT_K_SHADE, launch_shade_media(s, (uint32_t)c->shade_media_blocks, dsc, c->P, L.ps, L.ss, L.ms, L.queue[parity], L.ctr, L.sctr, parity));
+            TIMED(c, s, VPT_K_SHADOW, launch_trace_shadow(s, (uint32_t)c->shadow_blocks, false, count, dsc, L.ss, L.ctr, L.sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
+            TIMED(c, s, VPT_K_SHADOW, launch_trace_shadow(s, (uint32_t)c->shadow_blocks, true, count, dsc, L.ss, L.ctr, L.sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
+            TIMED(c, s, VPT_K_JOIN, launch_media_tail(s, (uint32_t)c->media_tail_blocks, dsc, c->P, L.ps, L.ss, L.ms, L.queue[parity], L.queue[parity ^ 1u], L.ctr, L.sctr, parity));
             parity ^= 1u;
             continue;
         }
         if (stream && b.finished) continue;   // k_finish has been enqueued: nothing is alive behind it
         if (stream && b.sd.finish_at != 0u && b.iter > b.sd.finish_at) {   // (b.iter counts this bounce): the rest of the batch in one launch
-            if (b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0)); b.join_pending = false; }   // pathLight of the queue's entries is final behind the previous join
-            TIMED(c, VPT_K_BOUNCE, launch_finish(s, (uint32_t)c->finish_blocks, count, c->dsc, c->P, c->ps, c->ss, c->queue[parity], c->sctr, c->ctr, parity));
+            if (b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, L.ev_join, 0)); b.join_pending = false; }   // pathLight of the queue's entries is final behind the previous join
+            TIMED(c, s, VPT_K_BOUNCE, launch_finish(s, (uint32_t)c->finish_blocks, count, dsc, c->P, L.ps, L.ss, L.queue[parity], L.sctr, L.ctr, parity));
             b.finished = true;
             continue;
         }
         if (stream) {   // stream pipeline: extend -> classify -> shade per class (streams out) -> sky rays, light rays -> join
-            launch_prepare_stream(s, c->sctr, parity);
+            launch_prepare_stream(s, L.sctr, parity);
             TraceArgs a{};
-            a.ro = c->ss.RA[parity]; a.rd = c->ss.RB[parity]; a.order = nullptr; a.valid = c->queue[parity]; a.hit = c->ss.SH; a.hinst = c->ss.SHI; a.cls = c->cls_q;
-            a.n = 0; a.n_dev = &c->sctr->queue_len[parity].v; a.head = &c->sctr->extend_head.v;
+            a.ro = L.ss.RA[parity]; a.rd = L.ss.RB[parity]; a.order = nullptr; a.valid = L.queue[parity]; a.hit = L.ss.SH; a.hinst = L.ss.SHI; a.cls = L.cls_q;
+            a.n = 0; a.n_dev = &L.sctr->queue_len[parity].v; a.head = &L.sctr->extend_head.v;
             a.tmin = 0.01f; a.tmax = 100000.0f; a.normalize_dir = 1u; a.store_gid = 1u; a.param = c->vote_param;
             if (!sorted) a.cls = nullptr;
-            TIMED(c, VPT_K_EXTEND, launch_trace(s, (uint32_t)c->vote_blocks, VPT_TRACE_VOTE, false, count, c->dsc, a, c->ctr));
+            TIMED(c, s, VPT_K_EXTEND, launch_trace(s, (uint32_t)c->vote_blocks, VPT_TRACE_VOTE, false, count, dsc, a, L.ctr));
             // the shade stage of this bounce overwrites the pending records and shadow-ray streams the join of the previous
             // bounce reads (overlapped mode: that join runs on the second stream, beside the extend launched above)
-            if (overlap && b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0)); b.join_pending = false; }
+            if (overlap && b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, L.ev_join, 0)); b.join_pending = false; }
             if (sorted) {   // the shade queue sorted by material class: one dense queue and one launch per class present in the scene
-                TIMED(c, VPT_K_SHADE, launch_classify(s, c->queue[parity], c->cls_q, c->class_queue, c->sctr, parity, n_slots + c->stream_slack, (uint32_t)c->shade_stream_blocks * 4u));
+                TIMED(c, s, VPT_K_SHADE, launch_classify(s, L.queue[parity], L.cls_q, L.class_queue, L.sctr, parity, n_slots + L.stream_slack, (uint32_t)c->shade_stream_blocks * 4u));
                 for (uint32_t k = 0; k < kShadeClasses; k++)
                     if (c->class_present & (1u << k))
-                        TIMED(c, VPT_K_SHADE, launch_shade_stream(s, (uint32_t)c->shade_stream_blocks, k, true, c->dsc, c->P, c->ps, c->ss, c->queue[parity], c->class_queue[k], c->queue[parity ^ 1u], c->ctr, c->sctr, parity));
+                        TIMED(c, s, VPT_K_SHADE, launch_shade_stream(s, (uint32_t)c->shade_stream_blocks, k, true, dsc, c->P, L.ps, L.ss, L.queue[parity], L.class_queue[k], L.queue[parity ^ 1u], L.ctr, L.sctr, parity));
             } else {
-                launch_layout_single(s, c->sctr, parity, (uint32_t)c->shade_stream_blocks * 4u);
-                TIMED(c, VPT_K_SHADE, launch_shade_stream(s, (uint32_t)c->shade_stream_blocks, 0u, false, c->dsc, c->P, c->ps, c->ss, c->queue[parity], nullptr, c->queue[parity ^ 1u], c->ctr, c->sctr, parity));
+                launch_layout_single(s, L.sctr, parity, (uint32_t)c->shade_stream_blocks * 4u);
+                TIMED(c, s, VPT_K_SHADE, launch_shade_stream(s, (uint32_t)c->shade_stream_blocks, 0u, false, dsc, c->P, L.ps, L.ss, L.queue[parity], nullptr, L.queue[parity ^ 1u], L.ctr, L.sctr, parity));
             }
             hipStream_t sb = s;
-            DeviceScene dsc_shadow = c->dsc;
+            DeviceScene dsc_shadow = dsc;
             if (overlap) {   // shadow rays and join of this bounce on the second stream: the next bounce's extend does not depend on them
-                HIPCHK(c, hipEventRecord(c->ev_shade, s));
-                HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_shade, 0));
-                sb = c->stream2;
-                dsc_shadow.stack_overflow = c->stack_overflow2;   // its own stack spill region: it runs beside the next extend
+                HIPCHK(c, hipEventRecord(L.ev_shade, s));
+                HIPCHK(c, hipStreamWaitEvent(L.stream2, L.ev_shade, 0));
+                sb = L.stream2;
+                dsc_shadow.stack_overflow = L.spill2;   // its own stack spill region: it runs beside the next extend
             }
             // regeneration: fresh camera rays into the room the ended paths left in the next queue (entries behind the ones the join of this
             // bounce addresses, so it may run beside the shadow kernels and the join)
-            if (b.sd.regen) TIMED(c, VPT_K_PRIMARY, launch_refill(s, 2048u, c->P, c->ps, c->ss, c->queue[parity ^ 1u], c->sctr, parity ^ 1u, b.n_first, b.dispatch_base));
-            TIMED(c, VPT_K_SHADOW, launch_trace_shadow(sb, (uint32_t)c->shadow_blocks, false, count, dsc_shadow, c->ss, c->ctr, c->sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
-            TIMED(c, VPT_K_SHADOW, launch_trace_shadow(sb, (uint32_t)c->shadow_blocks, true, count, dsc_shadow, c->ss, c->ctr, c->sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
-            TIMED(c, VPT_K_JOIN, launch_join(sb, (uint32_t)c->join_blocks, c->P, c->ps, c->ss, c->sctr, c->queue[parity], c->queue[parity ^ 1u], parity));
-            if (overlap) { HIPCHK(c, hipEventRecord(c->ev_join, c->stream2)); b.join_pending = true; }
+            if (b.sd.regen) TIMED(c, s, VPT_K_PRIMARY, launch_refill(s, 2048u, c->P, L.ps, L.ss, L.queue[parity ^ 1u], L.sctr, parity ^ 1u, b.n_first, b.dispatch_base));
+            TIMED(c, s, VPT_K_SHADOW, launch_trace_shadow(sb, (uint32_t)c->shadow_blocks, false, count, dsc_shadow, L.ss, L.ctr, L.sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
+            TIMED(c, s, VPT_K_SHADOW, launch_trace_shadow(sb, (uint32_t)c->shadow_blocks, true, count, dsc_shadow, L.ss, L.ctr, L.sctr, c->vote_param, (c->P.flags & VPT_FLAG_RAY_QUERIES) ? 1u : 0u));
+            TIMED(c, s, VPT_K_JOIN, launch_join(sb, (uint32_t)c->join_blocks, c->P, L.ps, L.ss, L.sctr, L.queue[parity], L.queue[parity ^ 1u], parity));
+            if (overlap) { HIPCHK(c, hipEventRecord(L.ev_join, L.stream2)); b.join_pending = true; }
             parity ^= 1u;
             continue;
         }
 #if VPT_LAB
-        launch_prepare(s, c->ctr, parity);
-        TIMED(c, VPT_K_EXTEND, launch_extend(s, (uint32_t)c->trav_blocks, c->lds_scene, count, c->dsc, c->ps, c->queue[parity], c->ctr, parity));
-        TIMED(c, VPT_K_SHADE, launch_shade(s, (uint32_t)c->shade_blocks, c->dsc, c->P, c->ps, c->queue[parity], c->queue[parity ^ 1u], c->cqueue, c->ctr, parity));
-        TIMED(c, VPT_K_CONNECT, launch_connect(s, (uint32_t)c->trav_blocks, c->lds_scene, count, c->dsc, c->P, c->ps, c->cqueue, c->ctr, parity));
+        launch_prepare(s, L.ctr, parity);
+        TIMED(c, s, VPT_K_EXTEND, launch_extend(s, (uint32_t)c->trav_blocks, c->lds_scene, count, dsc, L.ps, L.queue[parity], L.ctr, parity));
+        TIMED(c, s, VPT_K_SHADE, launch_shade(s, (uint32_t)c->shade_blocks, dsc, c->P, L.ps, L.queue[parity], L.queue[parity ^ 1u], L.cqueue, L.ctr, parity));
+        TIMED(c, s, VPT_K_CONNECT, launch_connect(s, (uint32_t)c->trav_blocks, c->lds_scene, count, dsc, c->P, L.ps, L.cqueue, L.ctr, parity));
 #endif
         parity ^= 1u;
     }
@@ -827,48 +861,46 @@ int batch_bounces(vpt_ctx* c, BatchState& b, uint32_t bounces) {
 // The resolve rides right behind the bounces that are expected to be the last ones; it does nothing if a path is still alive
 // (in-medium walks do not consume depth), in which case more bounces and another resolve follow.  Behind it the counters travel to
 // pinned host memory, for whoever synchronises next.
-int batch_resolve(vpt_ctx* c, BatchState& b) {
-    hipStream_t s = c->stream;
+int batch_resolve(vpt_ctx* c, Lane& L, BatchState& b) {
+    hipStream_t s = L.stream;
     if (b.n_slots == 0) return VPT_OK;
 #if VPT_LAB
-    if (b.sd.kind == Kind::StagedR1) launch_fold(s, c->ctr);
+    if (b.sd.kind == Kind::StagedR1) launch_fold(s, L.ctr);
 #endif
-    if (b.sd.overlap && b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0)); b.join_pending = false; }   // the resolve reads the frame sums the join writes
+    if (b.sd.overlap && b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, L.ev_join, 0)); b.join_pending = false; }   // the resolve reads the frame sums the join writes
     const bool stream = plan::runs_streams(b.sd.kind);
-    const uint32_t* guard = plan::runs_fused(b.sd.kind) ? &c->ctr->alive3[b.k3] : stream ? &c->sctr->alive[b.parity].v : &c->ctr->ray_count[b.parity];
-    TIMED(c, VPT_K_RESOLVE, launch_resolve(s, c->P, c->ps, c->image, b.frames, b.dispatch_base, guard));
-    HIPCHK(c, hipMemcpyAsync(&c->h_ctr->ctr, c->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    const uint32_t* guard = plan::runs_fused(b.sd.kind) ? &L.ctr->alive3[b.k3] : stream ? &L.sctr->alive[b.parity].v : &L.ctr->ray_count[b.parity];
+    TIMED(c, s, VPT_K_RESOLVE, launch_resolve(s, c->P, L.ps, c->image, b.frames, b.dispatch_base, guard));
+    HIPCHK(c, hipMemcpyAsync(&L.h_ctr->ctr, L.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
     if (stream) {  // the exact number of live paths, and the queue length (holes included), which must fit the queue allocation
-        HIPCHK(c, hipMemcpyAsync(&c->h_ctr->alive[0], &c->sctr->alive[b.parity].v, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&c->h_ctr->queue_len[0], &c->sctr->queue_len[b.parity].v, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&c->h_ctr->refill_next, &c->sctr->refill_next, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&L.h_ctr->alive[0], &L.sctr->alive[b.parity].v, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&L.h_ctr->queue_len[0], &L.sctr->queue_len[b.parity].v, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&L.h_ctr->refill_next, &L.sctr->refill_next, 4, hipMemcpyDeviceToHost, s));
     }
     return VPT_OK;
 }
 
 // The device-side ray statistics are running totals per lane (Counters::stat_*), copied to pinned memory behind every resolve.
 void update_ray_stats(vpt_ctx* c) {
-    vpt_ctx* root = c->owner ? c->owner : c;
     unsigned long long v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto add = [&](const vpt_ctx* x) {
-        const Counters& h = x->h_ctr->ctr;
-        v[0] += h.stat_closest; v[1] += h.stat_shadow; v[2] += h.stat_connect; v[3] += h.stat_primary_hits; v[4] += h.stat_primary_alive; v[5] += h.stat_primary_rays;
-        v[6] += h.stat_finish_paths; v[7] += h.stat_finish_closest; v[8] += h.stat_finish_shadow;
-    };
-    add(root);
-    for (vpt_ctx* L : root->lanes) if (L) add(L);
-    root->stats.closest_rays = v[0]; root->stats.shadow_rays = v[1]; root->stats.connect_paths = v[2];
-    root->stats.primary_hits = v[3]; root->stats.primary_survivors = v[4]; root->stats.primary_shadow_rays = v[5];
-    root->stats.finish_paths = v[6]; root->stats.finish_closest_rays = v[7]; root->stats.finish_shadow_rays = v[8];
+    for (int k = 0; k < kLanes; k++)
+        if (const Lane* L = c->lane(k)) {
+            const Counters& h = L->h_ctr->ctr;
+            v[0] += h.stat_closest; v[1] += h.stat_shadow; v[2] += h.stat_connect; v[3] += h.stat_primary_hits; v[4] += h.stat_primary_alive; v[5] += h.stat_primary_rays;
+            v[6] += h.stat_finish_paths; v[7] += h.stat_finish_closest; v[8] += h.stat_finish_shadow;
+        }
+    c->stats.closest_rays = v[0]; c->stats.shadow_rays = v[1]; c->stats.connect_paths = v[2];
+    c->stats.primary_hits = v[3]; c->stats.primary_survivors = v[4]; c->stats.primary_shadow_rays = v[5];
+    c->stats.finish_paths = v[6]; c->stats.finish_closest_rays = v[7]; c->stats.finish_shadow_rays = v[8];
 }
 
 // Host synchronisation: statistics, overflow checks, *alive = paths of the batch still in flight.
-int batch_check(vpt_ctx* c, BatchState& b, uint32_t* alive) {
+int batch_check(vpt_ctx* c, Lane& L, BatchState& b, uint32_t* alive) {
     *alive = 0;
     if (b.n_slots == 0) return VPT_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(L.stream));
     collect_timing(c);
-    const Counters& h = c->h_ctr->ctr;
+    const Counters& h = L.h_ctr->ctr;
     update_ray_stats(c);
     const bool counted = c->cfg.count_traversal != 0;   // (the finisher and the fused kernel on a tree in memory always count: reported only when asked for, so the figures are never partial)
     c->stats.nodes_visited = counted ? h.stat_nodes : 0;
@@ -877,29 +909,29 @@ int batch_check(vpt_ctx* c, BatchState& b, uint32_t* alive) {
     c->stats.shadow_tris_tested = counted ? h.stat_shadow_tris : 0;
     uint32_t n = plan::runs_fused(b.sd.kind) ? h.alive3[b.k3] : h.ray_count[b.parity];
     if (plan::runs_streams(b.sd.kind)) {
-        n = c->h_ctr->alive[0];
-        const uint64_t len = c->h_ctr->queue_len[0];
-        const uint64_t room = b.sd.kind == Kind::MediaStreams ? (uint64_t)c->media_frames * c->P.shard_pixels + c->stream_slack : (uint64_t)c->ps.capacity + c->stream_slack;
-        if (len > room || len > (uint64_t)c->ps.capacity + c->stream_slack) { (void)hipStreamSynchronize(c->stream2); return fail(c, VPT_ERR_DEVICE, "internal: stream overflow"); }
+        n = L.h_ctr->alive[0];
+        const uint64_t len = L.h_ctr->queue_len[0];
+        const uint64_t room = b.sd.kind == Kind::MediaStreams ? (uint64_t)L.media_frames * c->P.shard_pixels + L.stream_slack : (uint64_t)L.ps.capacity + L.stream_slack;
+        if (len > room || len > (uint64_t)L.ps.capacity + L.stream_slack) { (void)hipStreamSynchronize(L.stream2); return fail(c, VPT_ERR_DEVICE, "internal: stream overflow"); }
     }
-    if (n > b.n_first) { (void)hipStreamSynchronize(c->stream2); return fail(c, VPT_ERR_DEVICE, "internal: queue overflow"); }
-    if (n != 0 && b.iter > b.iter_cap) { (void)hipStreamSynchronize(c->stream2); return fail(c, VPT_ERR_DEVICE, "internal: bounce loop did not terminate"); }
+    if (n > b.n_first) { (void)hipStreamSynchronize(L.stream2); return fail(c, VPT_ERR_DEVICE, "internal: queue overflow"); }
+    if (n != 0 && b.iter > b.iter_cap) { (void)hipStreamSynchronize(L.stream2); return fail(c, VPT_ERR_DEVICE, "internal: bounce loop did not terminate"); }
     *alive = n;
     return VPT_OK;
 }
 
 // Runs a begun batch to its end: resolve + check, and while paths are alive four more bounces at a time.
-int batch_finish(vpt_ctx* c, BatchState& b, bool resolve_enqueued) {
+int batch_finish(vpt_ctx* c, Lane& L, BatchState& b, bool resolve_enqueued) {
     while (true) {
-        if (!resolve_enqueued) { int rc = batch_resolve(c, b); if (rc) return rc; }
+        if (!resolve_enqueued) { int rc = batch_resolve(c, L, b); if (rc) return rc; }
         resolve_enqueued = false;
         uint32_t n = 0;
-        int rc = batch_check(c, b, &n);
+        int rc = batch_check(c, L, b, &n);
         if (rc) return rc;
         if (n == 0) break;
         // few paths left — and, in a regenerating batch, no sample left to start: the next launch finishes them
-        if (b.sd.finisher && (!b.sd.regen || c->h_ctr->refill_next >= b.n_slots) && !b.finished && b.sd.finish_at == 0u && n < plan::kFinishBelowPaths) b.sd.finish_at = (uint32_t)b.iter;
-        rc = batch_bounces(c, b, b.sd.regen ? 8u : 4u);   // (a regenerating batch runs many more launches than max_depth: fewer host round trips)
+        if (b.sd.finisher && (!b.sd.regen || L.h_ctr->refill_next >= b.n_slots) && !b.finished && b.sd.finish_at == 0u && n < plan::kFinishBelowPaths) b.sd.finish_at = (uint32_t)b.iter;
+        rc = batch_bounces(c, L, b, b.sd.regen ? 8u : 4u);   // (a regenerating batch runs many more launches than max_depth: fewer host round trips)
         if (rc) return rc;
     }
     HIPCHK(c, hipGetLastError());
@@ -907,18 +939,19 @@ int batch_finish(vpt_ctx* c, BatchState& b, bool resolve_enqueued) {
 }
 
 int render_batch(vpt_ctx* c, uint32_t frames, uint32_t dispatch_base) {
+    Lane& L = c->main;
     plan::Schedule sd;
-    int rc = decide_batch(c, facts_of(c), frames, dispatch_base, false, sd);
+    int rc = decide_batch(c, L, facts_of(c), frames, dispatch_base, false, sd);
     if (rc) return rc;
     BatchState b;
-    rc = batch_begin(c, sd, frames, dispatch_base, b);
+    rc = batch_begin(c, L, sd, frames, dispatch_base, Grids{c->primary_blocks, 0}, b);
     if (rc) return rc;
     if (b.n_slots == 0) return VPT_OK;
     // the host looks at the queue after max_depth bounces (when a surface-only batch is done) or after eight, whichever comes first
     const uint32_t first = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(b.min_bounces - (plan::runs_fused(sd.kind) ? 1 : 0), 1), 8);
-    rc = batch_bounces(c, b, first);
+    rc = batch_bounces(c, L, b, first);
     if (rc) return rc;
-    rc = batch_finish(c, b, false);
+    rc = batch_finish(c, L, b, false);
     if (rc) return rc;
     c->stats.samples += (uint64_t)b.n_slots * c->P.samples_per_frame;
     return VPT_OK;
@@ -931,11 +964,11 @@ uint64_t issue_ticket(vpt_ctx* c, hipStream_t on) {
     c->async_dirty = true;
     return c->tick_issued;
 }
-// An enqueued batch whose paths may outlive the bounces enqueued with it: finish it exactly as render_batch would have.
+// An enqueued batch whose paths may outlive the bounces enqueued with it (always on the main lane): finish it exactly as render_batch would have.
 int finish_outstanding(vpt_ctx* c) {
     if (!c->out_active) return VPT_OK;
     c->out_active = false;
-    return batch_finish(c, c->out_batch, true);
+    return batch_finish(c, c->main, c->out_batch, true);
 }
 // Everything enqueued so far — on every lane — has finished when this returns (and an unfinished batch has been finished).
 int drain(vpt_ctx* c) {
@@ -943,162 +976,135 @@ int drain(vpt_ctx* c) {
     if (rc) return rc;
     if (!c->async_dirty) return VPT_OK;
     c->async_dirty = false;
-    for (vpt_ctx* L : c->lanes)
-        if (L) {
-            HIPCHK(c, hipStreamSynchronize(L->stream));
-            if (L->last_fixed_valid && (plan::runs_streams(L->last_fixed.sd.kind) ? L->h_ctr->alive[0] : L->h_ctr->ctr.alive3[L->last_fixed.k3]) != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
-            L->last_fixed_valid = false;
-            for (int k = 0; k < VPT_KERNEL_COUNT; k++) { c->stats.kernel_launches[k] += L->stats.kernel_launches[k]; L->stats.kernel_launches[k] = 0; }
-            c->stats.graph_launches += L->stats.graph_launches; L->stats.graph_launches = 0;
-        }
-    c->order_lane = nullptr; c->post_pending = false;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream2));
-    if (c->last_fixed_valid) {   // a fixed-schedule batch on the main lane: nothing may have outlived it either (its guarded resolve would have been a no-op)
-        c->last_fixed_valid = false;
-        const BatchState& f = c->last_fixed;
+    for (int k = 0; k < kLanes; k++) {
+        Lane* L = c->lane(k);
+        if (!L) continue;
+        HIPCHK(c, hipStreamSynchronize(L->stream));
+        if (!L->last_fixed_valid) continue;
+        L->last_fixed_valid = false;   // a fixed-schedule batch: nothing may have outlived it (its guarded resolve would have been a no-op)
+        const BatchState& f = L->last_fixed;
         if (plan::runs_streams(f.sd.kind)) {
-            if (c->h_ctr->alive[0] != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
-            if ((uint64_t)c->h_ctr->queue_len[0] > (uint64_t)c->ps.capacity + c->stream_slack) return fail(c, VPT_ERR_DEVICE, "internal: stream overflow");
-        } else if (plan::runs_fused(f.sd.kind) && c->h_ctr->ctr.alive3[f.k3] != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
+            if (L->h_ctr->alive[0] != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
+            if ((uint64_t)L->h_ctr->queue_len[0] > (uint64_t)L->ps.capacity + L->stream_slack) return fail(c, VPT_ERR_DEVICE, "internal: stream overflow");
+        } else if (plan::runs_fused(f.sd.kind) && L->h_ctr->ctr.alive3[f.k3] != 0u) return fail(c, VPT_ERR_DEVICE, "internal: a path outlived a fixed-schedule batch");
     }
+    c->order_lane = nullptr; c->post_pending = false;
+    HIPCHK(c, hipStreamSynchronize(c->main.stream2));
     collect_timing(c);
     update_ray_stats(c);   // fixed-schedule batches copy their counters to pinned memory too
     HIPCHK(c, hipGetLastError());
     return VPT_OK;
 }
-void destroy_graph(vpt_ctx* c) {
-    if (c->graph) (void)hipGraphExecDestroy(c->graph);
-    c->graph = nullptr; c->graph_gen = 0;
-}
 // A whole batch as a fixed schedule: bounce 0 (or the camera rays) and `bounces_total` bounces in all; the guarded resolve is the caller's.
-int enqueue_fixed(vpt_ctx* c, const plan::Schedule& sd, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, BatchState& b) {
-    int rc = batch_begin(c, sd, frames, dispatch_base, b);
+int enqueue_fixed(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, Grids grids, BatchState& b) {
+    int rc = batch_begin(c, L, sd, frames, dispatch_base, grids, b);
     if (rc) return rc;
     if (b.n_slots == 0) return VPT_OK;
-    return batch_bounces(c, b, plan::runs_fused(sd.kind) ? bounces_total - 1u : bounces_total);
+    return batch_bounces(c, L, b, plan::runs_fused(sd.kind) ? bounces_total - 1u : bounces_total);
 }
 // The same through a captured hipGraph: the fused pipeline's batch (memset, bounce 0, bounces) with the first dispatch index read from
-// device memory, captured once per (state, frames, bounces) and replayed.  b: the batch as it stands before its resolve.  f: the owner's
-// facts — the captured batch is decided for ONE stream (no shadow / join overlap on stream2).
-int enqueue_graph(vpt_ctx* c, const plan::Facts& f, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, bool* used, BatchState& b) {
+// device memory, captured once per (state, frames, bounces) — grids included — and replayed.  b: the batch as it stands before its resolve.
+// The captured batch is decided for ONE stream (no shadow / join overlap on stream2).
+int enqueue_graph(vpt_ctx* c, Lane& L, const plan::Facts& f, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, Grids grids, bool* used, BatchState& b) {
     *used = false;
-    if (c->graph_broken) return VPT_OK;
-    if (!c->graph || c->graph_gen != c->state_gen || c->graph_frames != frames || c->graph_bounces != bounces_total) {
-        destroy_graph(c);
+    if (L.graph_broken) return VPT_OK;
+    if (!L.graph || L.graph_gen != c->state_gen || L.graph_frames != frames || L.graph_bounces != bounces_total) {
+        destroy_graph(L);
         uint64_t before[VPT_KERNEL_COUNT];
         memcpy(before, c->stats.kernel_launches, sizeof(before));
-        c->P.dispatch_base_dev = c->d_dispatch_base;
+        c->P.dispatch_base_dev = L.d_dispatch_base;
         hipGraph_t g = nullptr;
-        bool ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+        bool ok = hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
         plan::Schedule sd;
-        int rc = ok ? decide_batch(c, f, frames, 0u, true, sd) : VPT_ERR_DEVICE;
-        if (rc == VPT_OK) rc = enqueue_fixed(c, sd, frames, 0u, bounces_total, c->graph_batch);
-        if (ok && hipStreamEndCapture(c->stream, &g) != hipSuccess) { ok = false; g = nullptr; }
+        int rc = ok ? decide_batch(c, L, f, frames, 0u, true, sd) : VPT_ERR_DEVICE;
+        if (rc == VPT_OK) rc = enqueue_fixed(c, L, sd, frames, 0u, bounces_total, grids, L.graph_batch);
+        if (ok && hipStreamEndCapture(L.stream, &g) != hipSuccess) { ok = false; g = nullptr; }
         c->P.dispatch_base_dev = nullptr;
-        for (int k = 0; k < VPT_KERNEL_COUNT; k++) { c->graph_kernel_launches[k] = c->stats.kernel_launches[k] - before[k]; c->stats.kernel_launches[k] = before[k]; }
-        if (ok && rc == VPT_OK && g && hipGraphInstantiate(&c->graph, g, nullptr, nullptr, 0) != hipSuccess) { ok = false; c->graph = nullptr; }
+        for (int k = 0; k < VPT_KERNEL_COUNT; k++) { L.graph_kernel_launches[k] = c->stats.kernel_launches[k] - before[k]; c->stats.kernel_launches[k] = before[k]; }
+        if (ok && rc == VPT_OK && g && hipGraphInstantiate(&L.graph, g, nullptr, nullptr, 0) != hipSuccess) { ok = false; L.graph = nullptr; }
         if (g) (void)hipGraphDestroy(g);
-        if (!ok || rc != VPT_OK || !c->graph) {   // capture is an optimisation: without it the batch goes out as plain launches
+        if (!ok || rc != VPT_OK || !L.graph) {   // capture is an optimisation: without it the batch goes out as plain launches
             (void)hipGetLastError();
-            destroy_graph(c);
-            c->graph_broken = true;
+            destroy_graph(L);
+            L.graph_broken = true;
             c->err.clear();
             return VPT_OK;
         }
-        c->graph_gen = c->state_gen; c->graph_frames = frames; c->graph_bounces = bounces_total;
+        L.graph_gen = c->state_gen; L.graph_frames = frames; L.graph_bounces = bounces_total;
     }
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_dispatch_base, (int)dispatch_base, 1, c->stream));
-    HIPCHK(c, hipGraphLaunch(c->graph, c->stream));
-    for (int k = 0; k < VPT_KERNEL_COUNT; k++) c->stats.kernel_launches[k] += c->graph_kernel_launches[k];
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)L.d_dispatch_base, (int)dispatch_base, 1, L.stream));
+    HIPCHK(c, hipGraphLaunch(L.graph, L.stream));
+    for (int k = 0; k < VPT_KERNEL_COUNT; k++) c->stats.kernel_launches[k] += L.graph_kernel_launches[k];
     c->stats.graph_launches++;
-    b = c->graph_batch;
+    b = L.graph_batch;
     b.dispatch_base = dispatch_base;
     *used = true;
     return VPT_OK;
 }
 
-// ---- lanes (see vpt_ctx::lanes)
-int init_ctx_resources(vpt_ctx* c) {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_shade, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_resolved, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_post, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc((void**)&c->ctr, sizeof(Counters)) != hipSuccess) return VPT_ERR_DEVICE;
-    (void)memset_now(c->stream, c->ctr, 0, sizeof(Counters));
-    if (hipMalloc((void**)&c->sctr, sizeof(StreamCounters)) != hipSuccess) return VPT_ERR_DEVICE;
-    (void)memset_now(c->stream, c->sctr, 0, sizeof(StreamCounters));
-    if (hipMalloc((void**)&c->d_launch_off, (plan::kMaxFramesInFlight + 1) * 4) != hipSuccess) return VPT_ERR_DEVICE;
-    for (int k = 0; k < kTickets; k++)
-        if (hipEventCreateWithFlags(&c->tick_ev[k], hipEventDisableTiming) != hipSuccess) { c->tick_ev[k] = nullptr; return VPT_ERR_DEVICE; }
-    if (hipHostMalloc((void**)&c->h_ctr, sizeof(HostCounters), hipHostMallocDefault) != hipSuccess) { c->h_ctr = nullptr; return VPT_ERR_DEVICE; }
-    memset(c->h_ctr, 0, sizeof(HostCounters));
-    if (hipMalloc((void**)&c->d_dispatch_base, 256) != hipSuccess || hipMalloc((void**)&c->d_spill_count, 256) != hipSuccess) return VPT_ERR_DEVICE;
+// ---- lanes (struct Lane)
+// Streams, events and counters of a lane.  A failure leaves what it got for lane_destroy.
+int lane_init(vpt_ctx* c, Lane& L) {
+    HIPCHK(c, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&L.stream2, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&L.ev_shade, &L.ev_join, &L.ev_resolved}) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    HIPCHK(c, hipMalloc((void**)&L.ctr, sizeof(Counters)));
+    HIPCHK(c, memset_now(L.stream, L.ctr, 0, sizeof(Counters)));
+    HIPCHK(c, hipMalloc((void**)&L.sctr, sizeof(StreamCounters)));
+    HIPCHK(c, memset_now(L.stream, L.sctr, 0, sizeof(StreamCounters)));
+    if (hipHostMalloc((void**)&L.h_ctr, sizeof(HostCounters), hipHostMallocDefault) != hipSuccess) { L.h_ctr = nullptr; return fail(c, VPT_ERR_DEVICE, "hipHostMalloc of a lane's counters failed"); }
+    memset(L.h_ctr, 0, sizeof(HostCounters));
+    HIPCHK(c, hipMalloc((void**)&L.d_dispatch_base, 256));
     return VPT_OK;
 }
-void destroy_lane(vpt_ctx* L);
-// Lane k of the owner: created on first use, holds one frame of path buffers for the owner's image size.
-vpt_ctx* get_lane(vpt_ctx* c, int k) {
-    if (c->lanes[k]) return c->lanes[k];
-    vpt_ctx* L = new vpt_ctx();
-    L->owner = c; L->cfg = c->cfg; L->cfg.frames_in_flight = 1; L->cfg.resident_frames = 1; L->cfg.profile = 0; L->cfg.count_traversal = 0;
-    L->cu_count = c->cu_count;
-    L->P = c->P;
-    bool ok = init_ctx_resources(L) == VPT_OK && alloc_path_buffers(L, 1, 1) == VPT_OK;
-    if (ok) {
-        const size_t bytes = stack_overflow_bytes((uint32_t)std::max(std::max(std::max(c->primary_blocks_general, c->primary_blocks_plain), c->whole_blocks), c->max_blocks));   // (the stream kernels' grids included)
-        ok = hipMalloc(&L->lane_spill, bytes) == hipSuccess && memset_now(L->stream, L->lane_spill, 0x7f, bytes) == hipSuccess;   // (kSpillPatternByte: vpt_get_stats counts what was spilled)
-        L->stack_overflow_words = (uint32_t)(bytes / 4);
-    }
-    if (!ok) { (void)hipGetLastError(); destroy_lane(L); return nullptr; }
-    L->frames_in_flight = 1; L->buffers_ok = true;
-    c->lanes[k] = L;
-    return L;
-}
-// What a lane borrows from its owner, refreshed before every use: scene tables, parameters, camera, the accumulation image — what its
-// LAUNCHES read.  How its batch runs is decided from the owner's facts (decide_batch), not from copies kept here.
-int sync_lane(vpt_ctx* c, vpt_ctx* L) {
-    L->P = c->P; L->P.dispatch_base_dev = nullptr;
-    L->dsc = c->dsc; L->dsc.stack_overflow = (uint32_t*)L->lane_spill;
-    L->params = c->params;
-    L->lds_scene = c->lds_scene; L->scene_plain = c->scene_plain;
-    L->primary_blocks = c->primary_blocks; L->whole_blocks = c->whole_blocks; L->lab_whole_sched = c->lab_whole_sched;
-    L->vote_blocks = c->vote_blocks; L->shadow_blocks = c->shadow_blocks; L->shade_stream_blocks = c->shade_stream_blocks; L->join_blocks = c->join_blocks; L->finish_blocks = c->finish_blocks;
-    L->max_blocks = c->max_blocks; L->vote_param = c->vote_param; L->class_present = c->class_present; L->stack_overflow2 = (uint32_t*)L->lane_spill;   // (a lane's batches run on one stream: no second region in use)
-    L->image = c->image;
-    // (vpt_set_params drained every lane before samples_per_frame changed: nothing of this lane is in flight when its per-sample words are replaced)
-    // New buffers first — free_path_buffers() bumps the lane's own generation — and the owner's generation assigned BEHIND that: a lane left one
-    // generation ahead of its owner would, after one more vpt_set_camera / vpt_set_params on the owner, find its stale captured batch "current" again.
-    if (!path_words_ok(L)) {
-        destroy_graph(L);   // the captured batch holds the old buffers' addresses
-        if (alloc_path_buffers(L, 1, 1) != VPT_OK) { L->buffers_ok = false; c->err = L->err.empty() ? "lane: out of memory" : L->err; return VPT_ERR_OUT_OF_MEMORY; }
-    }
-    L->state_gen = c->state_gen;   // the owner's generation invalidates the lane's captured batch too
+// `regions` per-thread overflow regions of the traversal stacks, each for the largest persistent grid the scene launches, preset to a
+// word no stack entry can be (a node index of 2.1e9; leaf codes are negative): vpt_get_stats counts what was spilled.
+int alloc_spill(vpt_ctx* c, Lane& L, int regions) {
+    const size_t region = stack_overflow_bytes((uint32_t)c->max_blocks);
+    HIPCHK(c, hipMalloc((void**)&L.spill, regions * region));
+    L.spill2 = regions > 1 ? (uint32_t*)((char*)L.spill + region) : L.spill;
+    HIPCHK(c, memset_now(L.stream, L.spill, kSpillPatternByte, regions * region));
+    L.stack_overflow_words = (uint32_t)(region / 4);
     return VPT_OK;
 }
-void destroy_lane(vpt_ctx* L) {
-    if (!L) return;
-    if (L->stream) (void)hipStreamSynchronize(L->stream);
-    destroy_graph(L);
-    L->image = nullptr; L->full_image = nullptr;   // borrowed
-    free_render_buffers(L);
-    if (L->lane_spill) (void)hipFree(L->lane_spill);
-    for (int k = 0; k < kTickets; k++) if (L->tick_ev[k]) (void)hipEventDestroy(L->tick_ev[k]);
-    if (L->h_ctr) (void)hipHostFree(L->h_ctr);
-    if (L->d_dispatch_base) (void)hipFree(L->d_dispatch_base);
-    if (L->d_spill_count) (void)hipFree(L->d_spill_count);
-    if (L->ctr) (void)hipFree(L->ctr);
-    if (L->sctr) (void)hipFree(L->sctr);
-    if (L->d_launch_off) (void)hipFree(L->d_launch_off);
-    if (L->ev_shade) (void)hipEventDestroy(L->ev_shade);
-    if (L->ev_join) (void)hipEventDestroy(L->ev_join);
-    if (L->ev_resolved) (void)hipEventDestroy(L->ev_resolved);
-    if (L->ev_post) (void)hipEventDestroy(L->ev_post);
-    if (L->stream2) (void)hipStreamDestroy(L->stream2);
-    if (L->stream) (void)hipStreamDestroy(L->stream);
-    delete L;
+// The one teardown of a lane: nothing of it is in flight, then its graph, its buffers, its events and streams.
+void lane_destroy(Lane& L) {
+    if (L.stream) (void)hipStreamSynchronize(L.stream);
+    if (L.stream2) (void)hipStreamSynchronize(L.stream2);
+    free_path_buffers(L);   // (the captured graph first)
+    free_spill(L);
+    if (L.h_ctr) (void)hipHostFree(L.h_ctr);
+    if (L.d_dispatch_base) (void)hipFree(L.d_dispatch_base);
+    if (L.ctr) (void)hipFree(L.ctr);
+    if (L.sctr) (void)hipFree(L.sctr);
+    for (hipEvent_t e : {L.ev_shade, L.ev_join, L.ev_resolved}) if (e) (void)hipEventDestroy(e);
+    if (L.stream2) (void)hipStreamDestroy(L.stream2);
+    if (L.stream) (void)hipStreamDestroy(L.stream);
+    L = Lane{};
+}
+// Lane k >= 1: created on first use with one frame of path buffers for the context's image size and one spill region (its batches stay on
+// one stream).  nullptr: out of memory — pipelining is an optimisation, the frame then goes to a lane there is.
+Lane* get_lane(vpt_ctx* c, int k) {
+    Lane*& slot = c->extra[k - 1];
+    if (slot) return slot;
+    Lane* L = new Lane();
+    if (lane_init(c, *L) != VPT_OK || alloc_path_buffers(c, *L, 1, 1) != VPT_OK || alloc_spill(c, *L, 1) != VPT_OK) {
+        (void)hipGetLastError();
+        lane_destroy(*L);
+        delete L;
+        c->err.clear();
+        return nullptr;
+    }
+    return slot = L;
+}
+// The lane's per-sample words must cover the next batch (samples_per_frame may have changed since; vpt_set_params drained every lane
+// before it did, so nothing of this lane is in flight when they are replaced).
+int ensure_lane_buffers(vpt_ctx* c, Lane& L) {
+    return path_words_ok(c, L) ? VPT_OK : alloc_path_buffers(c, L, 1, 1);
 }
 void destroy_lanes(vpt_ctx* c) {
-    for (vpt_ctx*& L : c->lanes) { destroy_lane(L); L = nullptr; }
+    for (Lane*& L : c->extra)
+        if (L) { lane_destroy(*L); delete L; L = nullptr; }
     c->order_lane = nullptr;
 }
 
@@ -1153,7 +1159,11 @@ vpt_ctx* vpt_create(const vpt_config* cfg, int* err) {
     c->cfg = *cfg;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) c->cu_count = prop.multiProcessorCount;
-    if (init_ctx_resources(c) != VPT_OK) { (void)hipGetLastError(); set(VPT_ERR_DEVICE); vpt_destroy(c); return nullptr; }
+    bool ok = lane_init(c, c->main) == VPT_OK && hipEventCreateWithFlags(&c->ev_post, hipEventDisableTiming) == hipSuccess &&
+              hipMalloc((void**)&c->d_launch_off, (plan::kMaxFramesInFlight + 1) * 4) == hipSuccess && hipMalloc((void**)&c->d_spill_count, 256) == hipSuccess;
+    for (int k = 0; ok && k < kTickets; k++)
+        if (hipEventCreateWithFlags(&c->tick_ev[k], hipEventDisableTiming) != hipSuccess) { c->tick_ev[k] = nullptr; ok = false; }
+    if (!ok) { (void)hipGetLastError(); set(VPT_ERR_DEVICE); vpt_destroy(c); return nullptr; }
     vpt_default_params(&c->params);
     const float id[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     memcpy(c->P.view_inv, id, 64); memcpy(c->P.proj_inv, id, 64);
@@ -1167,31 +1177,22 @@ vpt_ctx* vpt_create(const vpt_config* cfg, int* err) {
 void vpt_destroy(vpt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+    if (c->main.stream) (void)hipStreamSynchronize(c->main.stream);
+    if (c->main.stream2) (void)hipStreamSynchronize(c->main.stream2);
     destroy_lanes(c);
-    destroy_graph(c);
     if (c->comm) { (void)ncclCommDestroy(c->comm); c->comm = nullptr; }
-    if (c->ev_resolved) (void)hipEventDestroy(c->ev_resolved);
     if (c->ev_post) (void)hipEventDestroy(c->ev_post);
     for (int k = 0; k < kTickets; k++) if (c->tick_ev[k]) (void)hipEventDestroy(c->tick_ev[k]);
-    if (c->h_ctr) (void)hipHostFree(c->h_ctr);
-    if (c->d_dispatch_base) (void)hipFree(c->d_dispatch_base);
     if (c->d_spill_count) (void)hipFree(c->d_spill_count);
     free_lab(c);
     free_scene(c);
     free_render_buffers(c);
-    if (c->ctr) (void)hipFree(c->ctr);
-    if (c->sctr) (void)hipFree(c->sctr);
     if (c->d_launch_off) (void)hipFree(c->d_launch_off);
     if (c->d_volumes) (void)hipFree(c->d_volumes);
     for (DensityGrid& g : c->grids) { (void)hipFree((void*)g.values); (void)hipFree((void*)g.block_max); }
     if (c->d_grids) (void)hipFree(c->d_grids);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->ev_shade) (void)hipEventDestroy(c->ev_shade);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    lane_destroy(c->main);
     delete c;
 }
 
@@ -1384,32 +1385,22 @@ int vpt_set_scene(vpt_ctx* c, const vpt_scene_desc* sd) {
     c->media_tail_blocks = media_tail_blocks_per_cu() * c->cu_count;
     c->shadow_blocks = trace_shadow_blocks_per_cu() * c->cu_count;
     c->vote_blocks = std::min(trace_blocks_per_cu(VPT_TRACE_VOTE, false), trace_blocks_per_cu(VPT_TRACE_VOTE, true)) * c->cu_count;
-    {   // per-thread overflow region of the traversal stacks, for the largest persistent grid launched
-        c->max_blocks = std::max(std::max(std::max(std::max(c->trav_blocks, c->shade_blocks), std::max(c->primary_blocks, c->whole_blocks)), c->vote_blocks), std::max(std::max(c->shade_stream_blocks, c->finish_blocks), c->shadow_blocks));
-        void* d = nullptr;
-        // two regions: the shadow kernels of bounce k run on the second stream beside the extend kernel of bounce k + 1, and a
-        // spill slot is addressed by (block, thread) alone, so concurrent grids must not share one region (round 2 did)
-        const size_t region = stack_overflow_bytes((uint32_t)c->max_blocks);
-        HIPCHK(c, hipMalloc(&d, 2 * region));
-        c->scene_allocs.push_back(d);
-        D.stack_overflow = (uint32_t*)d;
-        c->stack_overflow2 = (uint32_t*)((char*)d + region);
-        // preset to a word no stack entry can be (a node index of 2.1e9; leaf codes are negative): vpt_get_stats counts what was spilled
-        HIPCHK(c, memset_now(c->stream, d, kSpillPatternByte, 2 * region));
-        c->stack_overflow_words = (uint32_t)(region / 4);
-        c->spill_dirty = true;
-    }
-    launch_precompute_tri_ng(c->stream, D, c->d_tri_ng);
-    launch_precompute_tri_shade(c->stream, D, c->d_tri_shade);
-    launch_precompute_materials(c->stream, D, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
-    launch_classify_instances(c->stream, D, c->d_inst_class, (uint32_t)c->instances.size());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->max_blocks = std::max(std::max(std::max(std::max(c->trav_blocks, c->shade_blocks), std::max(c->primary_blocks, c->whole_blocks)), c->vote_blocks), std::max(std::max(c->shade_stream_blocks, c->finish_blocks), c->shadow_blocks));
+    // two regions: the shadow kernels of bounce k run on the second stream beside the extend kernel of bounce k + 1, and a
+    // spill slot is addressed by (block, thread) alone, so concurrent grids must not share one region (round 2 did)
+    if ((rc = alloc_spill(c, c->main, 2))) return rc;
+    c->spill_dirty = true;
+    launch_precompute_tri_ng(c->main.stream, D, c->d_tri_ng);
+    launch_precompute_tri_shade(c->main.stream, D, c->d_tri_shade);
+    launch_precompute_materials(c->main.stream, D, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
+    launch_classify_instances(c->main.stream, D, c->d_inst_class, (uint32_t)c->instances.size());
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     if ((rc = update_class_present(c))) return rc;
     HIPCHK(c, hipGetLastError());
     c->has_scene = true;
     update_depth_bounded(c);
     // (after a failed vpt_resize there is no image to clear: the scene is installed all the same, rendering needs a successful resize first)
-    if (c->buffers_ok) HIPCHK(c, memset_now(c->stream, c->image, 0, (size_t)c->P.shard_pixels * 16));
+    if (c->buffers_ok) HIPCHK(c, memset_now(c->main.stream, c->image, 0, (size_t)c->P.shard_pixels * 16));
     c->set_scene_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scene0).count();
     return check_stream_slack(c);
 }
@@ -1429,9 +1420,9 @@ int vpt_set_material(vpt_ctx* c, uint32_t index, const vpt_material* m) {
     c->materials[index] = *m;
     HIPCHK(c, hipMemcpy(c->d_materials + index, m, sizeof(vpt_material), hipMemcpyHostToDevice));
     if (emissive_changed) { build_emissive(c); int rc = upload_emissive(c); if (rc) return rc; }
-    launch_precompute_materials(c->stream, c->dsc, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
-    launch_classify_instances(c->stream, c->dsc, c->d_inst_class, (uint32_t)c->instances.size());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    launch_precompute_materials(c->main.stream, c->dsc, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
+    launch_classify_instances(c->main.stream, c->dsc, c->d_inst_class, (uint32_t)c->instances.size());
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     { int rc2 = update_class_present(c); if (rc2) return rc2; }
     update_depth_bounded(c);
     reset_accum(c);
@@ -1471,9 +1462,9 @@ int vpt_set_params(vpt_ctx* c, const vpt_params* p) {
     reset_accum(c);
     if (flags_changed && c->has_scene) {  // FURNACE_TEST_MODE is baked into the resolved-material table
         HIPCHK(c, hipSetDevice(c->cfg.device));
-        launch_precompute_materials(c->stream, c->dsc, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
-        launch_classify_instances(c->stream, c->dsc, c->d_inst_class, (uint32_t)c->instances.size());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        launch_precompute_materials(c->main.stream, c->dsc, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
+        launch_classify_instances(c->main.stream, c->dsc, c->d_inst_class, (uint32_t)c->instances.size());
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         int rc2 = update_class_present(c); if (rc2) return rc2;
     }
     return VPT_OK;
@@ -1492,7 +1483,7 @@ int vpt_set_volumes(vpt_ctx* c, const vpt_volume* v, uint32_t count) {
     }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->state_gen++;
     if (c->d_volumes) { (void)hipFree(c->d_volumes); c->d_volumes = nullptr; }
     c->volumes.assign(v, v + count);
@@ -1525,7 +1516,7 @@ int vpt_add_density_grid(vpt_ctx* c, uint32_t dx, uint32_t dy, uint32_t dz, cons
             }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->state_gen++;
     DensityGrid g{};
     float *dv = nullptr, *db = nullptr;
@@ -1546,7 +1537,7 @@ int vpt_clear_density_grids(vpt_ctx* c) {
     for (const vpt_volume& v : c->volumes) if (v.density_data_index >= 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "a volume still references a density grid");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->state_gen++;
     for (DensityGrid& g : c->grids) { (void)hipFree((void*)g.values); (void)hipFree((void*)g.block_max); }
     c->grids.clear();
@@ -1619,9 +1610,9 @@ int next_batch(vpt_ctx* c, uint32_t left, uint32_t* nf) {
     }
     n = plan::fit_batch(policy_of(c), plan_state(c), n);
     if (plan::media_on_streams(facts_of(c))) {   // media on the streams: the batch is what the media streams hold
-        int rm = ensure_media_buffers(c);
+        int rm = ensure_media_buffers(c, c->main);
         if (rm) return rm;
-        n = std::min(n, c->media_frames);
+        n = std::min(n, c->main.media_frames);
     }
     *nf = n;
     return VPT_OK;
@@ -1673,63 +1664,52 @@ int vpt_render_async(vpt_ctx* c, uint32_t dispatches, int* done, uint64_t* ticke
         if (c->graph_streak_gen == c->state_gen) c->graph_streak++; else { c->graph_streak = 0; c->graph_streak_gen = c->state_gen; }
         const plan::Facts f = facts_of(c);
         plan::Schedule sd;
-        if ((rc = decide_batch(c, f, nf, base, false, sd))) return rc;
-        const plan::AsyncShape shape = plan::async_shape(f, sd, nf, c->resident_alloc, c->graph_streak);
+        if ((rc = decide_batch(c, c->main, f, nf, base, false, sd))) return rc;
+        const plan::AsyncShape shape = plan::async_shape(f, sd, nf, c->main.resident_alloc, c->graph_streak);
         const bool fixed = shape.fixed;
         const uint32_t enq = shape.bounces_to_enqueue;
-        // the fixed 1-frame batch goes to the next lane (vpt_ctx::lanes); asked for again with nothing changed since the last two calls it
+        // the fixed 1-frame batch goes to the next lane (vpt_ctx::main / extra); asked for again with nothing changed since the last two calls it
         // is replayed from the lane's captured graph
-        vpt_ctx* X = c;
+        Lane* X = &c->main;
         if (shape.lanes_ok) {
-            const uint32_t max_lanes = std::max(1u, std::min(c->lab_lanes, 3u));
-            vpt_ctx* idle = nullptr;
-            uint32_t have = 1;
-            if (hipEventQuery(c->ev_resolved) == hipSuccess) idle = c;
-            for (uint32_t k = 0; k + 1 < max_lanes; k++) {
-                vpt_ctx* L = c->lanes[k];
-                if (!L) { if (!idle) { L = get_lane(c, (int)k); if (L) idle = L; } break; }   // every existing lane is busy: one more
+            const int max_lanes = (int)std::max(1u, std::min(c->lab_lanes, (uint32_t)kLanes));
+            Lane* idle = nullptr;   // the first lane whose previous frame has been resolved
+            uint32_t have = 0;
+            for (int k = 0; k < max_lanes; k++) {
+                Lane* L = c->lane(k);
+                if (!L) { if (!idle) idle = get_lane(c, k); break; }   // every existing lane is busy: one more
                 have++;
                 if (!idle && hipEventQuery(L->ev_resolved) == hipSuccess) idle = L;
             }
             (void)hipGetLastError();   // (hipErrorNotReady is not an error)
-            if (!idle) {   // all lanes busy: round robin
-                const uint32_t k = c->lane_rr++ % have;
-                idle = k == 0u ? c : c->lanes[k - 1];
-            }
+            if (!idle) idle = c->lane((int)(c->lane_rr++ % have));   // all lanes busy: round robin
             X = idle;
-            if (X != c) {   // the lane runs the schedule its owner decides: the owner's facts, the lane's buffers
-                const int rc_lane = sync_lane(c, X); if (rc_lane != VPT_OK) return rc_lane;
-                if ((rc = decide_batch(X, f, nf, base, false, sd))) { c->err = X->err; return rc; }
+            if (X != &c->main) {   // the same decision on the lane's own buffers
+                if ((rc = ensure_lane_buffers(c, *X))) return rc;
+                if ((rc = decide_batch(c, *X, f, nf, base, false, sd))) return rc;
             }
         }
         // a batch on the main lane behind pipelined frames: their resolves come first (frame order), and the records it overwrites are the main lane's own
-        if (X == c && c->order_lane && c->order_lane != c) HIPCHK(c, hipStreamWaitEvent(c->stream, c->order_lane->ev_resolved, 0));
+        if (X == &c->main && c->order_lane && c->order_lane != X) HIPCHK(c, hipStreamWaitEvent(X->stream, c->order_lane->ev_resolved, 0));
         BatchState b;
         bool graphed = false;
         // Frames in steady accumulation share the chip: each lane's kernels take a third of the persistent grid (one block per CU of the
         // three the fused kernel's LDS allows), so that the three lanes' chains are co-resident and the tail of one frame — launches that are
         // bounded by one bounce's latency, not by throughput — runs beside the first bounces of the next two.  (A full-size grid fills every
         // CU's LDS and keeps the other lanes' blocks out until it retires.)
-        const int full_grid = X->primary_blocks;
+        Grids grids{c->primary_blocks, 0};
         auto part = [&](uint32_t div) { return std::max(c->cu_count, (c->primary_blocks / (int)std::max(1u, div) / std::max(c->cu_count, 1)) * c->cu_count); };
         if (shape.partial_grids) {
-            X->primary_blocks = part(std::max(1u, c->lab_lane_grid));
-            X->tail_blocks = c->lab_tail_grid > 1u ? std::min(X->primary_blocks, part(c->lab_tail_grid)) : 0;
+            grids.primary = part(std::max(1u, c->lab_lane_grid));
+            grids.tail = c->lab_tail_grid > 1u ? std::min(grids.primary, part(c->lab_tail_grid)) : 0;
         }
-        if (shape.graph_ok) {
-            rc = enqueue_graph(X, f, nf, base, enq, &graphed, b);
-            if (rc) { X->primary_blocks = full_grid; X->tail_blocks = 0; if (X != c) c->err = X->err; return rc; }
-        }
-        if (!graphed) {
-            rc = enqueue_fixed(X, sd, nf, base, enq, b);
-            if (rc) { X->primary_blocks = full_grid; X->tail_blocks = 0; if (X != c) c->err = X->err; return rc; }
-        }
-        X->primary_blocks = full_grid; X->tail_blocks = 0;
+        if (shape.graph_ok && (rc = enqueue_graph(c, *X, f, nf, base, enq, grids, &graphed, b))) return rc;
+        if (!graphed && (rc = enqueue_fixed(c, *X, sd, nf, base, enq, grids, b))) return rc;
         if (fixed && b.n_slots) {   // frames resolve in order: this one's resolve waits for the previous frame's, whichever lane that ran on
             if (c->order_lane && c->order_lane != X) HIPCHK(c, hipStreamWaitEvent(X->stream, c->order_lane->ev_resolved, 0));
-            if (c->post_pending && X != c) HIPCHK(c, hipStreamWaitEvent(X->stream, c->ev_post, 0));   // ... and for the post-process that is still reading the image
+            if (c->post_pending && X != &c->main) HIPCHK(c, hipStreamWaitEvent(X->stream, c->ev_post, 0));   // ... and for the post-process that is still reading the image
         }
-        if ((rc = batch_resolve(X, b))) { if (X != c) c->err = X->err; return rc; }
+        if ((rc = batch_resolve(c, *X, b))) return rc;
         if (fixed && b.n_slots) {
             HIPCHK(c, hipEventRecord(X->ev_resolved, X->stream));
             c->order_lane = X;
@@ -1761,8 +1741,8 @@ int vpt_get_radiance_device(vpt_ctx* c, void* dst) {
     if (c->P.shard_count > 1 && !c->full_valid) return fail(c, VPT_ERR_INVALID_ARGUMENT, "sharded context: call vpt_assemble_shards first");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
-    HIPCHK(c, hipMemcpyAsync(dst, whole_image(c), (size_t)c->P.width * c->P.height * 16, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, whole_image(c), (size_t)c->P.width * c->P.height * 16, hipMemcpyDeviceToDevice, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return VPT_OK;
 }
 int vpt_get_radiance(vpt_ctx* c, float* dst) {
@@ -1805,9 +1785,9 @@ int vpt_get_shard_device(vpt_ctx* c, void* dst) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
     size_t bytes = (size_t)c->P.shard_pixels * 16, padded = vpt_shard_floats(c) * 4;
-    HIPCHK(c, hipMemcpyAsync(dst, c->image, bytes, hipMemcpyDeviceToDevice, c->stream));
-    if (padded > bytes) HIPCHK(c, hipMemsetAsync((char*)dst + bytes, 0, padded - bytes, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, c->image, bytes, hipMemcpyDeviceToDevice, c->main.stream));
+    if (padded > bytes) HIPCHK(c, hipMemsetAsync((char*)dst + bytes, 0, padded - bytes, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return VPT_OK;
 }
 int vpt_assemble_shards(vpt_ctx* c, const void* gathered, uint32_t shard_count) {
@@ -1817,8 +1797,8 @@ int vpt_assemble_shards(vpt_ctx* c, const void* gathered, uint32_t shard_count) 
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
     float* dst = c->P.shard_count > 1 ? c->full_image : c->image;
-    launch_scatter_rows(c->stream, (const float*)gathered, dst, c->P.width, c->P.height, shard_count, (uint32_t)(vpt_shard_floats(c) / 4));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    launch_scatter_rows(c->main.stream, (const float*)gathered, dst, c->P.width, c->P.height, shard_count, (uint32_t)(vpt_shard_floats(c) / 4));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     HIPCHK(c, hipGetLastError());
     c->full_valid = true;
     return VPT_OK;
@@ -1829,7 +1809,7 @@ namespace {
 int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
     int rc = ensure_post_buffers(c);
     if (rc) return rc;
-    hipStream_t s = c->stream;
+    hipStream_t s = c->main.stream;
     const float* hdr = whole_image(c);
     const uint32_t W = c->P.width, H = c->P.height;
     uint32_t mip_count = std::max(1u, std::min(pp->mip_count, (uint32_t)c->mips.size()));
@@ -1837,19 +1817,19 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
     auto MW = [&](uint32_t i) { return c->mip_sizes[i].first; };
     auto MH = [&](uint32_t i) { return c->mip_sizes[i].second; };
     if (pp->schedule == VPT_POST_REFERENCE_PASSES) {   // PostProcessor.cpp:193-246 pass by pass: threshold, down x (n-1), up x (n-1), tonemap
-        TIMED(c, VPT_K_BLOOM, launch_bloom_threshold(s, hdr, c->mips[0], W, H, pp->bloom_threshold, pp->falloff_range));
+        TIMED(c, s, VPT_K_BLOOM, launch_bloom_threshold(s, hdr, c->mips[0], W, H, pp->bloom_threshold, pp->falloff_range));
         for (uint32_t i = 1; i < mip_count; i++)
-            TIMED(c, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
+            TIMED(c, s, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
         for (uint32_t i = mip_count - 1; i > 0; i--)
-            TIMED(c, VPT_K_BLOOM, launch_bloom_up(s, c->mips[i], MW(i), MH(i), c->mips[i - 1], MW(i - 1), MH(i - 1), pp->bloom_strength));
-        TIMED(c, VPT_K_TONEMAP, launch_tonemap(s, hdr, c->mips[0], c->post_out, W, H, pp->exposure, pp->gamma, linear_tap));
+            TIMED(c, s, VPT_K_BLOOM, launch_bloom_up(s, c->mips[i], MW(i), MH(i), c->mips[i - 1], MW(i - 1), MH(i - 1), pp->bloom_strength));
+        TIMED(c, s, VPT_K_TONEMAP, launch_tonemap(s, hdr, c->mips[0], c->post_out, W, H, pp->exposure, pp->gamma, linear_tap));
     } else {
         // Fused schedule, same values (kernels_post.hip): mip 0 is never materialised unless the caller asks for it.
         //   T = first mip the one-launch tail keeps in LDS (<= kBloomTailMaxTexels texels, and >= 2: its base mip must exist in memory)
         uint32_t T = mip_count;
         for (uint32_t i = 2; i < mip_count; i++) if ((uint64_t)MW(i) * MH(i) <= kBloomTailMaxTexels) { T = i; break; }
         if (mip_count - T > kBloomTailMaxLevels) T = mip_count;   // cannot happen with <= 10 mips; the per-pass kernels cover it
-        if (mip_count >= 2) TIMED(c, VPT_K_BLOOM, launch_bloom_down_first(s, hdr, W, H, c->mips[1], MW(1), MH(1), pp->bloom_strength, pp->bloom_threshold, pp->falloff_range));
+        if (mip_count >= 2) TIMED(c, s, VPT_K_BLOOM, launch_bloom_down_first(s, hdr, W, H, c->mips[1], MW(1), MH(1), pp->bloom_strength, pp->bloom_threshold, pp->falloff_range));
         {   // down-samples between mip 1 and the tail's base: one launch each while the levels are large, the last (up to three, at most
             // kBloomDownChainTexels texels in the first of them) in one launch
             const uint32_t last = std::min(T, mip_count) - 1;   // last level produced here
@@ -1859,10 +1839,10 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
                 if (left >= 2 && left <= kBloomDownChainMax && (uint64_t)MW(i) * MH(i) <= kBloomDownChainTexels) {
                     float* lv[kBloomDownChainMax]; uint32_t lw[kBloomDownChainMax], lh[kBloomDownChainMax];
                     for (uint32_t k = 0; k < left; k++) { lv[k] = c->mips[i + k]; lw[k] = MW(i + k); lh[k] = MH(i + k); }
-                    TIMED(c, VPT_K_BLOOM, launch_bloom_down_chain(s, c->mips[i - 1], MW(i - 1), MH(i - 1), lv, lw, lh, left, pp->bloom_strength));
+                    TIMED(c, s, VPT_K_BLOOM, launch_bloom_down_chain(s, c->mips[i - 1], MW(i - 1), MH(i - 1), lv, lw, lh, left, pp->bloom_strength));
                     i += left;
                 } else {
-                    TIMED(c, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
+                    TIMED(c, s, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
                     i++;
                 }
             }
@@ -1872,7 +1852,7 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
             uint32_t tw[kBloomTailMaxLevels], th[kBloomTailMaxLevels];
             for (uint32_t i = T; i < mip_count; i++) { tw[i - T] = MW(i); th[i - T] = MH(i); }
             const bool staged = bloom_tail_is_staged(MW(T - 1), MH(T - 1));
-            TIMED(c, VPT_K_BLOOM, launch_bloom_tail(s, c->mips[T - 1], c->mips[T], MW(T - 1), MH(T - 1), tw, th, mip_count - T, pp->bloom_strength));
+            TIMED(c, s, VPT_K_BLOOM, launch_bloom_tail(s, c->mips[T - 1], c->mips[T], MW(T - 1), MH(T - 1), tw, th, mip_count - T, pp->bloom_strength));
             if (staged) up_from = T;   // the staged tail leaves mip T finished in memory and mip T - 1 as the down-samples left it
         }
         // up-samples of the levels between the tail and mip 1: up to kBloomChainMax of them per launch, only the lowest level written
@@ -1880,15 +1860,15 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
         for (uint32_t top = up_from; top > 1;) {
             const uint32_t n = std::min(top - 1u, kBloomChainMax), base = top - n;
             if (n == 1) {
-                TIMED(c, VPT_K_BLOOM, launch_bloom_up(s, c->mips[top], MW(top), MH(top), c->mips[base], MW(base), MH(base), pp->bloom_strength));
+                TIMED(c, s, VPT_K_BLOOM, launch_bloom_up(s, c->mips[top], MW(top), MH(top), c->mips[base], MW(base), MH(base), pp->bloom_strength));
             } else {
                 float* lv[kBloomChainMax + 1]; uint32_t lw[kBloomChainMax + 1], lh[kBloomChainMax + 1];
                 for (uint32_t k = 0; k <= n; k++) { lv[k] = c->mips[base + k]; lw[k] = MW(base + k); lh[k] = MH(base + k); }
-                TIMED(c, VPT_K_BLOOM, launch_bloom_up_chain(s, lv, lw, lh, n, pp->bloom_strength));
+                TIMED(c, s, VPT_K_BLOOM, launch_bloom_up_chain(s, lv, lw, lh, n, pp->bloom_strength));
             }
             top = base;
         }
-        TIMED(c, VPT_K_TONEMAP, launch_post_final(s, hdr, mip_count >= 2 ? c->mips[1] : nullptr, mip_count >= 2 ? MW(1) : 0u, mip_count >= 2 ? MH(1) : 0u,
+        TIMED(c, s, VPT_K_TONEMAP, launch_post_final(s, hdr, mip_count >= 2 ? c->mips[1] : nullptr, mip_count >= 2 ? MW(1) : 0u, mip_count >= 2 ? MH(1) : 0u,
                                                   bloom0 ? c->mips[0] : nullptr, c->post_out, W, H, pp->bloom_threshold, pp->falloff_range, pp->bloom_strength,
                                                   pp->exposure, pp->gamma, linear_tap));
     }
@@ -1909,7 +1889,7 @@ int vpt_postprocess(vpt_ctx* c, const vpt_post_params* pp, uint8_t* out8, float*
     if ((rc = drain(c))) return rc;
     if ((rc = enqueue_post(c, pp, bloom0 != nullptr))) return rc;
     const uint32_t W = c->P.width, H = c->P.height;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     collect_timing(c);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpy(out8, c->post_out, (size_t)W * H * 4, hipMemcpyDeviceToHost));
@@ -1924,12 +1904,12 @@ int vpt_postprocess_device(vpt_ctx* c, const vpt_post_params* pp, void* rgba8_de
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((rc = finish_outstanding(c))) return rc;   // the image must be complete: an unfinished batch is finished first
-    if (c->order_lane && c->order_lane != c) HIPCHK(c, hipStreamWaitEvent(c->stream, c->order_lane->ev_resolved, 0));   // the latest frame was resolved on another lane
+    if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));   // the latest frame was resolved on another lane
     if ((rc = enqueue_post(c, pp, false))) return rc;
-    if (rgba8_device) HIPCHK(c, hipMemcpyAsync(rgba8_device, c->post_out, (size_t)c->P.width * c->P.height * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_post, c->stream));
+    if (rgba8_device) HIPCHK(c, hipMemcpyAsync(rgba8_device, c->post_out, (size_t)c->P.width * c->P.height * 4, hipMemcpyDeviceToDevice, c->main.stream));
+    HIPCHK(c, hipEventRecord(c->ev_post, c->main.stream));
     c->post_pending = true;
-    const uint64_t t = issue_ticket(c, c->stream);
+    const uint64_t t = issue_ticket(c, c->main.stream);
     if (ticket) *ticket = t;
     return VPT_OK;
 }
@@ -1939,7 +1919,7 @@ int vpt_get_output(vpt_ctx* c, uint8_t* out8) {
     if (!c->post_out) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_get_output before the first post-process");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     HIPCHK(c, hipMemcpy(out8, c->post_out, (size_t)c->post_w * c->post_h * 4, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
@@ -1958,21 +1938,22 @@ int vpt_get_stats(vpt_ctx* c, vpt_stats* out) {
     s.emissive_mesh_count = (uint32_t)c->emissive.size(); s.emissive_triangle_count = c->emissive_tris;
     s.frames_in_flight = batch_cap(c); s.shard_pixels = c->P.shard_pixels;   // (the largest batch the context renders at once with its current scene and parameters)
     s.build_flags = (c->sbvh ? VPT_BUILD_SBVH : 0u) | (c->cfg.build_flags & (VPT_BUILD_GENERAL_KERNELS | VPT_BUILD_STREAMS_ONLY));
-    s.frames_allocated = c->frames_alloc; s.resident_frames = c->resident_alloc;
+    s.frames_allocated = c->main.frames_alloc; s.resident_frames = c->main.resident_alloc;
     s.set_scene_ms = c->set_scene_ms; s.bvh_build_ms = c->bvh_build_ms;
     // what the traversal kernels have written into their spill regions: counted when something has run since the last count (the scan reads
     // ~0.4 GB: a host that asks for the statistics after every frame would otherwise pay 0.1-0.2 ms per call for a number that does not change)
-    if (c->has_scene && c->stack_overflow_words && c->dsc.stack_overflow && c->spill_dirty) {
+    if (c->has_scene && c->main.spill && c->spill_dirty) {
         HIPCHK(c, hipSetDevice(c->cfg.device));
         unsigned long long h[2] = {0ull, 0ull};
-        HIPCHK(c, hipMemsetAsync(c->d_spill_count, 0, 16, c->stream));
-        hipLaunchKernelGGL(k_count_spilled, dim3(1024), dim3(256), 0, c->stream, c->dsc.stack_overflow, c->stack_overflow_words, c->d_spill_count);
-        hipLaunchKernelGGL(k_count_spilled, dim3(1024), dim3(256), 0, c->stream, c->stack_overflow2, c->stack_overflow_words, c->d_spill_count + 1);
-        for (vpt_ctx* L : c->lanes)   // the lanes' own regions (pipelined asynchronous frames) count towards the first figure
-            if (L && L->lane_spill && L->stack_overflow_words)
-                hipLaunchKernelGGL(k_count_spilled, dim3(1024), dim3(256), 0, c->stream, (const uint32_t*)L->lane_spill, L->stack_overflow_words, c->d_spill_count);
-        HIPCHK(c, hipMemcpyAsync(h, c->d_spill_count, 16, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_spill_count, 0, 16, c->main.stream));
+        for (int k = 0; k < kLanes; k++) {   // first figure: every lane's region (the extra lanes': pipelined asynchronous frames), second: the main lane's second-stream region
+            const Lane* L = c->lane(k);
+            if (!L || !L->spill) continue;
+            hipLaunchKernelGGL(k_count_spilled, dim3(1024), dim3(256), 0, c->main.stream, L->spill, L->stack_overflow_words, c->d_spill_count);
+            if (L->spill2 != L->spill) hipLaunchKernelGGL(k_count_spilled, dim3(1024), dim3(256), 0, c->main.stream, L->spill2, L->stack_overflow_words, c->d_spill_count + 1);
+        }
+        HIPCHK(c, hipMemcpyAsync(h, c->d_spill_count, 16, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         c->spill_cached[0] = h[0]; c->spill_cached[1] = h[1];
         c->spill_dirty = false;
     }
@@ -1985,9 +1966,8 @@ int vpt_reset_stats(vpt_ctx* c) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
     c->stats = vpt_stats{};
-    HIPCHK(c, memset_now(c->stream, c->ctr, 0, sizeof(Counters)));
-    memset(c->h_ctr, 0, sizeof(HostCounters));
-    for (vpt_ctx* L : c->lanes) if (L) { HIPCHK(c, memset_now(L->stream, L->ctr, 0, sizeof(Counters))); memset(L->h_ctr, 0, sizeof(HostCounters)); L->stats = vpt_stats{}; }
+    for (int k = 0; k < kLanes; k++)
+        if (Lane* L = c->lane(k)) { HIPCHK(c, memset_now(L->stream, L->ctr, 0, sizeof(Counters))); memset(L->h_ctr, 0, sizeof(HostCounters)); }
     return VPT_OK;
 }
 
@@ -2004,8 +1984,8 @@ int vpt_trace_rays(vpt_ctx* c, const vpt_ray* rays, uint32_t n, vpt_hit* hits) {
     if (hipMemcpy(dr, rays, (size_t)n * sizeof(vpt_ray), hipMemcpyHostToDevice) != hipSuccess) rc = VPT_ERR_DEVICE;
     if (!rc) {
         c->spill_dirty = true;   // a traversal kernel runs: vpt_get_stats recounts the spill regions
-        launch_trace_rays(c->stream, (uint32_t)c->max_blocks, c->dsc, dr, n, dh);
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = VPT_ERR_DEVICE;
+        launch_trace_rays(c->main.stream, (uint32_t)c->max_blocks, lane_scene(c, c->main), dr, n, dh);
+        if (hipStreamSynchronize(c->main.stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = VPT_ERR_DEVICE;
     }
     if (!rc && hipMemcpy(hits, dh, (size_t)n * sizeof(vpt_hit), hipMemcpyDeviceToHost) != hipSuccess) rc = VPT_ERR_DEVICE;
     (void)hipFree(dr); (void)hipFree(dh);
@@ -2028,8 +2008,8 @@ int nccl_fail(vpt_ctx* c, const char* what, ncclResult_t r) {
 // root: gather_buf -> full image (rows re-interleaved); shard_count == 1: the image already is the whole image
 int assemble_from_gather_buf(vpt_ctx* c) {
     if (c->P.shard_count == 1) return VPT_OK;
-    launch_scatter_rows(c->stream, c->gather_buf, c->full_image, c->P.width, c->P.height, c->P.shard_count, (uint32_t)(vpt_shard_floats(c) / 4));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    launch_scatter_rows(c->main.stream, c->gather_buf, c->full_image, c->P.width, c->P.height, c->P.shard_count, (uint32_t)(vpt_shard_floats(c) / 4));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     HIPCHK(c, hipGetLastError());
     c->full_valid = true;
     return VPT_OK;
@@ -2075,9 +2055,9 @@ int vpt_comm_gather_shards(vpt_ctx* c, int root) {
     if (is_root) { int rc = ensure_gather_buf(c); if (rc) return rc; }
     // every rank contributes its rows padded to the largest shard (the image buffer is allocated at that size);
     // the launch is ordered behind the renders already on the context's stream
-    ncclResult_t r = ncclGather(c->image, is_root ? c->gather_buf : nullptr, vpt_shard_floats(c), ncclFloat32, root, c->comm, c->stream);
+    ncclResult_t r = ncclGather(c->image, is_root ? c->gather_buf : nullptr, vpt_shard_floats(c), ncclFloat32, root, c->comm, c->main.stream);
     if (r != ncclSuccess) return nccl_fail(c, "ncclGather", r);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return is_root ? assemble_from_gather_buf(c) : VPT_OK;
 }
 int vpt_comm_get_info(vpt_ctx* c, vpt_comm_info* out) {
@@ -2134,11 +2114,11 @@ int vpt_multi_gather_shards(vpt_ctx* const* ctxs, uint32_t count, uint32_t root)
             if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); }  // the copy below then stages through the host
             else (void)hipGetLastError();
         }
-        HIPCHK(R, hipMemcpyPeerAsync((char*)R->gather_buf + (size_t)k * stride, R->cfg.device, c->image, c->cfg.device, stride, c->stream));
+        HIPCHK(R, hipMemcpyPeerAsync((char*)R->gather_buf + (size_t)k * stride, R->cfg.device, c->image, c->cfg.device, stride, c->main.stream));
     }
     for (uint32_t k = 0; k < count; k++) {
         HIPCHK(R, hipSetDevice(ctxs[k]->cfg.device));
-        HIPCHK(R, hipStreamSynchronize(ctxs[k]->stream));
+        HIPCHK(R, hipStreamSynchronize(ctxs[k]->main.stream));
     }
     HIPCHK(R, hipSetDevice(R->cfg.device));
     return assemble_from_gather_buf(R);
@@ -2204,7 +2184,7 @@ int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t
     if (order) HIPCHK(c, hipMemcpy(c->lab_order, order, (size_t)n * 4, hipMemcpyHostToDevice));
     TraceArgs a{};
     a.ro = c->lab_ro; a.rd = c->lab_rd; a.order = order ? c->lab_order : nullptr; a.hit = c->lab_hit; a.hinst = c->lab_hinst;
-    a.n = n; a.head = &c->ctr->extend_head; a.tmin = c->lab_tmin; a.tmax = c->lab_tmax; a.normalize_dir = 0u; a.param = (variant == VPT_TRACE_POOL || variant == VPT_TRACE_PAIR) ? param : param & 0xfff1ffffu;
+    a.n = n; a.head = &c->main.ctr->extend_head; a.tmin = c->lab_tmin; a.tmax = c->lab_tmax; a.normalize_dir = 0u; a.param = (variant == VPT_TRACE_POOL || variant == VPT_TRACE_PAIR) ? param : param & 0xfff1ffffu;
     a.cull = variant == VPT_TRACE_VOTE ? (param >> 17) & 1u : 0u;     // lab: bit 17 = stale-entry culling (closest-hit, VPT_TRACE_VOTE)
     a.one_tri = variant == VPT_TRACE_VOTE ? (param >> 19) & 1u : 0u;     // lab: bit 19 = one triangle per triangle step, as before round 4 (VPT_TRACE_VOTE, product vote parameters)
     a.packed = variant == VPT_TRACE_VOTE ? (param >> 18) & 1u : 0u;   // lab: bit 18 = packed plane arithmetic in the node step (VPT_TRACE_VOTE, product vote parameters)
@@ -2215,23 +2195,23 @@ int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t
     float best = 1e30f;
     for (uint32_t r = 0; r < reps + (visits ? 1u : 0u); r++) {
         const bool count = visits && r == reps;
-        HIPCHK(c, hipMemsetAsync(c->ctr, 0, sizeof(Counters), c->stream));
-        HIPCHK(c, hipEventRecord(e0, c->stream));
-        launch_trace(c->stream, blocks, variant, any_hit != 0, count, c->dsc, a, c->ctr);
-        HIPCHK(c, hipEventRecord(e1, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemsetAsync(c->main.ctr, 0, sizeof(Counters), c->main.stream));
+        HIPCHK(c, hipEventRecord(e0, c->main.stream));
+        launch_trace(c->main.stream, blocks, variant, any_hit != 0, count, lane_scene(c, c->main), a, c->main.ctr);
+        HIPCHK(c, hipEventRecord(e1, c->main.stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         HIPCHK(c, hipGetLastError());
         float ms = 0.0f;
         HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
         if (!count) best = std::min(best, ms);
         else {
             Counters h{};
-            HIPCHK(c, hipMemcpy(&h, c->ctr, sizeof(Counters), hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(&h, c->main.ctr, sizeof(Counters), hipMemcpyDeviceToHost));
             visits[0] = h.stat_nodes; visits[1] = h.stat_tris;
         }
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIPCHK(c, memset_now(c->stream, c->ctr, 0, sizeof(Counters)));
+    HIPCHK(c, memset_now(c->main.stream, c->main.ctr, 0, sizeof(Counters)));
     if (best_ms) *best_ms = best;
     if (hits) {
         std::vector<float4> h4(n); std::vector<uint32_t> hi(n, 0xffffffffu);
