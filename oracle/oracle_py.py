@@ -231,6 +231,12 @@ class Oracle:
         self.L.orc_get_scene_info(self.h_, a.ctypes.data)
         return dict(tris=int(a[0]), nodes=int(a[1]), emissive_meshes=int(a[2]), emissive_tris=int(a[3]))
 
+    def env_tables(self, texels):
+        """The environment's alias table and pdf, per texel (row-major, `texels` = width * height): (alias uint32, importance, pdf)."""
+        alias = np.zeros(texels, np.uint32); importance = np.zeros(texels, np.float32); pdf = np.zeros(texels, np.float32)
+        self.L.orc_get_env_tables(self.h_, alias.ctypes.data, importance.ctypes.data, pdf.ctypes.data)
+        return alias, importance, pdf
+
     def trace_rays(self, rays):
         """rays: float32 [n,8] (ox,oy,oz,tmin,dx,dy,dz,tmax) -> structured hits."""
         rays = np.ascontiguousarray(rays, np.float32)

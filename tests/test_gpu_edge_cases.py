@@ -1,7 +1,8 @@
 """Edge cases: tiny and ragged image sizes, a scene with no triangles, degenerate triangles, depth 1, very large and
 very small scene scales (the quantised BVH boxes must stay conservative), post-processing of images too small for
-a full bloom chain."""
+a full bloom chain; a rejected scene description leaves the installed scene as it was."""
 import copy
+import ctypes as C
 
 import numpy as np
 import pytest
@@ -99,3 +100,45 @@ def test_rays_from_far_outside_the_scene(vpt, oracle, scenes, far):
     for f in ("t", "u", "v", "primitive", "instance"):
         assert np.array_equal(got[f], ref[f]), (f, int((got[f] != ref[f]).sum()))
     assert (ref["t"] >= 0).mean() > 0.2
+
+
+def rejected_descriptions(vpt):
+    """(name, scene, what to do to its description, error code, message): one ordinary rejection of scene_prep.hpp's check (the whole table:
+    tests/test_scene_prep_cpu.py) and the one that used to be noticed only after the installed scene had been freed."""
+    S = vpt.scenes
+    tri = S.Scene()
+    m = tri.add_mesh([(0, 0, 0), (1, 0, 0), (0, 1, 0)], [(0, 0, 1)] * 3, None, [0, 1, 2])
+    tri.materials.append(S.material())
+    tri.add_instance(m, 0)
+    lamps = copy.deepcopy(tri)
+    lamps.materials[0]["emissive_color"] = (3.0, 3.0, 3.0)
+    lamps.instances = lamps.instances * 10001            # VPT_MAX_EMISSIVE_MESHES + 1 instances of an emissive material
+
+    def bad_index(desc):
+        idx = (C.c_uint32 * 3)(0, 1, 3)
+        desc.meshes[0].indices = C.cast(idx, C.c_void_p).value
+        return idx
+
+    return [("mesh index out of range", tri, bad_index, -1, "mesh index out of range"),
+            ("too many emissive meshes", lamps, lambda desc: None, -7, "too many emissive meshes")]
+
+
+def test_a_rejected_scene_leaves_the_installed_one_untouched(vpt, scenes):
+    sc = scenes("cornell_box")
+    frames = 3
+    g = vpt.PathTracer(64, 36); g.set_scene(sc); g.set_params(vpt.default_params(max_depth=5)); g.render(frames)
+    first = g.radiance()
+    assert first[..., :3].max() > 0
+    keys = ("total_vertex_count", "total_index_count", "bvh_nodes", "bvh_triangles", "bvh_node_bytes", "emissive_mesh_count", "emissive_triangle_count", "frames")
+    before = {k: g.stats()[k] for k in keys}
+    assert before["bvh_triangles"] == sc.triangle_count() and before["emissive_mesh_count"] >= 1 and before["frames"] == frames
+    for name, bad, mutate, code, message in rejected_descriptions(vpt):
+        desc, keep = bad.to_desc()
+        keep.append(mutate(desc))
+        assert g.lib.vpt_set_scene(g.ctx, C.byref(desc)) == code, name
+        assert g.lib.vpt_last_error(g.ctx).decode() == message, name
+        assert {k: g.stats()[k] for k in keys} == before, name          # the old scene, and the frames accumulated on it
+        assert np.array_equal(g.radiance(), first), name
+        g.reset(); g.render(frames)
+        assert np.array_equal(g.radiance(), first), name                # ... which still renders what it rendered
+    g.close()

@@ -1,0 +1,480 @@
+"""What vpt_set_scene does on the host (vulkan-path-tracer_amd/csrc/scene_prep.hpp) without a device: tests/tools/scene_prep_driver.cpp
+wraps scene::check / prepare / emissive_list and the predicates, and is driven through ctypes with the package's own _abi.SceneDesc.
+  * every rejection of scene::check, one row each, with its code and its message;
+  * the prepared tables against the oracle's own writing of them (oracle.cpp build_tris / build_env / build_emissive), bit for bit;
+  * the predicates that pick the kernels and their grids, one flipped input at a time.
+The GPU side (a rejected description leaves the installed scene as it was): tests/test_gpu_edge_cases.py."""
+import copy
+import ctypes as C
+import os
+import subprocess
+import sys
+from importlib import import_module
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import material_scenes  # noqa: E402
+
+CSRC = os.path.join(ROOT, "vulkan-path-tracer_amd", "csrc")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+abi = import_module("vulkan-path-tracer_amd._abi")
+INVALID, LIMIT = -1, -7                                   # VPT_ERR_INVALID_ARGUMENT, VPT_ERR_LIMIT
+MAX_ENTITIES, MAX_INSTANCES, MAX_EMISSIVE = 10000, 100000, 10000   # include/vpt.h
+BUILD_GENERAL_KERNELS = 2
+TEXTURE_SLOTS = ("base_color_texture", "normal_texture", "roughness_texture", "metallic_texture", "emissive_texture")
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("scene_prep") / "libscene_prep.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-ffp-contract=off", "-fno-fast-math", "-march=x86-64-v3", "-D__HIP_PLATFORM_AMD__",
+                           "-I/opt/rocm/include", "-I" + CSRC, os.path.join(ROOT, "tests", "tools", "scene_prep_driver.cpp"), "-o", out])
+    L = C.CDLL(out)
+    L.sp_check.restype = C.c_char_p
+    L.sp_check.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_int)]
+    L.sp_check_pools.restype = C.c_char_p
+    L.sp_check_pools.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
+    L.sp_material_textures_ok.argtypes = [C.POINTER(abi.Material), C.c_uint32]
+    L.sp_prepare.restype = C.c_void_p
+    L.sp_prepare.argtypes = [C.POINTER(abi.SceneDesc)]
+    L.sp_destroy.argtypes = [C.c_void_p]
+    L.sp_counts.argtypes = [C.c_void_p, C.c_void_p]
+    L.sp_get_triangles.argtypes = [C.c_void_p, C.c_void_p]
+    L.sp_get_env_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sp_get_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sp_get_instances.argtypes = [C.c_void_p, C.c_void_p]
+    L.sp_set_material.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.Material)]
+    L.sp_get_emissive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sp_depth_bounded.argtypes = [C.c_void_p, C.c_uint32]
+    L.sp_plain.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32]
+    L.sp_rides_in_lds.argtypes = [C.c_uint64, C.c_uint64]
+    L.sp_fits_lds.argtypes = [C.c_uint64]
+    L.sp_node_bytes.restype = C.c_uint32
+    L.sp_tri_bytes.restype = C.c_uint32
+    L.sp_slot_of_gid.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    return L
+
+
+def check(lib, desc):
+    code = C.c_int(12345)
+    msg = lib.sp_check(C.byref(desc), C.byref(code))
+    return code.value, msg.decode()
+
+
+class Prepared:
+    """scene::prepare of a description, read back in the oracle's layouts."""
+
+    def __init__(self, lib, desc):
+        self.L = lib
+        assert check(lib, desc) == (0, "")
+        self.h = lib.sp_prepare(C.byref(desc))
+        c = np.zeros(10, np.uint64)
+        lib.sp_counts(self.h, c.ctypes.data)
+        assert c[0] != np.uint64(0xFFFFFFFFFFFFFFFF), "the pools do not hold what the totals say"
+        (self.kept, self.total_tris, self.total_vertices, self.total_indices, self.env_texels, self.n_inst, self.n_tex, self.texel_bytes,
+         self.env_black, self.n_mat) = (int(v) for v in c)
+
+    def close(self):
+        self.L.sp_destroy(self.h)
+
+    def triangles(self):
+        out = np.zeros((self.kept, 12), np.float32)
+        self.L.sp_get_triangles(self.h, out.ctypes.data)
+        return out
+
+    def env_tables(self):
+        alias = np.zeros(self.env_texels, np.uint32); importance = np.zeros(self.env_texels, np.float32); pdf = np.zeros(self.env_texels, np.float32)
+        self.L.sp_get_env_tables(self.h, alias.ctypes.data, importance.ctypes.data, pdf.ctypes.data)
+        return alias, importance, pdf
+
+    def textures(self):
+        d = np.zeros((self.n_tex, 5), np.uint32); t = np.zeros(max(self.texel_bytes, 1), np.uint8)
+        self.L.sp_get_textures(self.h, d.ctypes.data, t.ctypes.data)
+        return d, t[:self.texel_bytes]
+
+    def instances(self):
+        out = np.zeros((self.n_inst, 28), np.uint32)
+        self.L.sp_get_instances(self.h, out.ctypes.data)
+        return out
+
+    def emissive(self):
+        n = np.zeros(2, np.uint32)
+        self.L.sp_get_emissive(self.h, n.ctypes.data, None)
+        assert n[0] != 0xFFFFFFFF, "one triangle offset per entry (one zero for an empty list)"
+        e = np.zeros((int(n[0]), 5), np.uint32)
+        self.L.sp_get_emissive(self.h, n.ctypes.data, e.ctypes.data)
+        return int(n[0]), int(n[1]), e
+
+
+# ------------------------------------------------------------------ rejections
+def tiny_scene(vpt, instances=1, emissive=False):
+    """One triangle, one material, `instances` instances of it."""
+    S = vpt.scenes
+    sc = S.Scene()
+    m = sc.add_mesh([(0, 0, 0), (1, 0, 0), (0, 1, 0)], [(0, 0, 1)] * 3, None, [0, 1, 2])
+    sc.materials.append(S.material(emissive_color=(2.0, 0.0, 0.0) if emissive else (0, 0, 0)))
+    for _ in range(instances):
+        sc.add_instance(m, 0)
+    return sc
+
+
+def repeated(array, n):
+    """A ctypes array of n copies of array[0]."""
+    out = (type(array[0]) * n)()
+    for i in range(n):
+        out[i] = array[0]
+    return out
+
+
+def null(field):
+    def f(d, keep):
+        setattr(d, field, None)
+    return f
+
+
+def zero(field):
+    def f(d, keep):
+        setattr(d, field, 0)
+    return f
+
+
+def count_at_limit(array_field, count_field, n):
+    def f(d, keep):
+        a = repeated(getattr(d, array_field), n); keep.append(a)
+        setattr(d, array_field, a); setattr(d, count_field, n)
+    return f
+
+
+def mesh_with(**kw):
+    def f(d, keep):
+        idx = (C.c_uint32 * 6)(0, 1, 2, 0, 1, 2); keep.append(idx)
+        if "indices" not in kw:
+            d.meshes[0].indices = C.cast(idx, C.c_void_p).value
+        for k, v in kw.items():
+            if k == "index_values":
+                for i, x in enumerate(v):
+                    idx[i] = x
+            else:
+                setattr(d.meshes[0], k, v)
+    return f
+
+
+def material_with(slot):
+    def f(d, keep):
+        setattr(d.materials[0], slot, d.texture_count)
+    return f
+
+
+def instance_with(field, count_field):
+    def f(d, keep):
+        setattr(d.instances[0], field, getattr(d, count_field))
+    return f
+
+
+def texture_with(**kw):
+    def f(d, keep):
+        for k, v in kw.items():
+            setattr(d.textures[2], k, v)
+    return f
+
+
+INCOMPLETE = "incomplete scene description"
+REJECTIONS = [
+    ("no meshes: count", zero("mesh_count"), INVALID, "No meshes found in scene"),
+    ("no meshes: pointer", null("meshes"), INVALID, "No meshes found in scene"),
+    ("mesh count at the limit", count_at_limit("meshes", "mesh_count", MAX_ENTITIES), LIMIT, "too many meshes/materials"),
+    ("material count at the limit", count_at_limit("materials", "material_count", MAX_ENTITIES), LIMIT, "too many meshes/materials"),
+    ("instance count at the limit", count_at_limit("instances", "instance_count", MAX_INSTANCES), LIMIT, "too many mesh instances"),
+    ("no materials: pointer", null("materials"), INVALID, INCOMPLETE),
+    ("no materials: count", zero("material_count"), INVALID, INCOMPLETE),
+    ("no instances: pointer", null("instances"), INVALID, INCOMPLETE),
+    ("no textures: pointer", null("textures"), INVALID, INCOMPLETE),
+    ("no textures: count", zero("texture_count"), INVALID, INCOMPLETE),
+    ("no environment: pointer", null("env_rgba"), INVALID, INCOMPLETE),
+    ("no environment: width", zero("env_width"), INVALID, INCOMPLETE),
+    ("no environment: height", zero("env_height"), INVALID, INCOMPLETE),
+    ("no reflection table", null("lut_reflection"), INVALID, INCOMPLETE),
+    ("no refraction-outside table", null("lut_refraction_outside"), INVALID, INCOMPLETE),
+    ("no refraction-inside table", null("lut_refraction_inside"), INVALID, INCOMPLETE),
+    ("bad mesh: no vertices", mesh_with(vertices=None), INVALID, "bad mesh"),
+    ("bad mesh: no indices", mesh_with(indices=None), INVALID, "bad mesh"),
+    ("bad mesh: index count 4", mesh_with(index_count=4), INVALID, "bad mesh"),
+    ("bad mesh: index count 5", mesh_with(index_count=5), INVALID, "bad mesh"),
+    ("mesh index out of range", mesh_with(index_values=(0, 1, 3)), INVALID, "mesh index out of range"),
+    ("mesh index out of range in a later triangle", mesh_with(index_count=6, index_values=(0, 1, 2, 0, 0xFFFFFFFF, 2)), INVALID, "mesh index out of range"),
+] + [
+    ("material %s out of range" % slot, material_with(slot), INVALID, "material texture index out of range") for slot in TEXTURE_SLOTS
+] + [
+    ("instance mesh index out of range", instance_with("mesh_index", "mesh_count"), INVALID, "instance mesh index out of range"),
+    ("instance material index out of range", instance_with("material_index", "material_count"), INVALID, "Mesh instance has invalid material index"),
+    ("bad texture: no data", texture_with(data=None), INVALID, "bad texture"),
+    ("bad texture: width 0", texture_with(width=0), INVALID, "bad texture"),
+    ("bad texture: height 0", texture_with(height=0), INVALID, "bad texture"),
+] + [("bad texture: %d channels" % ch, texture_with(channels=ch), INVALID, "bad texture") for ch in (0, 2, 3, 5)]
+
+
+@pytest.mark.parametrize("name,mutate,code,message", REJECTIONS, ids=[r[0] for r in REJECTIONS])
+def test_check_rejects_with_its_code_and_message(lib, vpt, name, mutate, code, message):
+    desc, keep = tiny_scene(vpt).to_desc()
+    assert check(lib, desc) == (0, "")
+    mutate(desc, keep)
+    assert check(lib, desc) == (code, message)
+
+
+def test_check_accepts_counts_just_below_the_limits(lib, vpt):
+    for array_field, count_field, n in (("meshes", "mesh_count", MAX_ENTITIES - 1), ("materials", "material_count", MAX_ENTITIES - 1), ("instances", "instance_count", MAX_INSTANCES - 1)):
+        desc, keep = tiny_scene(vpt).to_desc()
+        count_at_limit(array_field, count_field, n)(desc, keep)
+        assert check(lib, desc) == (0, ""), count_field
+
+
+def test_check_bounds_the_emissive_list(lib, vpt):
+    """One entry per instance of an emissive material, whatever the mesh: VPT_MAX_EMISSIVE_MESHES passes, one more does not."""
+    desc, keep = tiny_scene(vpt, MAX_EMISSIVE, emissive=True).to_desc()
+    assert check(lib, desc) == (0, "")
+    p = Prepared(lib, desc)
+    assert p.emissive()[:2] == (MAX_EMISSIVE, MAX_EMISSIVE)
+    p.close()
+    desc, keep = tiny_scene(vpt, MAX_EMISSIVE + 1, emissive=True).to_desc()
+    assert check(lib, desc) == (LIMIT, "too many emissive meshes")
+    for ch in range(3):     # any one channel makes a material emissive; none leaves the instances out of the list
+        for k in range(3):
+            desc.materials[0].emissive_color[k] = 0.5 if k == ch else 0.0
+        assert check(lib, desc) == (LIMIT, "too many emissive meshes")
+    desc.materials[0].emissive_color[2] = 0.0
+    assert check(lib, desc) == (0, "")
+
+
+def check_pools(lib, meshes, textures):
+    v = np.ascontiguousarray([m[0] for m in meshes], np.uint32); i = np.ascontiguousarray([m[1] for m in meshes], np.uint32)
+    t = np.ascontiguousarray(textures, np.uint32).reshape(-1, 3)
+    code = C.c_int(12345)
+    msg = lib.sp_check_pools(v.ctypes.data, i.ctypes.data, len(meshes), t.ctypes.data, len(t), C.byref(code))
+    return code.value, msg.decode()
+
+
+def test_check_bounds_the_pools_by_their_32_bit_offsets(lib):
+    """The sums scene::check forms over meshes and textures, from counts alone (buffers of these sizes are no test's to allocate)."""
+    top = 0xFFFFFFFF
+    geometry = (LIMIT, "more than 2^32 pooled vertices / indices")
+    texels = (LIMIT, "texel pool over 4 GiB (TexDesc offsets are 32-bit)")
+    assert check_pools(lib, [(top, 3)], [(1, 1, 4)]) == (0, "")
+    assert check_pools(lib, [(top - 5, 3), (5, top - 3)], [(1, 1, 4)]) == (0, "")
+    assert check_pools(lib, [(top, 3), (1, 3)], [(1, 1, 4)]) == geometry
+    assert check_pools(lib, [(3, top - 2), (3, 3)], [(1, 1, 4)]) == geometry
+    assert check_pools(lib, [(top, top)] * 9999, [(1, 1, 4)]) == geometry          # (the sums are 64-bit: no wrap-around back into range)
+    # texels: width * height * channels + 3 bytes of alignment per texture, against 2^32 - 1
+    assert check_pools(lib, [(3, 3)], [(65536, 65535, 1), (65536 - 7, 1, 1)]) == (0, "")          # (2^32 - 65536 + 3) + (65529 + 3) = 2^32 - 1
+    assert check_pools(lib, [(3, 3)], [(65536, 65535, 1), (65536 - 6, 1, 1)]) == texels           # ... = 2^32
+    assert check_pools(lib, [(3, 3)], [(32768, 32768, 4)]) == texels
+    assert check_pools(lib, [(3, 3)], [(32768, 32767, 4), (32768, 1, 1)] + [(1, 1, 4)] * 5) == (0, "")
+    assert check_pools(lib, [(top, 3), (1, 3)], [(32768, 32768, 4)]) == geometry        # the order vpt_set_scene reports them in
+
+
+def test_material_textures_ok_is_the_bound_of_all_five_slots(lib, vpt):
+    desc, keep = tiny_scene(vpt).to_desc()
+    m = desc.materials[0]
+    assert lib.sp_material_textures_ok(C.byref(m), 5) == 1
+    assert lib.sp_material_textures_ok(C.byref(m), 4) == 0       # the default emissive texture is index 4
+    for slot in TEXTURE_SLOTS:
+        mm = abi.Material.from_buffer_copy(m)
+        setattr(mm, slot, 7)
+        assert lib.sp_material_textures_ok(C.byref(mm), 7) == 0 and lib.sp_material_textures_ok(C.byref(mm), 8) == 1
+
+
+# ------------------------------------------------------------------ the prepared tables against the oracle's
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def load_scene(vpt, name):
+    S = vpt.scenes
+    if name in ("cornell_box", "cornell_box_glass", "viking_room"):
+        return copy.deepcopy(S.Scene.load(os.path.join(GOLDEN, name + ".npz")))
+    if name == "textured_boxes":
+        return S.load_gltf(os.path.join(GOLDEN, "textured_boxes.gltf"))
+    if name == "atrium":                                        # the variant whose generator emits exact slivers (tests/test_bvh_host.py), small textures
+        return S.atrium(detail=1.0, env_size=(64, 32), tex_size=32)
+    return material_scenes.variant(name)[0]                     # non-identity, sheared and mirrored instance transforms
+
+
+SCENES = ["cornell_box", "cornell_box_glass", "viking_room", "textured_boxes", "atrium", "affine_instances", "combined"]
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_prepare_equals_the_oracle_bit_for_bit(lib, vpt, oracle, name):
+    sc = load_scene(vpt, name)
+    desc, keep = sc.to_desc()
+    p = Prepared(lib, desc)
+    o = oracle.Oracle(sc, 8, 8)
+    try:
+        # ---- triangles: the oracle keeps every triangle and marks slivers; the library drops them
+        ot = o.triangles()
+        sliver = oracle.leaf_eval("triangle_degenerate", ot[:, 3:9])[:, 0] != 0
+        lt = p.triangles()
+        assert p.total_tris == len(ot) == sc.triangle_count() and p.kept == len(ot) - int(sliver.sum())
+        if name == "atrium":
+            assert sliver.sum() > 0
+        if name in ("affine_instances", "combined"):
+            assert any(not np.array_equal(x[:3, :3], np.eye(3, dtype=np.float32)) for _, _, x in sc.instances)
+        kept_o, kept_l = bits(ot[~sliver]), bits(lt)
+        for what, cols in (("v0", slice(0, 3)), ("e1", slice(3, 6)), ("e2", slice(6, 9)), ("prim", 9), ("inst", 10), ("gid", 11)):
+            assert np.array_equal(kept_l[:, cols], kept_o[:, cols]), what
+        dropped = np.setdiff1d(np.arange(len(ot), dtype=np.uint32), kept_l[:, 11])
+        assert np.array_equal(dropped, bits(ot)[sliver, 11])
+        # ---- environment
+        w, h = sc.env.shape[1], sc.env.shape[0]
+        assert p.env_texels == w * h and p.env_black == int(not np.any(np.asarray(sc.env, np.float32)[..., :3] != 0) and not np.any(np.asarray(sc.env, np.float32)[..., 3] != 0))
+        for a, b, what in zip(p.env_tables(), o.env_tables(w * h), ("alias", "importance", "pdf")):
+            assert np.array_equal(bits(a), bits(b)), what
+        # ---- emissive list
+        info = o.scene_info()
+        n, tris, entries = p.emissive()
+        assert (n, tris) == (info["emissive_meshes"], info["emissive_tris"])
+        assert np.array_equal(entries[:, 4], np.concatenate([[0], np.cumsum(entries[:, 2])[:-1]]).astype(np.uint32) if n else np.zeros(0, np.uint32))
+        # ---- pools, instances, texel pool: against the description itself
+        assert p.total_vertices == sum(len(v) for v, _ in sc.meshes) and p.total_indices == sum(len(i) for _, i in sc.meshes)
+        inst = p.instances()
+        first = np.concatenate([[0], np.cumsum([len(sc.meshes[m][1]) // 3 for m, _, _ in sc.instances])[:-1]])
+        assert np.array_equal(inst[:, 0], [m for m, _, _ in sc.instances]) and np.array_equal(inst[:, 1], [m for _, m, _ in sc.instances]) and np.array_equal(inst[:, 2], first)
+        assert np.array_equal(inst[:, 3:19], bits(np.array([np.asarray(x, np.float32).T.reshape(-1) for _, _, x in sc.instances], np.float32)))
+        td, pool = p.textures()
+        for t, tex in enumerate(sc.textures):
+            off, tw, th, tc, one = (int(v) for v in td[t])
+            assert off % 4 == 0 and (tw, th, tc) == (tex.shape[1], tex.shape[0], tex.shape[2]) and one == int(tex.shape[:2] == (1, 1))
+            assert np.array_equal(pool[off:off + tw * th * tc], np.ascontiguousarray(tex, np.uint8).reshape(-1))
+    finally:
+        o.close(); p.close()
+
+
+def env_cases(vpt):
+    S = vpt.scenes
+    rng = np.random.RandomState(9)
+    hdr = np.zeros((16, 32, 4), np.float32); hdr[..., :3] = rng.gamma(0.6, 0.8, (16, 32, 3)); hdr[5, 7, :3] = (4.0e4, 3.0e4, 2.0e4)
+    cases = {"black_1x1": np.zeros((1, 1, 4), np.float32), "black": np.zeros((8, 16, 4), np.float32),          # every texel low: the partition's slot [size] is written
+             "uniform": S.constant_env(), "uniform_1x1": S.constant_env(w=1, h=1), "uniform_grey": S.constant_env((0.3, 0.3, 0.3), 16, 8),
+             "sun_sky": S.sun_sky_env(128, 64), "hdr": hdr, "one_texel_lit": np.zeros((4, 8, 4), np.float32)}
+    cases["one_texel_lit"][2, 3, :3] = (0.0, 7.0, 0.0)
+    for w in (2, 3, 5, 7, 10, 33):                                                                                # one row: every texel has the same importance, just below, at or above the mean
+        cases["uniform_row_%d" % w] = S.constant_env((0.7, 0.2, 0.1), w, 1)
+    return cases
+
+
+def test_environment_tables_equal_the_oracle_bit_for_bit(lib, vpt, oracle):
+    for name, env in env_cases(vpt).items():
+        sc = tiny_scene(vpt)
+        sc.env = env
+        desc, keep = sc.to_desc()
+        p = Prepared(lib, desc)
+        o = oracle.Oracle(sc, 8, 8)
+        n = env.shape[0] * env.shape[1]
+        for a, b, what in zip(p.env_tables(), o.env_tables(n), ("alias", "importance", "pdf")):
+            assert np.array_equal(bits(a), bits(b)), (name, what)
+        assert p.env_black == int(name.startswith("black")), name
+        if name.startswith("black"):
+            assert not p.env_tables()[1].any() and not p.env_tables()[2].any()
+        o.close(); p.close()
+
+
+@pytest.mark.parametrize("name", ["cornell_box_glass", "emissive_texture"])
+def test_emissive_list_follows_material_changes_like_the_oracle(lib, vpt, oracle, name):
+    sc = load_scene(vpt, name)
+    desc, keep = sc.to_desc()
+    p = Prepared(lib, desc)
+    o = oracle.Oracle(sc, 8, 8)
+
+    def same():
+        info = o.scene_info()
+        n, tris, entries = p.emissive()
+        assert (n, tris) == (info["emissive_meshes"], info["emissive_tris"])
+        want = [i for i, (_, m, _) in enumerate(sc.instances) if any(c != 0 for c in mats[m].emissive_color)]      # instance order
+        assert entries[:, 3].tolist() == want and entries[:, 0].tolist() == [sc.instances[i][0] for i in want] and entries[:, 1].tolist() == [sc.instances[i][1] for i in want]
+        assert entries[:, 2].tolist() == [len(sc.meshes[sc.instances[i][0]][1]) // 3 for i in want]
+        return n, tris
+
+    mats = [abi.Material.from_buffer_copy(desc.materials[i]) for i in range(desc.material_count)]
+    before = same()
+    assert before[0] >= 1
+    lit = [i for i, m in enumerate(mats) if any(c != 0 for c in m.emissive_color)]
+    dark = [i for i, m in enumerate(mats) if not any(c != 0 for c in m.emissive_color) and any(mi == i for _, mi, _ in sc.instances)]
+    steps = [(dark[0], (0.0, 0.0, 3.0)), (dark[-1], (1.0, 0.0, 0.0)), (lit[0], (0.0, 0.0, 0.0)), (dark[0], (0.0, 0.0, 0.0)), (dark[-1], (0.0, 0.0, 0.0)), (lit[0], tuple(mats[lit[0]].emissive_color))]
+    seen = [before]
+    for idx, colour in steps:
+        mats[idx].emissive_color[:] = colour
+        o.set_material(idx, mats[idx]); p.L.sp_set_material(p.h, idx, C.byref(mats[idx]))
+        seen.append(same())
+    assert seen[-1] == before and seen[1][0] == before[0] + sum(1 for _, mi, _ in sc.instances if mi == dark[0]) and seen[3][0] < seen[2][0]
+    o.close(); p.close()
+
+
+# ------------------------------------------------------------------ predicates
+def material_array(vpt, n=3, **kw):
+    S = vpt.scenes
+    sc = S.Scene()
+    sc.add_mesh([(0, 0, 0), (1, 0, 0), (0, 1, 0)], [(0, 0, 1)] * 3, None, [0, 1, 2])
+    for _ in range(n):
+        sc.materials.append(S.material())
+        sc.add_instance(0, len(sc.materials) - 1)
+    desc, keep = sc.to_desc()
+    return desc, keep
+
+
+def test_plain_flips_with_each_of_its_inputs(lib, vpt):
+    desc, keep = material_array(vpt)
+    one = np.array([1, 1, 1, 1, 1, 0, 1], np.uint8)      # textures 0..4: the 1x1 defaults; 5: a real texture; 6: another 1x1
+
+    def plain(env_black=1, flags=0, tex=one):
+        return lib.sp_plain(C.cast(desc.materials, C.c_void_p), desc.material_count, tex.ctypes.data, len(tex), env_black, flags)
+
+    assert plain() == 1
+    assert plain(env_black=0) == 0
+    assert plain(flags=BUILD_GENERAL_KERNELS) == 0
+    assert plain(flags=1 | 4) == 1                                 # (the other build flags do not matter)
+    for k in range(desc.material_count):
+        for slot in TEXTURE_SLOTS:
+            keep_index = getattr(desc.materials[k], slot)
+            setattr(desc.materials[k], slot, 5)
+            assert plain() == 0, (k, slot)
+            setattr(desc.materials[k], slot, 6)
+            assert plain() == 1, (k, slot)
+            setattr(desc.materials[k], slot, 7)                    # (no such texture: not 1x1)
+            assert plain() == 0, (k, slot)
+            setattr(desc.materials[k], slot, keep_index)
+    assert plain() == 1
+    assert plain(tex=np.array([1, 1, 1, 0, 1, 0, 1], np.uint8)) == 0
+
+
+def test_depth_bounded_needs_transmission_density_and_anisotropy_together(lib, vpt):
+    desc, keep = material_array(vpt)
+
+    def bounded():
+        return lib.sp_depth_bounded(C.cast(desc.materials, C.c_void_p), desc.material_count)
+
+    assert bounded() == 1
+    for k in range(desc.material_count):
+        m = desc.materials[k]
+        for t, d, a, want in ((0.5, 0.3, 0.2, 0), (0.0, 0.3, 0.2, 1), (0.5, 0.0, 0.2, 1), (0.5, 0.3, 1.0, 1), (1.0, -0.1, 0.0, 0), (-0.5, 0.3, 0.2, 1), (0.5, 0.3, -1.0, 0)):
+            m.transmission, m.medium_density, m.medium_anisotropy = t, d, a
+            assert bounded() == want, (k, t, d, a)
+        m.transmission, m.medium_density, m.medium_anisotropy = 0.0, 0.0, 0.0
+    assert bounded() == 1
+
+
+def test_rides_in_lds_up_to_3072_bytes(lib):
+    node, tri = lib.sp_node_bytes(), lib.sp_tri_bytes()
+    assert (node, tri) == (128, 48)
+    assert lib.sp_fits_lds(3072) == 1 and lib.sp_fits_lds(3073) == 0 and lib.sp_fits_lds(0) == 1
+    assert lib.sp_rides_in_lds(0, 64) == 1 and lib.sp_rides_in_lds(24, 0) == 1 and lib.sp_rides_in_lds(6, 48) == 1      # 3072 bytes each
+    assert lib.sp_rides_in_lds(0, 65) == 0 and lib.sp_rides_in_lds(25, 0) == 0 and lib.sp_rides_in_lds(6, 49) == 0      # 3120, 3200, 3120
+    assert 7 * node + 46 * tri == 3104 and lib.sp_rides_in_lds(7, 46) == 0 and 15 * node + 24 * tri == 3072 and lib.sp_rides_in_lds(15, 24) == 1
+    assert lib.sp_rides_in_lds(0, 0) == 1
+
+
+def test_slot_of_gid_inverts_the_leaf_order(lib):
+    gids = np.array([4, 0, 5, 2], np.uint32)          # gids 1 and 3 were slivers
+    out = np.zeros(7, np.uint32)
+    lib.sp_slot_of_gid(gids.ctypes.data, len(gids), 7, out.ctypes.data)
+    assert out.tolist() == [1, 0xFFFFFFFF, 3, 0xFFFFFFFF, 0, 2, 0xFFFFFFFF]

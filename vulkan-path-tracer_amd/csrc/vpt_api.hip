@@ -1,5 +1,5 @@
-// vpt_api.hip — implementation of the C-ABI in include/vpt.h: context, scene preparation (host
-// arithmetic of PathTracer.cpp restated), the wavefront render loop, sharding, post-process schedule.
+// vpt_api.hip — implementation of the C-ABI in include/vpt.h: context, scene installation (what scene_prep.hpp
+// prepares on the host, uploaded), the wavefront render loop, sharding, post-process schedule.
 // There is no CPU fallback in this file: without a HIP device vpt_create() fails.
 #include <algorithm>
 #include <chrono>
@@ -16,6 +16,7 @@
 #include "bvh_build.hpp"
 #include "kernels.hpp"
 #include "path_plan.hpp"
+#include "scene_prep.hpp"
 
 using namespace vpt;
 using plan::Kind;
@@ -108,22 +109,25 @@ struct vpt_ctx {
     std::vector<vpt_material> materials;
     std::vector<MeshDesc> meshes;
     std::vector<InstanceDesc> instances;
-    std::vector<EmissiveDesc> emissive;
-    uint32_t emissive_tris = 0;
+    scene::EmissiveList emissive;
     uint64_t total_vertices = 0, total_indices = 0;
     uint32_t bvh_depth = 0;
 
     DeviceScene dsc{};
     std::vector<void*> scene_allocs;
-    vpt_material* d_materials = nullptr;
-    EmissiveDesc* d_emissive = nullptr;
-    MatResolved* d_mat_resolved = nullptr;
-    EmissiveTri* d_emissive_tri = nullptr;
-    uint32_t* d_emissive_tri_offset = nullptr;
-    float4* d_tri_ng = nullptr;
-    float4* d_tri_shade = nullptr;
-    unsigned char* d_inst_class = nullptr;   // shade class per instance (kernels_path.hip k_classify_instances)
-    std::vector<BvhTri> bvh_input;           // the triangles the BVH was built from (trace lab: the eight-wide tree is built from them on first use)
+    // The scene tables the host patches or the precompute kernels fill after the upload: the writable pointer to each (DeviceScene's are
+    // const), set together with DeviceScene's by alloc_table and nowhere else.
+    struct Writable {
+        vpt_material* materials = nullptr;
+        EmissiveDesc* emissive = nullptr;
+        MatResolved* mat_resolved = nullptr;
+        EmissiveTri* emissive_tri = nullptr;
+        uint32_t* emissive_tri_offset = nullptr;
+        float4* tri_ng = nullptr;
+        float4* tri_shade = nullptr;
+        unsigned char* inst_class = nullptr;   // shade class per instance (kernels_path.hip k_classify_instances)
+    } dw;
+    std::vector<BvhTri> bvh_input;          // the triangles the BVH was built from (trace lab: the eight-wide tree is built from them on first use)
     bool lds_scene = false;
     bool scene_plain = false;    // every material's five textures are 1x1 and the environment is black: the fused kernel's PLAIN instantiation serves it
     std::vector<unsigned char> tex_1x1;   // per texture of the scene
@@ -246,16 +250,32 @@ hipError_t memset_now(hipStream_t s, void* p, int v, size_t n) {
     return e == hipSuccess ? hipStreamSynchronize(s) : e;
 }
 
+// A scene table of n (at least one) elements, freed with the scene: DeviceScene's pointer to it and, for a table that is written after the
+// upload, the writable one (vpt_ctx::Writable) are set here, from one allocation sized by their own element type.
 template <class T>
-int upload(vpt_ctx* c, const std::vector<T>& v, const T** out, size_t min_elems = 1) {
-    size_t n = std::max(v.size(), min_elems);
-    void* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, n * sizeof(T)));
+int alloc_table(vpt_ctx* c, size_t n, const T** out, T** writable = nullptr) {
+    T* d = nullptr;
+    HIPCHK(c, hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(T)));
     c->scene_allocs.push_back(d);
-    HIPCHK(c, memset_now(c->main.stream, d, 0, n * sizeof(T)));
-    if (!v.empty()) HIPCHK(c, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = (const T*)d;
+    *out = d;
+    if (writable) *writable = d;
     return VPT_OK;
+}
+// ... holding the n elements at src, zeros behind them up to min_elems.
+template <class T>
+int upload(vpt_ctx* c, const T* src, size_t n, const T** out, size_t min_elems = 1, T** writable = nullptr) {
+    const size_t elems = std::max(n, min_elems);
+    T* local = nullptr;
+    T** d = writable ? writable : &local;
+    int rc = alloc_table(c, elems, out, d);
+    if (rc) return rc;
+    HIPCHK(c, memset_now(c->main.stream, *d, 0, elems * sizeof(T)));
+    if (n) HIPCHK(c, hipMemcpy(*d, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return VPT_OK;
+}
+template <class T>
+int upload(vpt_ctx* c, const std::vector<T>& v, const T** out, size_t min_elems = 1, T** writable = nullptr) {
+    return upload(c, v.data(), v.size(), out, min_elems, writable);
 }
 
 void free_spill(Lane& L) {
@@ -267,7 +287,7 @@ void free_scene(vpt_ctx* c) {
     c->scene_allocs.clear();
     free_spill(c->main);   // (sized by the scene's grids)
     c->has_scene = false;
-    c->d_materials = nullptr; c->d_emissive = nullptr;
+    c->dw = vpt_ctx::Writable{};
 }
 void free_lab(vpt_ctx* c) {
     for (void* p : {(void*)c->lab_ro, (void*)c->lab_rd, (void*)c->lab_hit, (void*)c->lab_hinst, (void*)c->lab_order}) if (p) (void)hipFree(p);
@@ -549,93 +569,29 @@ void sync_params(vpt_ctx* c) {
 
 void reset_accum(vpt_ctx* c) { c->frame_count = 0; c->dispatch_count = 0; c->samples_accum = 0; }  // PathTracer.h:183
 
-// Emissive-mesh list, PathTracer.cpp:449-469 (and SetMaterial's rebuild, 712-794: same resulting order
-// only for additions at the end; we rebuild from instance order, which is what SetScene produces).
-void build_emissive(vpt_ctx* c) {
-    c->emissive.clear(); c->emissive_tris = 0;
-    for (uint32_t i = 0; i < c->instances.size(); i++) {
-        const vpt_material& m = c->materials[c->instances[i].material];
-        if (m.emissive_color[0] != 0.0f || m.emissive_color[1] != 0.0f || m.emissive_color[2] != 0.0f) {
-            EmissiveDesc e;
-            e.mesh = c->instances[i].mesh; e.material = c->instances[i].material;
-            e.tri_count = c->meshes[e.mesh].tri_count; e.instance = i;
-            memcpy(e.xform, c->instances[i].xform, 64);
-            c->emissive.push_back(e); c->emissive_tris += e.tri_count;
-        }
-    }
-}
+// The emissive-mesh list of the scene's current materials (scene_prep.hpp emissive_list) ...
+void build_emissive(vpt_ctx* c) { c->emissive = scene::emissive_list(c->meshes, c->instances, c->materials); }
+// ... and its tables on the device.
 int upload_emissive(vpt_ctx* c) {
-    if (c->emissive.size() > VPT_MAX_EMISSIVE_MESHES) return fail(c, VPT_ERR_LIMIT, "too many emissive meshes");
-    if (!c->emissive.empty())
-        HIPCHK(c, hipMemcpy(c->d_emissive, c->emissive.data(), c->emissive.size() * sizeof(EmissiveDesc), hipMemcpyHostToDevice));
-    c->dsc.emissive_count = (uint32_t)c->emissive.size();
-    c->dsc.emissive_tris = c->emissive_tris;
+    const scene::EmissiveList& em = c->emissive;
+    // (vpt_set_scene never gets here with such a list: scene::check refuses the description; this guards vpt_set_material's rebuild)
+    if (em.list.size() > VPT_MAX_EMISSIVE_MESHES) return fail(c, VPT_ERR_LIMIT, "too many emissive meshes");
+    if (!em.list.empty())
+        HIPCHK(c, hipMemcpy(c->dw.emissive, em.list.data(), em.list.size() * sizeof(EmissiveDesc), hipMemcpyHostToDevice));
+    c->dsc.emissive_count = (uint32_t)em.list.size();
+    c->dsc.emissive_tris = em.tris;
     // per-light-triangle table (world-space corners, normal, area)
-    std::vector<uint32_t> off(std::max<size_t>(1, c->emissive.size()), 0u);
-    uint32_t total = 0;
-    for (size_t k = 0; k < c->emissive.size(); k++) { off[k] = total; total += c->emissive[k].tri_count; }
-    HIPCHK(c, hipMemcpy(c->d_emissive_tri_offset, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    launch_precompute_emissive(c->main.stream, c->dsc, c->d_emissive_tri, total);
+    HIPCHK(c, hipMemcpy(c->dw.emissive_tri_offset, em.tri_offset.data(), em.tri_offset.size() * 4, hipMemcpyHostToDevice));
+    launch_precompute_emissive(c->main.stream, c->dsc, c->dw.emissive_tri, em.tris);
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return VPT_OK;
 }
 
-// LoadEnvironmentMap, PathTracer.cpp:1161-1296: per-texel importance = solid angle * max(rgb), alias
-// table (Vose-style pairing with the reference's pre-increment partition quirk), pdf into alpha.
-void build_env_tables(const float* rgba, uint32_t w, uint32_t h, std::vector<float>& env, std::vector<AliasEntry>& alias) {
-    const uint64_t size = (uint64_t)w * h;
-    env.assign(rgba, rgba + size * 4);
-    std::vector<float> importance(size);
-    float cos_prev = 1.0f;
-    const float step_phi = 2.0f * 3.14159265358979323846f / (float)w;
-    const float step_theta = 3.14159265358979323846f / (float)h;
-    for (uint32_t y = 0; y < h; y++) {
-        float cos_next = vptfp::cos_((float)(y + 1) * step_theta);
-        float area = (cos_prev - cos_next) * step_phi;
-        cos_prev = cos_next;
-        const float* row = &env[(size_t)y * w * 4];
-        for (uint32_t x = 0; x < w; x++) importance[(size_t)y * w + x] = area * std::max(row[x * 4], std::max(row[x * 4 + 1], row[x * 4 + 2]));
-    }
-    float sum = 0.0f;
-    for (uint64_t i = 0; i < size; i++) sum = sum + importance[i];  // std::accumulate in fp32, in order
-    const float average = sum / (float)size;
-    alias.resize(size);
-    for (uint64_t i = 0; i < size; i++) { alias[i].importance = (average == 0.0f) ? 0.0f : importance[i] / average; alias[i].alias = (uint32_t)i; }
-    std::vector<uint32_t> table(size + 1, 0u);
-    uint32_t lo = 0, hi = (uint32_t)size;
-    for (uint32_t i = 0; i < size; i++) {
-        if (alias[i].importance < 1.0f) table[++lo] = i;  // upstream pre-increments: slot 0 stays 0
-        else table[--hi] = i;
-    }
-    for (lo = 0; lo < hi && hi < size; lo++) {
-        const uint32_t l = table[lo], g = table[hi];
-        alias[l].alias = g;
-        alias[g].importance -= 1.0f - alias[l].importance;
-        if (alias[g].importance < 1.0f) hi++;
-    }
-    for (uint64_t i = 0; i < size; i++) {
-        float m = std::max(env[i * 4], std::max(env[i * 4 + 1], env[i * 4 + 2]));
-        env[i * 4 + 3] = (sum == 0.0f) ? 0.0f : m / sum;
-    }
-}
-
-// Does every path end within max_depth * samples_per_frame bounces?  A bounce either raises payload.Depth or ends the path — except a
-// scattering event INSIDE a medium (ClosestHit.slang:80-116: depth unchanged), which needs a transmissive material whose medium has a
-// density and an anisotropy other than 1 (shade_core.hpp); media (volumes / atmosphere) raise the depth per event but their batches
-// run stages with host-visible fallbacks, so they count as unbounded too.
+// The grid of the fused kernel's instantiation that serves the scene's current materials (scene_prep.hpp depth_bounded / plain).
 void update_depth_bounded(vpt_ctx* c) {
-    bool bounded = true;
-    for (const vpt_material& m : c->materials)
-        if (m.transmission > 0.0f && m.medium_density != 0.0f && m.medium_anisotropy != 1.0f) bounded = false;
-    c->depth_bounded = bounded;
-    // the scene class the fused kernel is specialised for (kernels_path.hip k_bounce<PLAIN>): what k_precompute_materials turns into
-    // MatResolved.flags == 63 for every material, and k_precompute_lights into uniform light samplers
-    bool plain = c->dsc.env_black != 0u && !(c->cfg.build_flags & VPT_BUILD_GENERAL_KERNELS);
-    auto one = [&](uint32_t t) { return t < c->tex_1x1.size() && c->tex_1x1[t] != 0; };
-    for (const vpt_material& m : c->materials)
-        if (!(one(m.base_color_texture) && one(m.normal_texture) && one(m.roughness_texture) && one(m.metallic_texture) && one(m.emissive_texture))) plain = false;
-    c->scene_plain = plain;
-    c->primary_blocks = (plain && c->lds_scene) ? c->primary_blocks_plain : c->primary_blocks_general;
+    c->depth_bounded = scene::depth_bounded(c->materials);
+    c->scene_plain = scene::plain(c->materials, c->tex_1x1, c->dsc.env_black != 0u, c->cfg.build_flags);
+    c->primary_blocks = (c->scene_plain && c->lds_scene) ? c->primary_blocks_plain : c->primary_blocks_general;
 }
 
 constexpr int kSpillPatternByte = 0x7f;
@@ -650,10 +606,18 @@ __global__ __launch_bounds__(256) void k_count_spilled(const uint32_t* p, uint32
 // Which shade classes occur in the scene: the staged pipeline launches the shade stage once per class that does.
 int update_class_present(vpt_ctx* c) {
     std::vector<unsigned char> cls(c->instances.size());
-    if (!cls.empty()) HIPCHK(c, hipMemcpy(cls.data(), c->d_inst_class, cls.size(), hipMemcpyDeviceToHost));
+    if (!cls.empty()) HIPCHK(c, hipMemcpy(cls.data(), c->dw.inst_class, cls.size(), hipMemcpyDeviceToHost));
     c->class_present = 1u << kShadeMiss;
     for (unsigned char k : cls) if (k < kShadeClasses) c->class_present |= 1u << k;
     return VPT_OK;
+}
+// Everything derived from the materials and the feature flags (FURNACE_TEST_MODE is baked into the resolved-material table): resolve,
+// classify the instances, and read the classes back.  Whoever changes a material, the flags or the scene calls this.
+int refresh_material_tables(vpt_ctx* c) {
+    launch_precompute_materials(c->main.stream, c->dsc, c->params.flags, c->dw.mat_resolved, (uint32_t)c->materials.size());
+    launch_classify_instances(c->main.stream, c->dsc, c->dw.inst_class, (uint32_t)c->instances.size());
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    return update_class_present(c);
 }
 
 void begin_timing(vpt_ctx* c, hipStream_t s, int kernel, hipEvent_t* a, hipEvent_t* b) {
@@ -1130,6 +1094,81 @@ int ensure_post_buffers(vpt_ctx* c) {
     return VPT_OK;
 }
 
+// The tree build_bvh makes of a prepared scene's triangles.
+struct SceneBvh {
+    std::vector<BvhNode> nodes; std::vector<BvhNodeWide> wide; std::vector<BvhTri> leaf_tris; int depth = 0;
+};
+// Uploads a prepared scene and its tree (the previous scene's tables are gone: free_scene), and takes over the host copies later calls
+// work from (vpt_set_material, vpt_get_stats, the trace lab).
+int upload_scene(vpt_ctx* c, const vpt_scene_desc& sd, scene::HostScene& hs, const SceneBvh& bvh) {
+    DeviceScene& D = c->dsc;
+    vpt_ctx::Writable& W = c->dw;
+    int rc;
+    c->lds_scene = scene::rides_in_lds(bvh.nodes.size(), bvh.leaf_tris.size());
+    c->bvh_depth = (uint32_t)bvh.depth;
+    D.nodes_wide = nullptr; D.nodes8 = nullptr; D.nodes4s = nullptr;
+    if ((rc = upload(c, bvh.nodes, &D.nodes))) return rc;
+    if (c->lds_scene && (rc = upload(c, bvh.wide, &D.nodes_wide))) return rc;
+    if ((rc = upload(c, bvh.leaf_tris, &D.tris))) return rc;
+    D.node_count = (uint32_t)bvh.nodes.size(); D.tri_count = (uint32_t)bvh.leaf_tris.size();
+    D.scene_extent = bvh_max_abs_coord(hs.tris);   // the number the builder padded the boxes by (slab.hpp: the reach of the fma box test)
+    if ((rc = upload(c, scene::slot_of_gid(bvh.leaf_tris, hs.total_tris), &D.tri_slot_of_gid))) return rc;
+    if ((rc = upload(c, hs.verts, &D.vertices))) return rc;
+    if ((rc = upload(c, hs.idx, &D.indices))) return rc;
+    if ((rc = upload(c, hs.meshes, &D.meshes))) return rc;
+    if ((rc = upload(c, hs.instances, &D.instances))) return rc;
+    if ((rc = upload(c, hs.materials, &D.materials, 1, &W.materials))) return rc;
+    if ((rc = upload(c, hs.textures, &D.textures))) return rc;
+    if ((rc = upload(c, hs.texels, &D.texels, 4))) return rc;
+    // filled on the device (kernels_path.hip k_precompute_*) or by upload_emissive; per instance: an emissive mesh is an instance of an emissive material
+    const size_t n_inst = hs.instances.size(), n_tris = hs.total_tris;
+    if ((rc = alloc_table(c, n_inst, &D.emissive, &W.emissive))) return rc;
+    if ((rc = alloc_table(c, hs.materials.size(), &D.mat_resolved, &W.mat_resolved))) return rc;
+    if ((rc = alloc_table(c, n_tris, &D.emissive_tri, &W.emissive_tri))) return rc;
+    if ((rc = alloc_table(c, n_inst, &D.emissive_tri_offset, &W.emissive_tri_offset))) return rc;
+    if ((rc = alloc_table(c, n_tris, &D.tri_ng, &W.tri_ng))) return rc;
+    if ((rc = alloc_table(c, 8 * std::max<size_t>(1, n_tris), &D.tri_shade, &W.tri_shade))) return rc;   // 8 float4, one 128-byte line, per triangle
+    if ((rc = alloc_table(c, n_inst, &D.lights))) return rc;
+    if ((rc = alloc_table(c, n_inst, &D.inst_class, &W.inst_class))) return rc;
+    if ((rc = upload(c, hs.env, &D.env))) return rc;
+    if ((rc = upload(c, hs.alias, &D.alias))) return rc;
+    D.env_w = sd.env_width; D.env_h = sd.env_height;
+    D.env_black = hs.env_black ? 1u : 0u;
+    if ((rc = upload(c, sd.lut_reflection, 64 * 64 * 32, &D.lut_r))) return rc;
+    if ((rc = upload(c, sd.lut_refraction_outside, 128 * 128 * 32, &D.lut_o))) return rc;
+    if ((rc = upload(c, sd.lut_refraction_inside, 128 * 128 * 32, &D.lut_i))) return rc;
+    c->meshes = std::move(hs.meshes); c->instances = std::move(hs.instances); c->materials = std::move(hs.materials);
+    c->total_vertices = hs.total_vertices; c->total_indices = hs.total_indices;
+    c->texture_count = hs.texture_count; c->tex_1x1 = std::move(hs.tex_1x1);
+    c->bvh_input = std::move(hs.tris);
+    build_emissive(c);
+    return upload_emissive(c);
+}
+
+// The persistent grids of the scene's kernels, from the occupancy queries (kernels.hpp).
+void size_grids(vpt_ctx* c) {
+    const DeviceScene& D = c->dsc;
+#if VPT_LAB
+    c->trav_blocks = traverse_blocks_per_cu(c->lds_scene, D) * c->cu_count;
+    c->shade_blocks = shade_blocks_per_cu() * c->cu_count;
+#else
+    c->trav_blocks = 0;
+    c->shade_blocks = 4 * c->cu_count;   // (the media scatter stage's grid-stride launch)
+#endif
+    c->join_blocks = join_blocks_per_cu() * c->cu_count;
+    c->primary_blocks_general = bounce_blocks_per_cu(c->lds_scene, D, false) * c->cu_count;
+    c->primary_blocks_plain = bounce_blocks_per_cu(c->lds_scene, D, true) * c->cu_count;
+    c->primary_blocks = std::max(c->primary_blocks_general, c->primary_blocks_plain);   // (sizes the spill regions; update_depth_bounded picks the grid)
+    c->whole_blocks = c->lds_scene ? std::max(whole_blocks_per_cu(D, false), whole_blocks_per_cu(D, true)) * c->cu_count : 0;
+    c->shade_stream_blocks = shade_stream_blocks_per_cu() * c->cu_count;
+    c->finish_blocks = finish_blocks_per_cu(D) * c->cu_count;
+    c->shade_media_blocks = shade_media_blocks_per_cu() * c->cu_count;
+    c->media_tail_blocks = media_tail_blocks_per_cu() * c->cu_count;
+    c->shadow_blocks = trace_shadow_blocks_per_cu() * c->cu_count;
+    c->vote_blocks = std::min(trace_blocks_per_cu(VPT_TRACE_VOTE, false), trace_blocks_per_cu(VPT_TRACE_VOTE, true)) * c->cu_count;
+    c->max_blocks = std::max(std::max(std::max(std::max(c->trav_blocks, c->shade_blocks), std::max(c->primary_blocks, c->whole_blocks)), c->vote_blocks), std::max(std::max(c->shade_stream_blocks, c->finish_blocks), c->shadow_blocks));
+}
+
 const float* whole_image(vpt_ctx* c) { return c->P.shard_count > 1 ? c->full_image : c->image; }
 
 }  // namespace
@@ -1200,202 +1239,34 @@ const char* vpt_last_error(const vpt_ctx* c) { return c ? c->err.c_str() : "null
 
 int vpt_set_scene(vpt_ctx* c, const vpt_scene_desc* sd) {
     if (!c || !sd) return VPT_ERR_INVALID_ARGUMENT;
-    if (sd->mesh_count == 0 || !sd->meshes) return fail(c, VPT_ERR_INVALID_ARGUMENT, "No meshes found in scene");  // PathTracer.cpp:180
-    if (sd->mesh_count >= VPT_MAX_ENTITIES || sd->material_count >= VPT_MAX_ENTITIES) return fail(c, VPT_ERR_LIMIT, "too many meshes/materials");
-    if (sd->instance_count >= VPT_MAX_INSTANCES) return fail(c, VPT_ERR_LIMIT, "too many mesh instances");
-    if (!sd->materials || sd->material_count == 0 || !sd->instances || !sd->textures || sd->texture_count == 0 || !sd->env_rgba ||
-        sd->env_width == 0 || sd->env_height == 0 || !sd->lut_reflection || !sd->lut_refraction_outside || !sd->lut_refraction_inside)
-        return fail(c, VPT_ERR_INVALID_ARGUMENT, "incomplete scene description");
+    // a rejected description leaves the current scene untouched: everything that can refuse one is in scene::check, and what follows fails only on the device
+    const scene::Verdict verdict = scene::check(*sd);
+    if (verdict.code) return fail(c, verdict.code, verdict.msg);
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }
     const auto t_scene0 = std::chrono::steady_clock::now();
-    // ---- validate the whole description first: a rejected scene leaves the current one untouched
-    {
-        uint64_t nv = 0, ni = 0, texel_bytes = 0;
-        for (uint32_t m = 0; m < sd->mesh_count; m++) {
-            const vpt_mesh& me = sd->meshes[m];
-            if (!me.vertices || !me.indices || me.index_count % 3 != 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "bad mesh");
-            for (uint32_t k = 0; k < me.index_count; k++) if (me.indices[k] >= me.vertex_count) return fail(c, VPT_ERR_INVALID_ARGUMENT, "mesh index out of range");
-            nv += me.vertex_count; ni += me.index_count;
-        }
-        if (nv > 0xffffffffull || ni > 0xffffffffull) return fail(c, VPT_ERR_LIMIT, "more than 2^32 pooled vertices / indices");
-        for (uint32_t i = 0; i < sd->material_count; i++) {
-            const vpt_material& m = sd->materials[i];
-            if (m.base_color_texture >= sd->texture_count || m.normal_texture >= sd->texture_count || m.roughness_texture >= sd->texture_count ||
-                m.metallic_texture >= sd->texture_count || m.emissive_texture >= sd->texture_count)
-                return fail(c, VPT_ERR_INVALID_ARGUMENT, "material texture index out of range");
-        }
-        for (uint32_t i = 0; i < sd->instance_count; i++) {
-            if (sd->instances[i].mesh_index >= sd->mesh_count) return fail(c, VPT_ERR_INVALID_ARGUMENT, "instance mesh index out of range");
-            if (sd->instances[i].material_index >= sd->material_count) return fail(c, VPT_ERR_INVALID_ARGUMENT, "Mesh instance has invalid material index");  // PathTracer.cpp:454
-        }
-        for (uint32_t t = 0; t < sd->texture_count; t++) {
-            const vpt_texture& tx = sd->textures[t];
-            if (!tx.data || tx.width == 0 || tx.height == 0 || (tx.channels != 1 && tx.channels != 4)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "bad texture");
-            texel_bytes += (uint64_t)tx.width * tx.height * tx.channels + 3;
-        }
-        if (texel_bytes > 0xffffffffull) return fail(c, VPT_ERR_LIMIT, "texel pool over 4 GiB (TexDesc offsets are 32-bit)");
-    }
+    // ---- on the host: the tables and the tree
+    scene::HostScene hs = scene::prepare(*sd);
+    SceneBvh bvh;
+    c->sbvh = (c->cfg.build_flags & VPT_BUILD_SBVH) != 0u;   // spatial splits in the builder: a per-context option
+    const auto t_bvh0 = std::chrono::steady_clock::now();
+    build_bvh(hs.tris, bvh.nodes, bvh.wide, bvh.leaf_tris, &bvh.depth, nullptr, c->sbvh);
+    c->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_bvh0).count();
+    // ---- the old scene goes before the new one's tables are allocated: a scene near the memory limit never needs room for both
     free_scene(c);
     reset_accum(c);
     destroy_lanes(c);   // (their spill regions are sized by this scene's grids)
     c->state_gen++;
-    // ---- geometry pools
-    std::vector<vpt_vertex> verts; std::vector<uint32_t> idx;
-    c->meshes.clear(); c->total_vertices = 0; c->total_indices = 0;
-    for (uint32_t m = 0; m < sd->mesh_count; m++) {
-        const vpt_mesh& me = sd->meshes[m];
-        MeshDesc d; d.vertex_offset = (uint32_t)verts.size(); d.index_offset = (uint32_t)idx.size(); d.tri_count = me.index_count / 3; d.pad = 0;
-        verts.insert(verts.end(), me.vertices, me.vertices + me.vertex_count);
-        idx.insert(idx.end(), me.indices, me.indices + me.index_count);
-        c->meshes.push_back(d);
-        c->total_vertices += me.vertex_count; c->total_indices += me.index_count;
-    }
-    c->materials.assign(sd->materials, sd->materials + sd->material_count);
-    c->texture_count = sd->texture_count;
-    // ---- instances, flattened world-space triangles (instance-major global ids)
-    c->instances.clear();
-    std::vector<BvhTri> tris;
-    uint32_t total_tris = 0;
-    for (uint32_t i = 0; i < sd->instance_count; i++) {
-        const vpt_instance& in = sd->instances[i];
-        InstanceDesc d; memset(&d, 0, sizeof(d));
-        d.mesh = in.mesh_index; d.material = in.material_index; d.tri_offset = total_tris;
-        memcpy(d.xform, in.transform, 64);
-        vptfp::inverse3x3_from_mat4(in.transform, d.inv3);
-        c->instances.push_back(d);
-        const MeshDesc& me = c->meshes[d.mesh];
-        for (uint32_t t = 0; t < me.tri_count; t++) {
-            const uint32_t* ii = &idx[me.index_offset + t * 3];
-            vptfp::V3 p[3];
-            for (int k = 0; k < 3; k++) {
-                const vpt_vertex& v = verts[me.vertex_offset + ii[k]];
-                p[k] = vptfp::mat_point(d.xform, vptfp::v3(v.position[0], v.position[1], v.position[2]));
-            }
-            vptfp::V3 e1 = p[1] - p[0], e2 = p[2] - p[0];
-            BvhTri bt;
-            bt.v0[0] = p[0].x; bt.v0[1] = p[0].y; bt.v0[2] = p[0].z;
-            bt.e1[0] = e1.x; bt.e1[1] = e1.y; bt.e1[2] = e1.z;
-            bt.e2[0] = e2.x; bt.e2[1] = e2.y; bt.e2[2] = e2.z;
-            bt.prim = t; bt.inst = i; bt.gid = total_tris++;  // instance-major id over ALL triangles (tie-break key)
-            if (!vptfp::triangle_degenerate(e1, e2)) tris.push_back(bt);  // slivers are not intersectable (vpt_fp32.h)
-        }
-    }
-    std::vector<BvhNode> nodes; std::vector<BvhNodeWide> wide; std::vector<BvhTri> leaf_tris; int depth = 0;
-    c->sbvh = (c->cfg.build_flags & VPT_BUILD_SBVH) != 0u;   // spatial splits in the builder: a per-context option
-    const auto t_bvh0 = std::chrono::steady_clock::now();
-    build_bvh(tris, nodes, wide, leaf_tris, &depth, nullptr, c->sbvh);
-    c->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_bvh0).count();
-    c->bvh_input = tris; c->dsc.nodes8 = nullptr; c->dsc.nodes4s = nullptr;
-    c->bvh_depth = (uint32_t)depth;
-    // ---- textures
-    c->tex_1x1.clear();
-    std::vector<TexDesc> tds; std::vector<uint8_t> texels;
-    for (uint32_t t = 0; t < sd->texture_count; t++) {
-        const vpt_texture& tx = sd->textures[t];
-        while (texels.size() % 4) texels.push_back(0);
-        TexDesc d; d.offset = (uint32_t)texels.size(); d.w = tx.width; d.h = tx.height; d.c = tx.channels;
-        c->tex_1x1.push_back(tx.width == 1 && tx.height == 1 ? 1 : 0);
-        texels.insert(texels.end(), tx.data, tx.data + (size_t)tx.width * tx.height * tx.channels);
-        tds.push_back(d);
-    }
-    // TexDesc.offset and the shade stage's texel addresses are 32-bit byte offsets into the pool
-    if (texels.size() > 0xffffffffull) return fail(c, VPT_ERR_LIMIT, "the scene's textures exceed the 4 GiB texel pool");
-    // ---- environment + tables
-    std::vector<float> env; std::vector<AliasEntry> alias;
-    build_env_tables(sd->env_rgba, sd->env_width, sd->env_height, env, alias);
-    std::vector<float> lr(sd->lut_reflection, sd->lut_reflection + 64 * 64 * 32);
-    std::vector<float> lo(sd->lut_refraction_outside, sd->lut_refraction_outside + 128 * 128 * 32);
-    std::vector<float> li(sd->lut_refraction_inside, sd->lut_refraction_inside + 128 * 128 * 32);
-    build_emissive(c);
-    // ---- upload
-    DeviceScene& D = c->dsc;
     int rc;
-    if ((rc = upload(c, nodes, &D.nodes))) return rc;
-    // small scenes ride in LDS next to the traversal stacks, in the fp32 node form: up to 3 KB, so that three blocks of the fused
-    // kernel (14 KB of stacks + 36 KB of regrouping ring + the scene each) still fit the 160 KB of a CU
-    c->lds_scene = (nodes.size() * sizeof(BvhNodeWide) + leaf_tris.size() * sizeof(BvhTri)) <= 3072;
-    D.nodes_wide = nullptr;
-    if (c->lds_scene && (rc = upload(c, wide, &D.nodes_wide))) return rc;
-    if ((rc = upload(c, leaf_tris, &D.tris))) return rc;
-    D.node_count = (uint32_t)nodes.size(); D.tri_count = (uint32_t)leaf_tris.size();
-    D.scene_extent = bvh_max_abs_coord(tris);   // the number the builder padded the boxes by (slab.hpp: the reach of the fma box test)
-    {
-        std::vector<uint32_t> slot_of(total_tris, 0xffffffffu);  // 0xffffffff: a sliver, in no leaf
-        for (size_t i = 0; i < leaf_tris.size(); i++) slot_of[leaf_tris[i].gid] = (uint32_t)i;
-        if ((rc = upload(c, slot_of, &D.tri_slot_of_gid))) return rc;
-    }
-    if ((rc = upload(c, verts, &D.vertices))) return rc;
-    if ((rc = upload(c, idx, &D.indices))) return rc;
-    if ((rc = upload(c, c->meshes, &D.meshes))) return rc;
-    if ((rc = upload(c, c->instances, &D.instances))) return rc;
-    const vpt_material* dm = nullptr;
-    if ((rc = upload(c, c->materials, &dm))) return rc;
-    D.materials = dm; c->d_materials = const_cast<vpt_material*>(dm);
-    if ((rc = upload(c, tds, &D.textures))) return rc;
-    if ((rc = upload(c, texels, &D.texels, 4))) return rc;
-    {
-        void* d = nullptr;
-        HIPCHK(c, hipMalloc(&d, sizeof(EmissiveDesc) * std::max<size_t>(1, c->instances.size())));
-        c->scene_allocs.push_back(d);
-        c->d_emissive = (EmissiveDesc*)d; D.emissive = c->d_emissive;
-    }
-    {
-        void *d1 = nullptr, *d2 = nullptr, *d3 = nullptr, *d4 = nullptr;
-        HIPCHK(c, hipMalloc(&d1, sizeof(MatResolved) * c->materials.size())); c->scene_allocs.push_back(d1);
-        HIPCHK(c, hipMalloc(&d2, sizeof(EmissiveTri) * std::max<size_t>(1, total_tris))); c->scene_allocs.push_back(d2);
-        HIPCHK(c, hipMalloc(&d3, 4 * std::max<size_t>(1, c->instances.size()))); c->scene_allocs.push_back(d3);
-        HIPCHK(c, hipMalloc(&d4, 16 * std::max<size_t>(1, total_tris))); c->scene_allocs.push_back(d4);
-        void* d6 = nullptr;
-        HIPCHK(c, hipMalloc(&d6, 128 * std::max<size_t>(1, total_tris))); c->scene_allocs.push_back(d6);
-        c->d_tri_shade = (float4*)d6; D.tri_shade = c->d_tri_shade;
-        void* d7 = nullptr;   // one LightSampler per emissive mesh (at most one per instance)
-        HIPCHK(c, hipMalloc(&d7, sizeof(LightSampler) * std::max<size_t>(1, c->instances.size()))); c->scene_allocs.push_back(d7);
-        D.lights = (const LightSampler*)d7;
-        void* d5 = nullptr;
-        HIPCHK(c, hipMalloc(&d5, std::max<size_t>(1, c->instances.size()))); c->scene_allocs.push_back(d5);
-        c->d_inst_class = (unsigned char*)d5; D.inst_class = c->d_inst_class;
-        c->d_mat_resolved = (MatResolved*)d1; c->d_emissive_tri = (EmissiveTri*)d2; c->d_emissive_tri_offset = (uint32_t*)d3; c->d_tri_ng = (float4*)d4;
-        D.mat_resolved = c->d_mat_resolved; D.emissive_tri = c->d_emissive_tri; D.emissive_tri_offset = c->d_emissive_tri_offset; D.tri_ng = c->d_tri_ng;
-    }
-    if ((rc = upload_emissive(c))) return rc;
-    if ((rc = upload(c, env, &D.env))) return rc;
-    if ((rc = upload(c, alias, &D.alias))) return rc;
-    D.env_w = sd->env_width; D.env_h = sd->env_height;
-    D.env_black = 1u;
-    for (size_t i = 0; i < env.size(); i++) if (env[i] != 0.0f) { D.env_black = 0u; break; }
-    if ((rc = upload(c, lr, &D.lut_r))) return rc;
-    if ((rc = upload(c, lo, &D.lut_o))) return rc;
-    if ((rc = upload(c, li, &D.lut_i))) return rc;
-#if VPT_LAB
-    c->trav_blocks = traverse_blocks_per_cu(c->lds_scene, D) * c->cu_count;
-    c->shade_blocks = shade_blocks_per_cu() * c->cu_count;
-#else
-    c->trav_blocks = 0;
-    c->shade_blocks = 4 * c->cu_count;   // (the media scatter stage's grid-stride launch)
-#endif
-    c->join_blocks = join_blocks_per_cu() * c->cu_count;
-    c->primary_blocks_general = bounce_blocks_per_cu(c->lds_scene, D, false) * c->cu_count;
-    c->primary_blocks_plain = bounce_blocks_per_cu(c->lds_scene, D, true) * c->cu_count;
-    c->primary_blocks = std::max(c->primary_blocks_general, c->primary_blocks_plain);   // (sizes the spill regions below; update_depth_bounded picks the grid)
-    c->whole_blocks = c->lds_scene ? std::max(whole_blocks_per_cu(D, false), whole_blocks_per_cu(D, true)) * c->cu_count : 0;
-    c->shade_stream_blocks = shade_stream_blocks_per_cu() * c->cu_count;
-    c->finish_blocks = finish_blocks_per_cu(D) * c->cu_count;
-    c->shade_media_blocks = shade_media_blocks_per_cu() * c->cu_count;
-    c->media_tail_blocks = media_tail_blocks_per_cu() * c->cu_count;
-    c->shadow_blocks = trace_shadow_blocks_per_cu() * c->cu_count;
-    c->vote_blocks = std::min(trace_blocks_per_cu(VPT_TRACE_VOTE, false), trace_blocks_per_cu(VPT_TRACE_VOTE, true)) * c->cu_count;
-    c->max_blocks = std::max(std::max(std::max(std::max(c->trav_blocks, c->shade_blocks), std::max(c->primary_blocks, c->whole_blocks)), c->vote_blocks), std::max(std::max(c->shade_stream_blocks, c->finish_blocks), c->shadow_blocks));
+    if ((rc = upload_scene(c, *sd, hs, bvh))) return rc;
+    size_grids(c);
     // two regions: the shadow kernels of bounce k run on the second stream beside the extend kernel of bounce k + 1, and a
     // spill slot is addressed by (block, thread) alone, so concurrent grids must not share one region (round 2 did)
     if ((rc = alloc_spill(c, c->main, 2))) return rc;
     c->spill_dirty = true;
-    launch_precompute_tri_ng(c->main.stream, D, c->d_tri_ng);
-    launch_precompute_tri_shade(c->main.stream, D, c->d_tri_shade);
-    launch_precompute_materials(c->main.stream, D, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
-    launch_classify_instances(c->main.stream, D, c->d_inst_class, (uint32_t)c->instances.size());
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    if ((rc = update_class_present(c))) return rc;
+    launch_precompute_tri_ng(c->main.stream, c->dsc, c->dw.tri_ng);
+    launch_precompute_tri_shade(c->main.stream, c->dsc, c->dw.tri_shade);
+    if ((rc = refresh_material_tables(c))) return rc;
     HIPCHK(c, hipGetLastError());
     c->has_scene = true;
     update_depth_bounded(c);
@@ -1409,21 +1280,16 @@ int vpt_set_material(vpt_ctx* c, uint32_t index, const vpt_material* m) {
     if (!c || !m) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
     if (index >= c->materials.size()) return fail(c, VPT_ERR_INVALID_ARGUMENT, "material index out of range");
-    if (m->base_color_texture >= c->texture_count || m->normal_texture >= c->texture_count || m->roughness_texture >= c->texture_count ||
-        m->metallic_texture >= c->texture_count || m->emissive_texture >= c->texture_count)
-        return fail(c, VPT_ERR_INVALID_ARGUMENT, "material texture index out of range");   // the shade stage indexes textures[] unchecked
+    if (!scene::material_textures_ok(*m, c->texture_count)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "material texture index out of range");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rd = drain(c); if (rd) return rd; }   // batches in flight read the tables patched below
     c->state_gen++;
     const vpt_material& old = c->materials[index];
     bool emissive_changed = old.emissive_color[0] != m->emissive_color[0] || old.emissive_color[1] != m->emissive_color[1] || old.emissive_color[2] != m->emissive_color[2];
     c->materials[index] = *m;
-    HIPCHK(c, hipMemcpy(c->d_materials + index, m, sizeof(vpt_material), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->dw.materials + index, m, sizeof(vpt_material), hipMemcpyHostToDevice));
     if (emissive_changed) { build_emissive(c); int rc = upload_emissive(c); if (rc) return rc; }
-    launch_precompute_materials(c->main.stream, c->dsc, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
-    launch_classify_instances(c->main.stream, c->dsc, c->d_inst_class, (uint32_t)c->instances.size());
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    { int rc2 = update_class_present(c); if (rc2) return rc2; }
+    { int rc2 = refresh_material_tables(c); if (rc2) return rc2; }
     update_depth_bounded(c);
     reset_accum(c);
     return VPT_OK;
@@ -1462,10 +1328,7 @@ int vpt_set_params(vpt_ctx* c, const vpt_params* p) {
     reset_accum(c);
     if (flags_changed && c->has_scene) {  // FURNACE_TEST_MODE is baked into the resolved-material table
         HIPCHK(c, hipSetDevice(c->cfg.device));
-        launch_precompute_materials(c->main.stream, c->dsc, c->params.flags, c->d_mat_resolved, (uint32_t)c->materials.size());
-        launch_classify_instances(c->main.stream, c->dsc, c->d_inst_class, (uint32_t)c->instances.size());
-        HIPCHK(c, hipStreamSynchronize(c->main.stream));
-        int rc2 = update_class_present(c); if (rc2) return rc2;
+        int rc2 = refresh_material_tables(c); if (rc2) return rc2;
     }
     return VPT_OK;
 }
@@ -1935,7 +1798,7 @@ int vpt_get_stats(vpt_ctx* c, vpt_stats* out) {
     s.total_vertex_count = c->total_vertices; s.total_index_count = c->total_indices;
     s.bvh_nodes = c->dsc.node_count; s.bvh_triangles = c->dsc.tri_count;
     s.bvh_node_bytes = c->lds_scene ? sizeof(BvhNodeWide) : sizeof(BvhNode); s.bvh_tri_bytes = sizeof(BvhTri);
-    s.emissive_mesh_count = (uint32_t)c->emissive.size(); s.emissive_triangle_count = c->emissive_tris;
+    s.emissive_mesh_count = (uint32_t)c->emissive.list.size(); s.emissive_triangle_count = c->emissive.tris;
     s.frames_in_flight = batch_cap(c); s.shard_pixels = c->P.shard_pixels;   // (the largest batch the context renders at once with its current scene and parameters)
     s.build_flags = (c->sbvh ? VPT_BUILD_SBVH : 0u) | (c->cfg.build_flags & (VPT_BUILD_GENERAL_KERNELS | VPT_BUILD_STREAMS_ONLY));
     s.frames_allocated = c->main.frames_alloc; s.resident_frames = c->main.resident_alloc;
