@@ -1,0 +1,87 @@
+// stack_bound_host — how deep the traversal stack of a closest-hit search (traverse.hpp trace_closest_pass) can get on the product builder's
+// four-wide tree over a set of triangles: a bound from the tree's shape alone, and the depth that given rays reach, by the same loop on the
+// host (slab.hpp box_entry, vpt_fp32.h ray_triangle).  The whole-path kernel keeps kWholeStackRows (6) entries per lane in LDS; a scene whose
+// bound is at most that can never write its overflow region.  Shared library for tests/test_stack_bound_cpu.py and the scene of
+// tests/test_gpu_whole_refill.py.  Test utility only (built on demand by the tests); nothing in the product links it.
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#include "../../vulkan-path-tracer_amd/csrc/bvh_build.hpp"
+#include "../../vulkan-path-tracer_amd/csrc/slab.hpp"
+using namespace vpt;
+
+namespace {
+struct Tree {
+    std::vector<BvhNode> nodes; std::vector<BvhNodeWide> wide; std::vector<BvhTri> leaf; int depth = 0;
+};
+void build(const void* tris_in, int ntris, Tree& t) {
+    std::vector<BvhTri> tris(ntris);
+    memcpy(tris.data(), tris_in, sizeof(BvhTri) * (size_t)ntris);
+    build_bvh(tris, t.nodes, t.wide, t.leaf, &t.depth, nullptr, false, false);
+}
+bool used(const BvhNodeWide& n, int k) { return n.minx[k] < 1.0e29f; }   // (an unused slot is an unreachable point box: bvh_build.cpp empty_wide)
+// A node with k children pushes at most k - 1 of them and goes down into the other; whichever it takes first has all its siblings below it.
+int bound(const Tree& t, int node) {
+    int k = 0, below = 0;
+    for (int s = 0; s < 4; s++) {
+        if (!used(t.wide[node], s)) continue;
+        k++;
+        if (t.wide[node].child[s] >= 0) below = std::max(below, bound(t, t.wide[node].child[s]));
+    }
+    return (k > 0 ? k - 1 : 0) + below;
+}
+}  // namespace
+
+extern "C" {
+
+// out: {four-wide nodes, leaf triangles, bytes of the tree in LDS, levels of inner nodes below the root, stack bound}
+void sb_tree(const void* tris_in, int ntris, int* out) {
+    Tree t; build(tris_in, ntris, t);
+    out[0] = (int)t.wide.size(); out[1] = (int)t.leaf.size();
+    out[2] = (int)(t.wide.size() * sizeof(BvhNodeWide) + t.leaf.size() * sizeof(BvhTri));
+    out[3] = t.depth; out[4] = bound(t, 0);
+}
+
+// n rays (o, d: n x 3, d normalised; the kernels' closest-hit range 0.01 .. 1e5): per ray the largest number of entries its stack held.
+// prune = 0: tlimit stays tmax (no triangle tests), what a search whose triangles all miss would do.
+void sb_rays(const void* tris_in, int ntris, int64_t n, const float* o, const float* d, int prune, int* max_sp) {
+    Tree t; build(tris_in, ntris, t);
+    const float tmin = 0.01f, tmax = 100000.0f;
+    for (int64_t i = 0; i < n; i++) {
+        const V3 O = vptfp::v3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), D = vptfp::v3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), inv = safe_inverse(D);
+        std::vector<int> stack;
+        size_t deepest = 0;
+        float best_t = tmax; bool found = false; uint32_t best_gid = 0xffffffffu;
+        int cur = 0;
+        while (true) {
+            if (cur >= 0) {
+                const BvhNodeWide& nd = t.wide[cur];
+                float te[4]; int c[4];
+                for (int k = 0; k < 4; k++) { te[k] = box_entry(nd.minx[k], nd.miny[k], nd.minz[k], nd.maxx[k], nd.maxy[k], nd.maxz[k], O, inv, tmin, best_t); c[k] = nd.child[k]; }
+                auto cswap = [&](int a, int b) { if (te[b] < te[a]) { std::swap(te[a], te[b]); std::swap(c[a], c[b]); } };
+                cswap(0, 1); cswap(2, 3); cswap(0, 2); cswap(1, 3); cswap(1, 2);
+                if (te[0] < kMissT) {
+                    for (int k = 3; k >= 1; k--) if (te[k] < kMissT) stack.push_back(c[k]);
+                    deepest = std::max(deepest, stack.size());
+                    cur = c[0];
+                    continue;
+                }
+            } else if (prune) {
+                const uint32_t enc = (uint32_t)(~cur);
+                const int first = (int)(enc >> 3), cnt = (int)(enc & 7u) + 1;
+                for (int k = 0; k < cnt; k++) {
+                    const BvhTri& tr = t.leaf[first + k];
+                    float tt, u, v;
+                    if (vptfp::ray_triangle(O, D, vptfp::v3(tr.v0[0], tr.v0[1], tr.v0[2]), vptfp::v3(tr.e1[0], tr.e1[1], tr.e1[2]), vptfp::v3(tr.e2[0], tr.e2[1], tr.e2[2]),
+                                            tmin, tmax, &tt, &u, &v) && (!found || tt < best_t || (tt == best_t && tr.gid < best_gid))) { best_t = tt; best_gid = tr.gid; found = true; }
+                }
+            }
+            if (stack.empty()) break;
+            cur = stack.back(); stack.pop_back();
+        }
+        max_sp[i] = (int)deepest;
+    }
+}
+
+}

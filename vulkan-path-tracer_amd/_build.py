@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libvpt_hip.so")
 # slower, round 1's stage kernels (VPT_PIPELINE_STAGED_R1) and the vpt_lab_* entry points of include/vpt_lab.h.  The product library has none of it.
 LIB_LAB = os.path.join(HERE, "libvpt_hip_lab.so")
 SOURCES = ["kernels_path.hip", "kernels_trace.hip", "kernels_stream.hip", "kernels_media.hip", "kernels_post.hip", "kernels_lut.hip", "vpt_api.hip", "bvh_build.cpp"]
-HEADERS = ["device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "kernels.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp",
+HEADERS = ["device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "kernels.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp", "whole_refill.hpp",
            os.path.join("..", "..", "include", "vpt.h"), os.path.join("..", "..", "include", "vpt_lab.h"), os.path.join("..", "..", "include", "vpt_fp32.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-result", "-Wno-pass-failed"]

@@ -179,7 +179,7 @@ struct DeviceScene {
     const LightSampler* lights;             // per emissive mesh
     const uint32_t* tri_slot_of_gid;        // per global triangle id: position in the leaf-ordered triangle array
     const unsigned char* inst_class;        // per instance: shade class of its material (kShade*), the sort key of the shade queues
-    uint32_t* stack_overflow;               // traversal stack entries beyond the LDS part, kStackOverflow per resident thread
+    uint32_t* stack_overflow;               // traversal stack entries beyond the LDS part, kOverflowStride (traverse.hpp) per resident thread
     const vpt_volume* volumes;              // uVolumes (Volume.slang:9); volume_count == 0: none
     uint32_t volume_count, phase;           // PHASE_FUNCTION_* (PathTracer.h:76-81)
     uint32_t atm_on;                        // ENABLE_ATMOSPHERE

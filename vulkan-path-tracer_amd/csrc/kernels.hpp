@@ -35,7 +35,7 @@ void launch_precompute_materials(hipStream_t s, const DeviceScene& sc, uint32_t 
 void launch_precompute_tri_ng(hipStream_t s, const DeviceScene& sc, float4* out);
 void launch_precompute_tri_shade(hipStream_t s, const DeviceScene& sc, float4* out);
 void launch_precompute_emissive(hipStream_t s, const DeviceScene& sc, EmissiveTri* out, uint32_t total);
-size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene);
+size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene, int stack_rows);   // stack_rows: LDS entries per lane (traverse.hpp kStackDepth; k_whole: kWholeStackRows)
 size_t stack_overflow_bytes(uint32_t blocks);  // per-thread spill region of the traversal stacks for a grid of `blocks`
 int traverse_blocks_per_cu(bool lds_scene, const DeviceScene& sc);
 int shade_blocks_per_cu();

@@ -18,6 +18,7 @@
 #include "wave.hpp"
 #include "shade_core.hpp"
 #include "vote.hpp"
+#include "whole_refill.hpp"
 
 namespace vpt {
 
@@ -56,9 +57,9 @@ __device__ inline void stage_scene(const DeviceScene& sc, float4* lds_nodes, flo
         __syncthreads();
     }
 }
-template <bool LDS_SCENE, bool COUNT>
+template <bool LDS_SCENE, bool COUNT, class Stack>
 __device__ inline bool trace_any(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, float tmin,
-                                 float tmax, const TravStack& stack, HitRec& h, TravStats& st) {
+                                 float tmax, const Stack& stack, HitRec& h, TravStats& st) {
     if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
     GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
     return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st);
@@ -66,16 +67,16 @@ __device__ inline bool trace_any(const DeviceScene& sc, const float4* lds_nodes,
 
 // Sky visibility / light identity as exact any-hit queries (traverse.hpp).
 // rq: USE_RAY_QUERIES (RTCommon.slang:52-63: the direction as it is, TMin 1e-4, TMax 1e6); otherwise RTCommon.slang:64-84: normalised, TMin 1e-5, TMax 1000.
-template <bool LDS_SCENE, bool COUNT>
-__device__ inline bool sky_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const TravStack& stack, TravStats& st, bool rq) {
+template <bool LDS_SCENE, bool COUNT, class Stack>
+__device__ inline bool sky_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const Stack& stack, TravStats& st, bool rq) {
     const float tmin = rq ? 0.0001f : 0.00001f, tmax = rq ? 1000000.0f : 1000.0f;
     if (!rq) d = normalize(d);
     if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
     GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
     return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st);
 }
-template <bool LDS_SCENE, bool COUNT>
-__device__ inline bool light_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const TravStack& stack, TravStats& st) {
+template <bool LDS_SCENE, bool COUNT, class Stack>
+__device__ inline bool light_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const Stack& stack, TravStats& st) {
     uint32_t slot = sc.tri_slot_of_gid[gid];
     if (slot == 0xffffffffu) return false;  // the sampled light triangle is a sliver: nothing can hit it
     if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
@@ -778,10 +779,14 @@ __global__ void k_finish_done(StreamCounters* sctr, uint32_t parity) { sctr->ali
 #ifndef VPT_DIAG_NO_LIGHT_SEARCH
 #define VPT_DIAG_NO_LIGHT_SEARCH 0
 #endif
+#ifndef VPT_DIAG_REFILL_LANES
+#define VPT_DIAG_REFILL_LANES 0
+#endif
 constexpr int kWalkDone = 0x7fffffff;
-__device__ __forceinline__ int walk_pop(TravStack& stack) { return stack.sp ? (int)stack.pop() : kWalkDone; }
-template <bool COUNT>
-__device__ __forceinline__ bool lds_closest_vote(const LdsSceneSrc& src, V3 o, V3 d, float tmin, float tmax, TravStack stack, HitRec& best, TravStats& st) {
+template <class Stack>
+__device__ __forceinline__ int walk_pop(Stack& stack) { return stack.sp ? (int)stack.pop() : kWalkDone; }
+template <bool COUNT, class Stack>
+__device__ __forceinline__ bool lds_closest_vote(const LdsSceneSrc& src, V3 o, V3 d, float tmin, float tmax, Stack stack, HitRec& best, TravStats& st) {
     best.t = tmax; best.u = 0.0f; best.v = 0.0f; best.prim = 0xffffffffu; best.inst = 0xffffffffu; best.gid = 0xffffffffu; best.slot = 0;
     bool found = false;
     const RaySlabWide slab = make_slab<false>(src, o, d);
@@ -828,8 +833,8 @@ __device__ __forceinline__ bool lds_closest_vote(const LdsSceneSrc& src, V3 o, V
     return found;
 }
 // any-hit: LIGHT = false: occluded <=> some triangle is hit in (tmin, tmax); LIGHT = true: something beats the sampled triangle's hit at t_e (traverse.hpp)
-template <bool COUNT, bool LIGHT>
-__device__ __forceinline__ bool lds_occluded_vote(const LdsSceneSrc& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, TravStack stack, TravStats& st) {
+template <bool COUNT, bool LIGHT, class Stack>
+__device__ __forceinline__ bool lds_occluded_vote(const LdsSceneSrc& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, Stack stack, TravStats& st) {
     const float tlimit = LIGHT ? t_e : tmax;
     const RaySlabWide slab = make_slab<false>(src, o, d);
     stack.sp = 0;
@@ -871,15 +876,15 @@ __device__ __forceinline__ bool lds_occluded_vote(const LdsSceneSrc& src, V3 o, 
     return occluded;
 }
 // sky_visible / light_visible of k_whole's non-validating instantiations (the interval and direction rules of sky_visible above)
-template <bool COUNT>
-__device__ __forceinline__ bool sky_visible_vote(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const TravStack& stack, TravStats& st, bool rq) {
+template <bool COUNT, class Stack>
+__device__ __forceinline__ bool sky_visible_vote(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const Stack& stack, TravStats& st, bool rq) {
     const float tmin = rq ? 0.0001f : 0.00001f, tmax = rq ? 1000000.0f : 1000.0f;
     if (!rq) d = normalize(d);
     LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * sc.scene_extent};
     return !lds_occluded_vote<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st);
 }
-template <bool COUNT>
-__device__ __forceinline__ bool light_visible_vote(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const TravStack& stack, TravStats& st) {
+template <bool COUNT, class Stack>
+__device__ __forceinline__ bool light_visible_vote(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const Stack& stack, TravStats& st) {
     const uint32_t slot = sc.tri_slot_of_gid[gid];
     if (slot == 0xffffffffu) return false;  // the sampled light triangle is a sliver: nothing can hit it
     LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * sc.scene_extent};
@@ -930,25 +935,27 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
     if (P.dispatch_base_dev) dispatch_base = *P.dispatch_base_dev;   // a replayed graph: the batch's first dispatch index lives in device memory
     const bool rq = (P.flags & VPT_FLAG_RAY_QUERIES) != 0u;
     extern __shared__ __align__(16) unsigned char smem[];
-    const TravStack stack = make_stack(smem, sc.stack_overflow);
-    float4* lds_nodes = reinterpret_cast<float4*>(smem + kStackDepth * kTraverseBlock * 4);
+    const TravStackT<kWholeStackRows> stack = make_stack<kWholeStackRows>(smem, sc.stack_overflow);
+    float4* lds_nodes = reinterpret_cast<float4*>(smem + kWholeStackRows * kTraverseBlock * 4);
     float4* lds_tris = lds_nodes + sc.node_count * 8;
     stage_scene<true>(sc, lds_nodes, lds_tris);
     constexpr uint32_t kWaves = kTraverseBlock / 64u;
     __shared__ uint32_t r_slot[kWaves][128], r_prim[kWaves][128], r_inst[kWaves][128];
     __shared__ float r_t[kWaves][128], r_u[kWaves][128], r_v[kWaves][128];
     __shared__ float4 r_ra[kWaves][128], r_rb[kWaves][128], r_rt[kWaves][128];
-    const uint32_t wave = threadIdx.x >> 6;
-    const uint32_t n = n_slots;
-    // tile cursor, wave-uniform by construction (kernels_trace.hip k_trace_vote)
-    const uint32_t n_waves = gridDim.x * kWaves, n_tiles = (n + 63u) / 64u;
-    const uint32_t dyn_first = static_rounds * n_waves;   // tiles from here on are taken through the counter
-    uint32_t static_left = static_rounds;
-    uint32_t next_static = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wave);
-    uint32_t w_next = 0u, w_end = 0u;
-    uint32_t last_seen = dyn_first;   // how far the tile counter had got when this wave last took from it
-    bool exhausted = false;
+    // the wave's fresh camera rays (whole_refill.hpp): slot, origin, direction, RNG state behind camera_ray; dword arrays, lane = bank
+    __shared__ uint32_t f_slot[kWaves][refill::kTile], f_rng[kWaves][refill::kTile];
+    __shared__ float f_ox[kWaves][refill::kTile], f_oy[kWaves][refill::kTile], f_oz[kWaves][refill::kTile];
+    __shared__ float f_dx[kWaves][refill::kTile], f_dy[kWaves][refill::kTile], f_dz[kWaves][refill::kTile];
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (uniform: the rings' and the buffer's rows are addressed from a scalar base)
+    // tile cursor and fresh-ray buffer, wave-uniform by construction (kernels_trace.hip k_trace_vote)
+    const refill::Shape shape{n_slots, gridDim.x * kWaves, static_rounds, chunk_tiles};
+    refill::Cursor cur = refill::make_cursor(shape, blockIdx.x * kWaves + wave);
+    refill::Fresh fresh = refill::make_fresh();
     uint32_t hit_head = 0u, hit_count = 0u;   // wave-uniform
+#if VPT_DIAG_REFILL_LANES
+    uint32_t d_passes = 0u, d_lanes = 0u;
+#endif
     TravStats st, sst; st.nodes = 0; st.tris = 0; sst.nodes = 0; sst.tris = 0;
     uint32_t w_paths = 0u, w_rays = 0u, w_hits0 = 0u, w_alive0 = 0u, w_rays0 = 0u, w_parked = 0u;   // wave totals (uniform); *0: bounce 0 only; parked: hits of later bounces (their pathLight waits in ACC)
     // the lane's path between two steps
@@ -959,7 +966,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
     float pdf = 1.0f;
     for (;;) {
         // ---- shade: a chunk of parked hits (a partial one only when nothing can be added to it any more: no lane holds a ray here)
-        if (hit_count >= 64u || (exhausted && hit_count > 0u)) {
+        if (hit_count >= 64u || (refill::exhausted(cur, fresh) && hit_count > 0u)) {
             const uint32_t cnt = hit_count < 64u ? hit_count : 64u;
             const bool valid = lane_id() < cnt;
             uint32_t nrays = 0u;
@@ -1015,47 +1022,55 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
             w_rays0 += (uint32_t)__popcll(__ballot(first && nrays >= 1u)) + (uint32_t)__popcll(__ballot(first && nrays >= 2u));
             w_alive0 += (uint32_t)__popcll(__ballot(first && alive));
         }
-        // ---- refill: free lanes take the next unstarted samples (a second pass when the wave's chunk ran out half-way)
-        if (!exhausted) {
+        // ---- refill: free lanes take the next unstarted samples from the front of the wave's buffer; when it runs out, ALL lanes generate the next
+        // tile of camera rays into it (a second pass when the buffer ran out half-way)
+        if (!refill::exhausted(cur, fresh)) {
 #pragma unroll 1
             for (int pass = 0; pass < 2; pass++) {
                 const unsigned long long m_free = __ballot(!has_ray);
                 if (m_free == 0ull) break;
-                if (w_next >= w_end) {   // the next tile(s)
-                    uint32_t tile, span = 1u;
-                    if (static_left != 0u) { tile = next_static; next_static += n_waves; static_left--; }
-                    else {
-                        // guided (chunk_tiles bit 8): the chunk shrinks with what is left — by this wave's last look at the counter — so that the waves run dry within a tile of each other
-                        uint32_t take = chunk_tiles & 0xffu;
-                        if (chunk_tiles & 0x100u) {
-                            const uint32_t left_tiles = n_tiles > last_seen ? n_tiles - last_seen : 0u, fair = left_tiles / (2u * n_waves);
-                            take = fair < 1u ? 1u : (fair < take ? fair : take);
-                        }
+                if (fresh.count == 0u) {
+                    if (refill::range_empty(cur) && !refill::take_static(shape, cur)) {   // the next tile(s) through the counter
+                        const uint32_t take = refill::dyn_take(shape, cur);
                         uint32_t k = 0u;
                         if (lane_id() == 0u) k = atomicAdd(&ctr->extend_head, take);
-                        tile = dyn_first + __builtin_amdgcn_readfirstlane(k); span = take;
-                        last_seen = tile + take;
+                        refill::take_dynamic(shape, cur, __builtin_amdgcn_readfirstlane(k), take);
                     }
-                    if (tile >= n_tiles) exhausted = true;
-                    else { w_next = tile * 64u; w_end = (tile + span) * 64u < n ? (tile + span) * 64u : n; }
+                    if (refill::exhausted(cur, fresh)) break;
+                    const uint32_t g = refill::gen_count(cur);
+#if VPT_DIAG_REFILL_LANES
+                    d_passes++; d_lanes += g;
+#endif
+                    if (lane_id() < g) {
+                        uint32_t gslot, x, y, f;
+                        launch_pixel(P, cur.w_next + lane_id(), dispatch_base, gslot, x, y, f);
+                        const uint32_t seed = pcg_hash(P.base_seed + dispatch_base + f);  // PathTracer.cpp:139 with an explicit seed
+                        Rng r; r.s = y + P.width * x + seed;                              // RayGen.slang:28
+                        V3 go, gd;
+                        camera_ray(P, r, x, y, go, gd);
+                        const uint32_t j = lane_id();
+                        f_slot[wave][j] = gslot; f_rng[wave][j] = r.s;
+                        f_ox[wave][j] = go.x; f_oy[wave][j] = go.y; f_oz[wave][j] = go.z;
+                        f_dx[wave][j] = gd.x; f_dy[wave][j] = gd.y; f_dz[wave][j] = gd.z;
+                    }
+                    refill::generated(cur, fresh, g);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 }
-                if (exhausted) break;
-                const uint32_t li = w_next + lanes_below(m_free);
-                if (!has_ray && li < w_end) {
-                    uint32_t x, y, f;
-                    launch_pixel(P, li, dispatch_base, slot, x, y, f);
-                    const uint32_t seed = pcg_hash(P.base_seed + dispatch_base + f);  // PathTracer.cpp:139 with an explicit seed
-                    Rng r; r.s = y + P.width * x + seed;                              // RayGen.slang:28
-                    camera_ray(P, r, x, y, porg, pdir);
-                    rng_s = r.s; depth = 0u; in_medium = false; thr = v3s(1.0f); pdf = 1.0f; lightp = v3s(0.0f);
+                const uint32_t q = fresh.head + lanes_below(m_free);
+                refill::pop(fresh, (uint32_t)__popcll(m_free));
+                if (!has_ray && q < fresh.head) {
+                    slot = f_slot[wave][q]; rng_s = f_rng[wave][q];
+                    porg = v3(f_ox[wave][q], f_oy[wave][q], f_oz[wave][q]);
+                    pdir = v3(f_dx[wave][q], f_dy[wave][q], f_dz[wave][q]);
+                    depth = 0u; in_medium = false; thr = v3s(1.0f); pdf = 1.0f; lightp = v3s(0.0f);
                     has_ray = true;
                 }
-                const uint32_t want = (uint32_t)__popcll(m_free), left = w_end - w_next;
-                w_next += want < left ? want : left;
             }
         }
         if (__ballot(has_ray) == 0ull) {
-            if (exhausted && hit_count == 0u) break;
+            if (refill::exhausted(cur, fresh) && hit_count == 0u) break;
             continue;
         }
         // ---- trace: closest hits; park the hits, finish the misses
@@ -1104,7 +1119,13 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
         if (w_rays0) atomicAdd(&ctr->stat_primary_rays, (unsigned long long)w_rays0);
         if (w_parked) atomicAdd(&ctr->stat_connect, (unsigned long long)w_parked);   // vpt_stats.connect_paths: here, the hits whose pathLight made the round trip through ACC
     }
-    if (COUNT) {
+#if VPT_DIAG_REFILL_LANES   // measuring build only: passes of camera_ray and the lanes that ran them, reported IN PLACE of a counting context's closest-hit visits
+    if (lane_id() == 0) { atomicAdd(&ctr->stat_nodes, (unsigned long long)d_passes); atomicAdd(&ctr->stat_tris, (unsigned long long)d_lanes); }
+    constexpr bool kReportVisits = false;
+#else
+    constexpr bool kReportVisits = COUNT;
+#endif
+    if (kReportVisits) {
         atomicAdd(&ctr->stat_nodes, (unsigned long long)st.nodes);
         atomicAdd(&ctr->stat_tris, (unsigned long long)st.tris);
         atomicAdd(&ctr->stat_shadow_nodes, (unsigned long long)sst.nodes);
@@ -1395,7 +1416,7 @@ static inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 void launch_bounce(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, bool first, const DeviceScene& sc, const RenderParams& P,
                    const PathState& ps, const StreamState& ss, const uint32_t* queue, uint32_t* queue_next, Counters* ctr, uint32_t parity, uint32_t n_slots,
                    uint32_t dispatch_base, uint32_t k3, bool plain) {
-    size_t lds = traverse_lds_bytes(sc, lds_scene);
+    size_t lds = traverse_lds_bytes(sc, lds_scene, kStackDepth);
     dim3 g(blocks), b(kTraverseBlock);
     if (plain && lds_scene && !count && !sc.strict_hits && sc.volume_count == 0u && !sc.atm_on && sc.env_black) {   // the scene-class instantiation
         if (first) hipLaunchKernelGGL((k_bounce<true, false, true, false, false, true>), g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3);
@@ -1424,14 +1445,14 @@ void launch_bounce(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, b
 // Whole paths in one launch (k_whole): LDS-resident scenes without media, one sample per pixel and frame.
 void launch_whole(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, Counters* ctr, uint32_t n_slots,
                   uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles) {
-    const size_t lds = traverse_lds_bytes(sc, true);
+    const size_t lds = traverse_lds_bytes(sc, true, kWholeStackRows);
     const dim3 g(blocks), b(kTraverseBlock);
-#define VPT_LW(C, S, PL) hipLaunchKernelGGL((k_whole<C, S, PL>), g, b, lds, s, sc, P, ps, ctr, n_slots, dispatch_base, static_rounds, chunk_tiles)
-    if (plain && !count && !sc.strict_hits && sc.env_black) VPT_LW(false, false, true);
-    else if (sc.strict_hits) { if (count) VPT_LW(true, true, false); else VPT_LW(false, true, false); }
-    else if (count) VPT_LW(true, false, false);
-    else VPT_LW(false, false, false);
-#undef VPT_LW
+    // one launch site for the five instantiations (the argument marshalling is host code the library's size bound pays for five times otherwise)
+    void (*k)(DeviceScene, RenderParams, PathState, Counters*, uint32_t, uint32_t, uint32_t, uint32_t);
+    if (plain && !count && !sc.strict_hits && sc.env_black) k = k_whole<false, false, true>;
+    else if (sc.strict_hits) k = count ? k_whole<true, true, false> : k_whole<false, true, false>;
+    else k = count ? k_whole<true, false, false> : k_whole<false, false, false>;
+    hipLaunchKernelGGL(k, g, b, lds, s, sc, P, ps, ctr, n_slots, dispatch_base, static_rounds, chunk_tiles);
 }
 void launch_finish(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, const StreamState& ss, const uint32_t* queue,
                    StreamCounters* sctr, Counters* ctr, uint32_t parity) {
@@ -1452,14 +1473,14 @@ int finish_blocks_per_cu(const DeviceScene& sc) {
 }
 int whole_blocks_per_cu(const DeviceScene& sc, bool plain) {
     int nb = 0;
-    const size_t lds = traverse_lds_bytes(sc, true);
+    const size_t lds = traverse_lds_bytes(sc, true, kWholeStackRows);
     if (plain) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_whole<false, false, true>, kTraverseBlock, lds);
     else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_whole<false, false, false>, kTraverseBlock, lds);
     return nb > 0 ? nb : 1;
 }
 int bounce_blocks_per_cu(bool lds_scene, const DeviceScene& sc, bool plain) {
     int nb = 0;
-    size_t lds = traverse_lds_bytes(sc, lds_scene);
+    size_t lds = traverse_lds_bytes(sc, lds_scene, kStackDepth);
     if (lds_scene && plain) {   // the smaller of the two instantiations a batch launches
         int a = 0, b = 0;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_bounce<true, false, true, false, false, true>, kTraverseBlock, lds);
@@ -1479,15 +1500,15 @@ void launch_prepare(hipStream_t s, Counters* ctr, uint32_t parity) { hipLaunchKe
 void launch_fold(hipStream_t s, Counters* ctr) { hipLaunchKernelGGL(k_fold, dim3(1), dim3(1), 0, s, ctr); }
 #endif
 
-size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene) {
-    size_t b = (size_t)kStackDepth * kTraverseBlock * 4;
+size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene, int stack_rows) {
+    size_t b = (size_t)stack_rows * kTraverseBlock * 4;
     if (lds_scene) b += (size_t)sc.node_count * sizeof(BvhNodeWide) + (size_t)sc.tri_count * sizeof(BvhTri);
     return b;
 }
 #if VPT_LAB
 void launch_extend(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, const DeviceScene& sc, const PathState& ps,
                    const uint32_t* queue, Counters* ctr, uint32_t parity) {
-    size_t lds = traverse_lds_bytes(sc, lds_scene);
+    size_t lds = traverse_lds_bytes(sc, lds_scene, kStackDepth);
     if (lds_scene) {
         if (count) { if (sc.strict_hits) hipLaunchKernelGGL((k_extend<true, true, true>), dim3(blocks), dim3(kTraverseBlock), lds, s, sc, ps, queue, ctr, parity); else hipLaunchKernelGGL((k_extend<true, true, false>), dim3(blocks), dim3(kTraverseBlock), lds, s, sc, ps, queue, ctr, parity); }
         else { if (sc.strict_hits) hipLaunchKernelGGL((k_extend<true, false, true>), dim3(blocks), dim3(kTraverseBlock), lds, s, sc, ps, queue, ctr, parity); else hipLaunchKernelGGL((k_extend<true, false, false>), dim3(blocks), dim3(kTraverseBlock), lds, s, sc, ps, queue, ctr, parity); }
@@ -1498,7 +1519,7 @@ void launch_extend(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, c
 }
 void launch_connect(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, const DeviceScene& sc, const RenderParams& P,
                     const PathState& ps, const uint32_t* cqueue, Counters* ctr, uint32_t parity) {
-    size_t lds = traverse_lds_bytes(sc, lds_scene) + kConnectScratch;
+    size_t lds = traverse_lds_bytes(sc, lds_scene, kStackDepth) + kConnectScratch;
     if (lds_scene) {
         if (count) { if (sc.strict_hits) hipLaunchKernelGGL((k_connect<true, true, true>), dim3(blocks), dim3(kTraverseBlock), lds, s, sc, P, ps, cqueue, ctr, parity); else hipLaunchKernelGGL((k_connect<true, true, false>), dim3(blocks), dim3(kTraverseBlock), lds, s, sc, P, ps, cqueue, ctr, parity); }
         else { if (sc.strict_hits) hipLaunchKernelGGL((k_connect<true, false, true>), dim3(blocks), dim3(kTraverseBlock), lds, s, sc, P, ps, cqueue, ctr, parity); else hipLaunchKernelGGL((k_connect<true, false, false>), dim3(blocks), dim3(kTraverseBlock), lds, s, sc, P, ps, cqueue, ctr, parity); }
@@ -1523,11 +1544,11 @@ void launch_scatter_rows(hipStream_t s, const float* gathered, float* full, uint
     hipLaunchKernelGGL(k_scatter_rows, dim3(cdiv(w * h, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(gathered),
                        reinterpret_cast<float4*>(full), w, h, shard_count, stride_px);
 }
-size_t stack_overflow_bytes(uint32_t blocks) { return (size_t)blocks * kTraverseBlock * kStackOverflow * 4; }
+size_t stack_overflow_bytes(uint32_t blocks) { return (size_t)blocks * kTraverseBlock * kOverflowStride * 4; }   // (traverse.hpp: the longest per-thread region of any kernel)
 #if VPT_LAB
 int traverse_blocks_per_cu(bool lds_scene, const DeviceScene& sc) {
     int nb = 0;
-    size_t lds = traverse_lds_bytes(sc, lds_scene) + kConnectScratch;
+    size_t lds = traverse_lds_bytes(sc, lds_scene, kStackDepth) + kConnectScratch;
     if (lds_scene) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_connect<true, false, false>, kTraverseBlock, lds);
     else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_connect<false, false, false>, kTraverseBlock, lds);
     return nb > 0 ? nb : 1;

@@ -21,6 +21,9 @@ namespace vpt {
 constexpr int kStackDepth = 14;      // LDS entries per lane
 constexpr int kStackOverflow = 82;   // global entries per lane: 3 pushes per level x binary depth bound 30, minus the LDS part
 constexpr int kTraverseBlock = 256;
+// The whole-path kernel (kernels_path.hip k_whole) keeps fewer rows in LDS: a tree that rides in LDS is at most 3 KB (the Cornell box: three
+// nodes, never more than 6 entries deep), and the 8 KB it gives up hold the waves' buffers of fresh camera rays.
+constexpr int kWholeStackRows = 6;
 
 struct HitRec {
     float t, u, v;
@@ -32,24 +35,36 @@ struct TravStats {
     uint32_t nodes, tris;
 };
 
-struct TravStack {
+// ROWS: the LDS entries per lane.  Every kernel but the whole-path one keeps kStackDepth; what a stack holds in all — LDS rows plus
+// the per-thread overflow region — is kStackDepth + kStackOverflow whatever ROWS is (a shorter LDS part spills earlier, not less deep).
+template <int ROWS>
+struct TravStackT {
+    static constexpr int kRows = ROWS;
+    static constexpr int kOverflow = kStackDepth + kStackOverflow - ROWS;   // global entries per lane
     uint32_t* lds;    // this lane's column: entry k at lds[k * kTraverseBlock]
     uint32_t* glob;   // this thread's overflow region
     int sp;
     __device__ inline void push(uint32_t v) {
-        if (sp < kStackDepth) lds[sp * kTraverseBlock] = v;
-        else if (sp < kStackDepth + kStackOverflow) glob[sp - kStackDepth] = v;
+        if (sp < ROWS) lds[sp * kTraverseBlock] = v;
+        else if (sp < ROWS + kOverflow) glob[sp - ROWS] = v;
         sp++;
     }
     __device__ inline uint32_t pop() {
         sp--;
-        return sp < kStackDepth ? lds[sp * kTraverseBlock] : glob[sp - kStackDepth];
+        return sp < ROWS ? lds[sp * kTraverseBlock] : glob[sp - ROWS];
     }
 };
-__device__ inline TravStack make_stack(unsigned char* smem, uint32_t* overflow) {
-    TravStack s;
+using TravStack = TravStackT<kStackDepth>;
+// Words of the overflow region per resident thread: every kernel addresses the one region with its own stride — kStackOverflow (the trace
+// kernels: 2 x kStackOverflow on half as many blocks) or TravStackT<ROWS>::kOverflow — and the host sizes it by the longest (stack_overflow_bytes).
+constexpr int kOverflowStride = TravStackT<kWholeStackRows>::kOverflow > kStackOverflow ? TravStackT<kWholeStackRows>::kOverflow : kStackOverflow;
+static_assert(kOverflowStride >= TravStackT<kStackDepth>::kOverflow && kOverflowStride >= TravStackT<kWholeStackRows>::kOverflow && kOverflowStride >= kStackOverflow,
+              "a kernel's overflow stride is longer than the region the host allocates per thread");
+template <int ROWS = kStackDepth>
+__device__ inline TravStackT<ROWS> make_stack(unsigned char* smem, uint32_t* overflow) {
+    TravStackT<ROWS> s;
     s.lds = reinterpret_cast<uint32_t*>(smem) + threadIdx.x;
-    s.glob = overflow + (size_t)(blockIdx.x * blockDim.x + threadIdx.x) * kStackOverflow;
+    s.glob = overflow + (size_t)(blockIdx.x * blockDim.x + threadIdx.x) * TravStackT<ROWS>::kOverflow;
     s.sp = 0;
     return s;
 }
@@ -201,8 +216,8 @@ __device__ inline void cswap(float& ta, int& ca, float& tb, int& cb) {
 }
 
 // One closest-hit search (tmin < t < tmax; ties -> smaller global triangle id) that ignores triangles ex0 / ex1.
-template <bool COUNT, bool STRICT, class Src>
-__device__ inline bool trace_closest_pass(const Src& src, V3 o, V3 d, float tmin, float tmax, TravStack stack, HitRec& best, TravStats& st,
+template <bool COUNT, bool STRICT, class Src, class Stack>
+__device__ inline bool trace_closest_pass(const Src& src, V3 o, V3 d, float tmin, float tmax, Stack stack, HitRec& best, TravStats& st,
                                           uint32_t ex0, uint32_t ex1) {
     best.t = tmax; best.u = 0.0f; best.v = 0.0f; best.prim = 0xffffffffu; best.inst = 0xffffffffu; best.gid = 0xffffffffu; best.slot = 0;
     bool found = false;
@@ -266,8 +281,8 @@ __device__ inline bool slot_hit_is_local(const Src& src, int slot, V3 o, V3 d, f
 // and a local hit closer than the final winner is never pruned (boxes contain the triangle boxes).
 // The path kernels are instantiated twice (STRICT template flag): the default instantiation sees strict == false as a
 // compile-time constant and carries none of this code (the fused bounce kernel is instruction-cache sensitive).
-template <bool COUNT, class Src>
-__device__ inline bool trace_closest_strict(const Src& src, V3 o, V3 d, float tmin, float tmax, TravStack stack, HitRec& best, TravStats& st) {
+template <bool COUNT, class Src, class Stack>
+__device__ inline bool trace_closest_strict(const Src& src, V3 o, V3 d, float tmin, float tmax, Stack stack, HitRec& best, TravStats& st) {
     uint32_t ex0 = 0xffffffffu, ex1 = 0xffffffffu;
     while (true) {
         if (!trace_closest_pass<COUNT, true>(src, o, d, tmin, tmax, stack, best, st, ex0, ex1)) return false;
@@ -275,8 +290,8 @@ __device__ inline bool trace_closest_strict(const Src& src, V3 o, V3 d, float tm
         ex1 = ex0; ex0 = best.gid;
     }
 }
-template <bool COUNT, class Src>
-__device__ inline bool trace_closest(const Src& src, V3 o, V3 d, float tmin, float tmax, TravStack stack, HitRec& best, TravStats& st) {
+template <bool COUNT, class Src, class Stack>
+__device__ inline bool trace_closest(const Src& src, V3 o, V3 d, float tmin, float tmax, Stack stack, HitRec& best, TravStats& st) {
     if (!src.strict) return trace_closest_pass<COUNT, false>(src, o, d, tmin, tmax, stack, best, st, 0xffffffffu, 0xffffffffu);  // default: the unguarded winner
     return trace_closest_strict<COUNT>(src, o, d, tmin, tmax, stack, best, st);
 }
@@ -291,8 +306,8 @@ __device__ inline bool trace_closest(const Src& src, V3 o, V3 d, float tmin, flo
 // The search stops at the first such triangle and never looks beyond t_e, so it visits far fewer nodes than a
 // closest-hit traversal.  LIGHT = false: (a); LIGHT = true: (b) with `t_e`, `expect`.
 // One any-hit search ignoring triangles ex0 / ex1; reports the triangle that stopped it (cand_slot, cand_t, cand_gid).
-template <bool COUNT, bool LIGHT, bool STRICT, class Src>
-__device__ inline bool trace_occluded_pass(const Src& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, TravStack stack,
+template <bool COUNT, bool LIGHT, bool STRICT, class Src, class Stack>
+__device__ inline bool trace_occluded_pass(const Src& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, Stack stack,
                                            TravStats& st, uint32_t ex0, uint32_t ex1, int& cand_slot, float& cand_t, uint32_t& cand_gid) {
     const float tlimit = LIGHT ? t_e : tmax;
     const auto slab = make_slab<STRICT>(src, o, d);
@@ -335,8 +350,8 @@ __device__ inline bool trace_occluded_pass(const Src& src, V3 o, V3 d, float tmi
 }
 
 // Any-hit search over LOCAL hits only: the triangle that stops a pass is validated afterwards (see trace_closest).
-template <bool COUNT, bool LIGHT, class Src>
-__device__ inline bool trace_occluded_strict(const Src& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, TravStack stack,
+template <bool COUNT, bool LIGHT, class Src, class Stack>
+__device__ inline bool trace_occluded_strict(const Src& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, Stack stack,
                                                    TravStats& st) {
     int slot = 0; float t = 0.0f; uint32_t gid = 0xffffffffu;
     uint32_t ex0 = 0xffffffffu, ex1 = 0xffffffffu;
@@ -346,8 +361,8 @@ __device__ inline bool trace_occluded_strict(const Src& src, V3 o, V3 d, float t
         ex1 = ex0; ex0 = gid;
     }
 }
-template <bool COUNT, bool LIGHT, class Src>
-__device__ inline bool trace_occluded(const Src& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, TravStack stack,
+template <bool COUNT, bool LIGHT, class Src, class Stack>
+__device__ inline bool trace_occluded(const Src& src, V3 o, V3 d, float tmin, float tmax, float t_e, uint32_t expect, Stack stack,
                                       TravStats& st) {
     int slot = 0; float t = 0.0f; uint32_t gid = 0xffffffffu;
     if (!src.strict) return trace_occluded_pass<COUNT, LIGHT, false>(src, o, d, tmin, tmax, t_e, expect, stack, st, 0xffffffffu, 0xffffffffu, slot, t, gid);
@@ -356,8 +371,8 @@ __device__ inline bool trace_occluded(const Src& src, V3 o, V3 d, float tmin, fl
 
 // (b) in full: is the closest hit of the ray the triangle with global id `expect`?  `slot` is that triangle's
 // position in the leaf-ordered triangle array.
-template <bool COUNT, class Src>
-__device__ inline bool closest_is(const Src& src, V3 o, V3 d, float tmin, float tmax, uint32_t expect, uint32_t slot, TravStack stack,
+template <bool COUNT, class Src, class Stack>
+__device__ inline bool closest_is(const Src& src, V3 o, V3 d, float tmin, float tmax, uint32_t expect, uint32_t slot, Stack stack,
                                   TravStats& st) {
     float4 a, b, c;
     src.tri((int)slot, a, b, c);
