@@ -299,6 +299,7 @@ typedef struct vpt_stats {
     uint64_t finish_paths;
     uint64_t finish_closest_rays;
     uint64_t finish_shadow_rays;
+    double set_environment_ms; /* wall time of the last vpt_set_environment (alias table and pdf on the host, upload); 0 before the first */
 } vpt_stats;
 
 typedef struct vpt_ctx vpt_ctx;
@@ -319,6 +320,16 @@ int vpt_set_scene(vpt_ctx* ctx, const vpt_scene_desc* scene);
  * if emission changed, resets accumulation. */
 int vpt_set_material(vpt_ctx* ctx, uint32_t index, const vpt_material* material);
 int vpt_get_material(const vpt_ctx* ctx, uint32_t index, vpt_material* out);
+/* PathTracer::SetEnvMapFilepath (PathTracer.h:154) = LoadEnvironmentMap (PathTracer.cpp:1137-1332) with the .hdr already decoded by the
+ * caller: replaces the environment map of the installed scene and nothing else.  env_rgba is what vpt_scene_desc.env_rgba is (RGBA32F,
+ * alpha ignored, borrowed for the call); the importance, alias table and pdf are derived as vpt_set_scene derives them, so the context is
+ * the one vpt_set_scene would have produced from the same description with this environment and every later image is bit-identical to
+ * that context's.  The BVH, the pools, the derived tables, materials edited since, volumes, atmosphere, camera and parameters stay as
+ * they are (no BLAS / TLAS work upstream either); vpt_stats.set_scene_ms / bvh_build_ms keep their values and set_environment_ms takes
+ * this call's.  Waits for batches in flight.  VPT_ERR_NO_SCENE before the first vpt_set_scene, VPT_ERR_INVALID_ARGUMENT for a NULL map
+ * or a zero dimension, VPT_ERR_LIMIT for 2^32 texels or more; a rejected or failed call leaves the previous environment installed.
+ * Resets accumulation. */
+int vpt_set_environment(vpt_ctx* ctx, const float* env_rgba, uint32_t env_width, uint32_t env_height);
 /* ---- participating media: homogeneous box volumes ---------------------------------
  * PathTracer::Volume / VolumeGPU (PathTracer.h:36-74, 341-400) as the shaders read it (Volume.slang:19-52).
  * corner_min / corner_max are the WORLD-space box, i.e. Position + Corner * Scale already applied

@@ -145,6 +145,14 @@ class PathTracer:
         _check(self.lib, self.ctx, self.lib.vpt_get_material(self.ctx, index, C.byref(m)), "vpt_get_material")
         return m
 
+    def set_environment(self, env):
+        """SetEnvMapFilepath with the .hdr already decoded (vpt_set_environment): float32 [h, w, 4], alpha ignored.  Replaces the
+        environment of the installed scene only: no BVH build, no geometry upload."""
+        env = np.ascontiguousarray(env, np.float32)
+        if env.ndim != 3 or env.shape[2] != 4:
+            raise ValueError("environment must be [h, w, 4], got %r" % (env.shape,))
+        _check(self.lib, self.ctx, self.lib.vpt_set_environment(self.ctx, env.ctypes.data, env.shape[1], env.shape[0]), "vpt_set_environment")
+
     def resize(self, w, h):
         _check(self.lib, self.ctx, self.lib.vpt_resize(self.ctx, w, h), "vpt_resize")
         self.width, self.height = w, h

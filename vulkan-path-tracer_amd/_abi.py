@@ -181,6 +181,7 @@ class Stats(C.Structure):
         ("frames_allocated", C.c_uint32), ("resident_frames", C.c_uint32), ("reserved0", C.c_uint32), ("graph_launches", C.c_uint32), ("stack_spills", C.c_uint64 * 2),
         ("set_scene_ms", C.c_double), ("bvh_build_ms", C.c_double),
         ("finish_paths", C.c_uint64), ("finish_closest_rays", C.c_uint64), ("finish_shadow_rays", C.c_uint64),
+        ("set_environment_ms", C.c_double),
     ]
 
 
@@ -206,6 +207,7 @@ PROTOTYPES = {
     "vpt_set_scene": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "vpt_set_material": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Material)]),
     "vpt_get_material": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Material)]),
+    "vpt_set_environment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "vpt_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vpt_default_atmosphere": (None, [C.POINTER(Atmosphere)]),
     "vpt_set_atmosphere": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1,4 +1,4 @@
-// scene_prep.hpp — everything vpt_set_scene / vpt_set_material decide and compute on the host before a byte reaches the device: the checks
+// scene_prep.hpp — everything vpt_set_scene / vpt_set_material / vpt_set_environment decide and compute on the host before a byte reaches the device: the checks
 // of a scene description, the pooled and flattened geometry, the texel pool, the environment's alias table and pdf, the emissive-mesh
 // list, and the predicates the grids are picked by (host arithmetic of PathTracer.cpp restated).  Plain C++ on plain values, no context and
 // no HIP call: vpt_api.hip uploads what this prepares, and tests/test_scene_prep_cpu.py holds every rejection to its code and message and
@@ -76,6 +76,15 @@ inline Verdict check(const vpt_scene_desc& sd) {
     return kAccepted;
 }
 
+// Every reason vpt_set_environment rejects a map for, in the order it reports them (vpt_set_scene's own checks of a description's
+// environment are in check() above and stay as they are).
+inline Verdict check_environment(const float* rgba, uint32_t w, uint32_t h) {
+    if (!rgba || w == 0 || h == 0) return {VPT_ERR_INVALID_ARGUMENT, "incomplete environment map"};
+    // the alias table's entries and sample_env's texel index are 32-bit (shading.hpp sample_env: size = w * h)
+    if ((uint64_t)w * h > 0xffffffffull) return {VPT_ERR_LIMIT, "environment map of 2^32 texels or more"};
+    return kAccepted;
+}
+
 // LoadEnvironmentMap, PathTracer.cpp:1161-1296: per-texel importance = solid angle * max(rgb), alias
 // table (Vose-style pairing with the reference's pre-increment partition quirk), pdf into alpha.
 inline void env_tables(const float* rgba, uint32_t w, uint32_t h, std::vector<float>& env, std::vector<AliasEntry>& alias) {
@@ -113,6 +122,12 @@ inline void env_tables(const float* rgba, uint32_t w, uint32_t h, std::vector<fl
         float m = std::max(env[i * 4], std::max(env[i * 4 + 1], env[i * 4 + 2]));
         env[i * 4 + 3] = (sum == 0.0f) ? 0.0f : m / sum;
     }
+}
+
+// Every float of the finished table (pdf included) is exactly 0: DeviceScene::env_black, and one of the conditions of plain() below.
+inline bool env_is_black(const std::vector<float>& env) {
+    for (size_t i = 0; i < env.size(); i++) if (env[i] != 0.0f) return false;
+    return true;
 }
 
 // Emissive-mesh list, PathTracer.cpp:449-469 (and SetMaterial's rebuild, 712-794: same resulting order
@@ -237,7 +252,7 @@ inline HostScene prepare(const vpt_scene_desc& sd) {
     }
     // ---- environment + tables
     env_tables(sd.env_rgba, sd.env_width, sd.env_height, s.env, s.alias);
-    for (size_t i = 0; i < s.env.size(); i++) if (s.env[i] != 0.0f) { s.env_black = false; break; }
+    s.env_black = env_is_black(s.env);
     return s;
 }
 

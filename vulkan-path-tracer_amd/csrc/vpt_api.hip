@@ -176,7 +176,7 @@ struct vpt_ctx {
     unsigned long long* d_spill_count = nullptr;
     bool spill_dirty = true;         // traversal kernels have run since the spill regions were last counted (vpt_get_stats counts lazily)
     uint64_t spill_cached[2] = {0, 0};
-    double set_scene_ms = 0.0, bvh_build_ms = 0.0;
+    double set_scene_ms = 0.0, bvh_build_ms = 0.0, set_environment_ms = 0.0;
 
     int shade_media_blocks = 768, media_tail_blocks = 768;
     uint32_t class_present = 0x1fu;   // shade classes some instance of the scene belongs to (bit kShadeMiss always set): the others get no launch
@@ -959,6 +959,11 @@ int drain(vpt_ctx* c) {
     HIPCHK(c, hipGetLastError());
     return VPT_OK;
 }
+// What every entry that replaces something batches in flight read begins with: the context's device current, nothing in flight.
+int quiesce(vpt_ctx* c) {
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return drain(c);
+}
 // A whole batch as a fixed schedule: bounce 0 (or the camera rays) and `bounces_total` bounces in all; the guarded resolve is the caller's.
 int enqueue_fixed(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, uint32_t dispatch_base, uint32_t bounces_total, Grids grids, BatchState& b) {
     int rc = batch_begin(c, L, sd, frames, dispatch_base, grids, b);
@@ -1098,6 +1103,24 @@ int ensure_post_buffers(vpt_ctx* c) {
 struct SceneBvh {
     std::vector<BvhNode> nodes; std::vector<BvhNodeWide> wide; std::vector<BvhTri> leaf_tris; int depth = 0;
 };
+// The environment's tables (scene_prep.hpp env_tables) on the device and DeviceScene's fields for them: both tables or, after a failure,
+// neither, with DeviceScene as it was.  Whatever DeviceScene pointed to before is the caller's to free.
+int upload_environment(vpt_ctx* c, const std::vector<float>& env, const std::vector<AliasEntry>& alias, uint32_t w, uint32_t h, bool black) {
+    DeviceScene& D = c->dsc;
+    const size_t held = c->scene_allocs.size();
+    const float* e = nullptr;
+    const AliasEntry* a = nullptr;
+    int rc = upload(c, env, &e);
+    if (rc == VPT_OK) rc = upload(c, alias, &a);
+    if (rc) {
+        while (c->scene_allocs.size() > held) { (void)hipFree(c->scene_allocs.back()); c->scene_allocs.pop_back(); }
+        return rc;
+    }
+    D.env = e; D.alias = a;
+    D.env_w = w; D.env_h = h;
+    D.env_black = black ? 1u : 0u;
+    return VPT_OK;
+}
 // Uploads a prepared scene and its tree (the previous scene's tables are gone: free_scene), and takes over the host copies later calls
 // work from (vpt_set_material, vpt_get_stats, the trace lab).
 int upload_scene(vpt_ctx* c, const vpt_scene_desc& sd, scene::HostScene& hs, const SceneBvh& bvh) {
@@ -1130,10 +1153,7 @@ int upload_scene(vpt_ctx* c, const vpt_scene_desc& sd, scene::HostScene& hs, con
     if ((rc = alloc_table(c, 8 * std::max<size_t>(1, n_tris), &D.tri_shade, &W.tri_shade))) return rc;   // 8 float4, one 128-byte line, per triangle
     if ((rc = alloc_table(c, n_inst, &D.lights))) return rc;
     if ((rc = alloc_table(c, n_inst, &D.inst_class, &W.inst_class))) return rc;
-    if ((rc = upload(c, hs.env, &D.env))) return rc;
-    if ((rc = upload(c, hs.alias, &D.alias))) return rc;
-    D.env_w = sd.env_width; D.env_h = sd.env_height;
-    D.env_black = hs.env_black ? 1u : 0u;
+    if ((rc = upload_environment(c, hs.env, hs.alias, sd.env_width, sd.env_height, hs.env_black))) return rc;
     if ((rc = upload(c, sd.lut_reflection, 64 * 64 * 32, &D.lut_r))) return rc;
     if ((rc = upload(c, sd.lut_refraction_outside, 128 * 128 * 32, &D.lut_o))) return rc;
     if ((rc = upload(c, sd.lut_refraction_inside, 128 * 128 * 32, &D.lut_i))) return rc;
@@ -1242,8 +1262,7 @@ int vpt_set_scene(vpt_ctx* c, const vpt_scene_desc* sd) {
     // a rejected description leaves the current scene untouched: everything that can refuse one is in scene::check, and what follows fails only on the device
     const scene::Verdict verdict = scene::check(*sd);
     if (verdict.code) return fail(c, verdict.code, verdict.msg);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     const auto t_scene0 = std::chrono::steady_clock::now();
     // ---- on the host: the tables and the tree
     scene::HostScene hs = scene::prepare(*sd);
@@ -1281,8 +1300,7 @@ int vpt_set_material(vpt_ctx* c, uint32_t index, const vpt_material* m) {
     if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
     if (index >= c->materials.size()) return fail(c, VPT_ERR_INVALID_ARGUMENT, "material index out of range");
     if (!scene::material_textures_ok(*m, c->texture_count)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "material texture index out of range");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }   // batches in flight read the tables patched below
+    { int rd = quiesce(c); if (rd) return rd; }   // batches in flight read the tables patched below
     c->state_gen++;
     const vpt_material& old = c->materials[index];
     bool emissive_changed = old.emissive_color[0] != m->emissive_color[0] || old.emissive_color[1] != m->emissive_color[1] || old.emissive_color[2] != m->emissive_color[2];
@@ -1292,6 +1310,31 @@ int vpt_set_material(vpt_ctx* c, uint32_t index, const vpt_material* m) {
     { int rc2 = refresh_material_tables(c); if (rc2) return rc2; }
     update_depth_bounded(c);
     reset_accum(c);
+    return VPT_OK;
+}
+int vpt_set_environment(vpt_ctx* c, const float* env_rgba, uint32_t env_width, uint32_t env_height) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
+    const scene::Verdict verdict = scene::check_environment(env_rgba, env_width, env_height);
+    if (verdict.code) return fail(c, verdict.code, verdict.msg);
+    { int rd = quiesce(c); if (rd) return rd; }   // batches in flight read the tables replaced below
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<float> env;
+    std::vector<AliasEntry> alias;
+    scene::env_tables(env_rgba, env_width, env_height, env, alias);
+    // the new tables are on the device before the old ones go: a failure here leaves the previous environment installed
+    const void* old_env = c->dsc.env;
+    const void* old_alias = c->dsc.alias;
+    int rc = upload_environment(c, env, alias, env_width, env_height, scene::env_is_black(env));
+    if (rc) return rc;
+    for (size_t i = 0; i < c->scene_allocs.size();) {   // (the order of scene_allocs means nothing: free_scene frees them all)
+        void*& p = c->scene_allocs[i];
+        if (p == old_env || p == old_alias) { (void)hipFree(p); p = c->scene_allocs.back(); c->scene_allocs.pop_back(); } else i++;
+    }
+    c->state_gen++;            // a captured batch holds the old tables' addresses
+    update_depth_bounded(c);   // env_black is one of the conditions of the PLAIN instantiation
+    reset_accum(c);
+    c->set_environment_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return VPT_OK;
 }
 int vpt_get_material(const vpt_ctx* c, uint32_t index, vpt_material* out) {
@@ -1344,8 +1387,7 @@ int vpt_set_volumes(vpt_ctx* c, const vpt_volume* v, uint32_t count) {
         if (v[i].has_temperature_data && v[i].density_data_index < 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "has_temperature_data needs a density grid");
         if (!(v[i].density > 0.0f)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "volume density must be > 0");  // -log(u)/0 (Sampler.slang:427)
     }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->state_gen++;
     if (c->d_volumes) { (void)hipFree(c->d_volumes); c->d_volumes = nullptr; }
@@ -1377,8 +1419,7 @@ int vpt_add_density_grid(vpt_ctx* c, uint32_t dx, uint32_t dy, uint32_t dz, cons
                 const uint32_t bi = ((x * 32u) / dx) + ((y * 32u) / dy) * 32u + ((z * 32u) / dz) * 1024u;
                 if (block_max[bi] < dens) block_max[bi] = dens;
             }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->state_gen++;
     DensityGrid g{};
@@ -1398,8 +1439,7 @@ int vpt_add_density_grid(vpt_ctx* c, uint32_t dx, uint32_t dy, uint32_t dz, cons
 int vpt_clear_density_grids(vpt_ctx* c) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
     for (const vpt_volume& v : c->volumes) if (v.density_data_index >= 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "a volume still references a density grid");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->state_gen++;
     for (DensityGrid& g : c->grids) { (void)hipFree((void*)g.values); (void)hipFree((void*)g.block_max); }
@@ -1492,8 +1532,7 @@ int vpt_render(vpt_ctx* c, uint32_t dispatches, int* done) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "vpt_render before vpt_set_scene");
     if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     if (done) *done = 0;
     uint32_t left = dispatches;
     while (left > 0) {
@@ -1602,8 +1641,7 @@ int vpt_get_radiance_device(vpt_ctx* c, void* dst) {
     if (!c || !dst) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
     if (c->P.shard_count > 1 && !c->full_valid) return fail(c, VPT_ERR_INVALID_ARGUMENT, "sharded context: call vpt_assemble_shards first");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     HIPCHK(c, hipMemcpyAsync(dst, whole_image(c), (size_t)c->P.width * c->P.height * 16, hipMemcpyDeviceToDevice, c->main.stream));
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return VPT_OK;
@@ -1612,16 +1650,14 @@ int vpt_get_radiance(vpt_ctx* c, float* dst) {
     if (!c || !dst) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
     if (c->P.shard_count > 1 && !c->full_valid) return fail(c, VPT_ERR_INVALID_ARGUMENT, "sharded context: call vpt_assemble_shards first");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     HIPCHK(c, hipMemcpy(dst, whole_image(c), (size_t)c->P.width * c->P.height * 16, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
 int vpt_set_radiance(vpt_ctx* c, const float* src, uint32_t frame_count) {
     if (!c || !src) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     const uint32_t W = c->P.width;
     if (c->P.shard_count == 1) {
         HIPCHK(c, hipMemcpy(c->image, src, (size_t)W * c->P.height * 16, hipMemcpyHostToDevice));
@@ -1645,8 +1681,7 @@ size_t vpt_shard_floats(const vpt_ctx* c) {
 int vpt_get_shard_device(vpt_ctx* c, void* dst) {
     if (!c || !dst) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     size_t bytes = (size_t)c->P.shard_pixels * 16, padded = vpt_shard_floats(c) * 4;
     HIPCHK(c, hipMemcpyAsync(dst, c->image, bytes, hipMemcpyDeviceToDevice, c->main.stream));
     if (padded > bytes) HIPCHK(c, hipMemsetAsync((char*)dst + bytes, 0, padded - bytes, c->main.stream));
@@ -1657,8 +1692,7 @@ int vpt_assemble_shards(vpt_ctx* c, const void* gathered, uint32_t shard_count) 
     if (!c || !gathered) return VPT_ERR_INVALID_ARGUMENT;
     if (shard_count != c->P.shard_count) return fail(c, VPT_ERR_INVALID_ARGUMENT, "shard_count mismatch");
     if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     float* dst = c->P.shard_count > 1 ? c->full_image : c->image;
     launch_scatter_rows(c->main.stream, (const float*)gathered, dst, c->P.width, c->P.height, shard_count, (uint32_t)(vpt_shard_floats(c) / 4));
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
@@ -1780,8 +1814,7 @@ const void* vpt_output_device(vpt_ctx* c) { return c ? c->post_out : nullptr; }
 int vpt_get_output(vpt_ctx* c, uint8_t* out8) {
     if (!c || !out8) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->post_out) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_get_output before the first post-process");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     HIPCHK(c, hipMemcpy(out8, c->post_out, (size_t)c->post_w * c->post_h * 4, hipMemcpyDeviceToHost));
     return VPT_OK;
@@ -1802,7 +1835,7 @@ int vpt_get_stats(vpt_ctx* c, vpt_stats* out) {
     s.frames_in_flight = batch_cap(c); s.shard_pixels = c->P.shard_pixels;   // (the largest batch the context renders at once with its current scene and parameters)
     s.build_flags = (c->sbvh ? VPT_BUILD_SBVH : 0u) | (c->cfg.build_flags & (VPT_BUILD_GENERAL_KERNELS | VPT_BUILD_STREAMS_ONLY));
     s.frames_allocated = c->main.frames_alloc; s.resident_frames = c->main.resident_alloc;
-    s.set_scene_ms = c->set_scene_ms; s.bvh_build_ms = c->bvh_build_ms;
+    s.set_scene_ms = c->set_scene_ms; s.bvh_build_ms = c->bvh_build_ms; s.set_environment_ms = c->set_environment_ms;
     // what the traversal kernels have written into their spill regions: counted when something has run since the last count (the scan reads
     // ~0.4 GB: a host that asks for the statistics after every frame would otherwise pay 0.1-0.2 ms per call for a number that does not change)
     if (c->has_scene && c->main.spill && c->spill_dirty) {
@@ -1826,8 +1859,7 @@ int vpt_get_stats(vpt_ctx* c, vpt_stats* out) {
 }
 int vpt_reset_stats(vpt_ctx* c) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     c->stats = vpt_stats{};
     for (int k = 0; k < kLanes; k++)
         if (Lane* L = c->lane(k)) { HIPCHK(c, memset_now(L->stream, L->ctr, 0, sizeof(Counters))); memset(L->h_ctr, 0, sizeof(HostCounters)); }
@@ -1838,8 +1870,7 @@ int vpt_trace_rays(vpt_ctx* c, const vpt_ray* rays, uint32_t n, vpt_hit* hits) {
     if (!c || (n && (!rays || !hits))) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
     if (n == 0) return VPT_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     vpt_ray* dr = nullptr; vpt_hit* dh = nullptr;
     HIPCHK(c, hipMalloc((void**)&dr, (size_t)n * sizeof(vpt_ray)));
     if (hipMalloc((void**)&dh, (size_t)n * sizeof(vpt_hit)) != hipSuccess) { (void)hipFree(dr); return fail(c, VPT_ERR_OUT_OF_MEMORY, "hipMalloc hits"); }
@@ -1912,8 +1943,7 @@ int vpt_comm_gather_shards(vpt_ctx* c, int root) {
     if (!c->comm) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_comm_gather_shards before vpt_comm_init");
     if (root < 0 || root >= c->comm_world) return fail(c, VPT_ERR_INVALID_ARGUMENT, "root out of range");
     if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     const bool is_root = c->comm_rank == root;
     if (is_root) { int rc = ensure_gather_buf(c); if (rc) return rc; }
     // every rank contributes its rows padded to the largest shard (the image buffer is allocated at that size);
@@ -1990,8 +2020,7 @@ int vpt_multi_gather_shards(vpt_ctx* const* ctxs, uint32_t count, uint32_t root)
 #if VPT_LAB   // ---- the laboratory's entry points (include/vpt_lab.h): absent from the product library
 int vpt_lab_set(vpt_ctx* c, uint32_t key, uint32_t value) {
     if (!c || (value > 3u && key != VPT_LAB_WHOLE_FRAMES && key != VPT_LAB_WHOLE_SCHED)) return VPT_ERR_INVALID_ARGUMENT;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     if (key == VPT_LAB_LANES && value >= 1u) c->lab_lanes = value;
     else if (key == VPT_LAB_LANE_GRID && value >= 1u) c->lab_lane_grid = value;
     else if (key == VPT_LAB_TAIL_GRID && value >= 1u) c->lab_tail_grid = value;
@@ -2025,8 +2054,7 @@ int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t
     if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
     if (c->lds_scene) return fail(c, VPT_ERR_UNSUPPORTED, "the trace lab runs on scenes whose BVH lives in memory");
     if (c->lab_n == 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_lab_trace before vpt_lab_set_rays");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = drain(c); if (rd) return rd; }
+    { int rd = quiesce(c); if (rd) return rd; }
     if (variant == VPT_TRACE_VOTE4S && !c->dsc.nodes4s) {   // split-order experiment: the same binary tree collapsed pair-wise with order tables, over the same leaf-ordered triangles
         std::vector<BvhNode> n4, n4s; std::vector<BvhNodeWide> w4; std::vector<BvhTri> lt; int d = 0;
         BvhBuildOptions opt; opt.spatial_splits = c->sbvh; opt.nodes4s = &n4s;

@@ -235,7 +235,8 @@ void PathTracer::Push(bool resets) {
 void PathTracer::SetEnvironmentMap(const std::vector<float>& rgba, uint32_t width, uint32_t height) {
     if (rgba.size() != (size_t)width * height * 4 || width == 0 || height == 0) throw std::runtime_error("SetEnvironmentMap: bad size");
     m_Env = rgba; m_EnvW = width; m_EnvH = height;
-    if (m_Ctx) { UploadScene(); Check(vpt_set_camera(m_Ctx, m_CameraViewInverse.m, m_CameraProjectionInverse.m), "vpt_set_camera"); }
+    // with a scene installed only the environment's tables are replaced (LoadEnvironmentMap touches no BLAS / TLAS either); before SetScene the map waits for it
+    if (m_Ctx) Check(vpt_set_environment(m_Ctx, m_Env.data(), m_EnvW, m_EnvH), "vpt_set_environment");
     ResetPathTracing();
 }
 void PathTracer::SetEnvMapFilepath(const std::string& filePath) {  // PathTracer.cpp:1137-1164 (ImportTexture of an .hdr)

@@ -3,6 +3,7 @@
 //   vpt_render --scene S.gltf --luts lookup_tables.bin [--size WxH] [--spp N] [--depth D] [--seed K] [--split S]
 //              [--env-constant r,g,b] [--radiance out.f32] [--camera out.f32] [--ppm out.ppm] [--info] [--dump-scene out.bin]
 //              [--env-hdr sky.hdr] [--png out.png] [--atmosphere] [--sun altitude,azimuth]
+//              [--env-late]   apply --env-constant / --env-hdr after SetScene instead of before (the Editor's order of calls: the map is swapped on the installed scene)
 //              [--volume minx,miny,minz,maxx,maxy,maxz,density,g,r,g,b]... [--phase hg|draine|hg+draine]
 //              [--async]   one PathTraceAsync + PostProcessAsync per frame with a one-frame fence lag (the reference's Editor loop) instead of blocking batches
 //              [--async-step N]   dispatches per PathTraceAsync call (default 1)
@@ -40,7 +41,7 @@ int main(int argc, char** argv) {
     std::vector<PathTracer::Volume> volumes; int phase = 0; bool atmosphere = false; float sunAlt = 0.0f, sunAz = 0.0f;
     uint32_t lutSamples = 10000000u, lutTime = 0; UVec3 lutSize{0, 0, 0};
     uint32_t w = 0, h = 0, spp = 16, depth = 8, seed = 1, split = 1, gpus = 1; std::vector<int> devices;
-    bool async = false, rayQueries = true; uint32_t asyncStep = 1;
+    bool async = false, rayQueries = true, envLate = false; uint32_t asyncStep = 1;
     bool info = false, selftest = false; float env[3] = {0, 0, 0}; bool haveEnv = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -63,6 +64,7 @@ int main(int argc, char** argv) {
         else if (a == "--ppm") ppm = next();
         else if (a == "--png") png = next();                 // Editor::SaveToFile
         else if (a == "--env-hdr") envHdr = next();          // SetEnvMapFilepath
+        else if (a == "--env-late") envLate = true;
         else if (a == "--dump-env") dumpEnv = next();        // with --env-hdr: decoded RGBA32F (no device needed)
         else if (a == "--decode-image") decodeImage = next(); // with --dump-image: a PNG / JPEG texture as the importer decodes it, raw RGBA8 (no device needed)
         else if (a == "--dump-image") dumpImage = next();
@@ -187,10 +189,14 @@ int main(int argc, char** argv) {
         for (uint32_t k = 0; k < gpus; k++) shards.push_back(PathTracer::New(devices[k], k, gpus));
         for (PathTracer& pt : shards) {   // every shard holds a replica of the scene and the same settings
             pt.SetLookupTablePath(luts);
-            if (haveEnv) { std::vector<float> e(64 * 32 * 4, 0.0f); for (size_t i = 0; i < 64 * 32; i++) { e[i * 4] = env[0]; e[i * 4 + 1] = env[1]; e[i * 4 + 2] = env[2]; } pt.SetEnvironmentMap(e, 64, 32); }
+            auto applyEnv = [&]() {
+                if (haveEnv) { std::vector<float> e(64 * 32 * 4, 0.0f); for (size_t i = 0; i < 64 * 32; i++) { e[i * 4] = env[0]; e[i * 4 + 1] = env[1]; e[i * 4 + 2] = env[2]; } pt.SetEnvironmentMap(e, 64, 32); }
+                if (!envHdr.empty()) pt.SetEnvMapFilepath(envHdr);
+            };
+            if (!envLate) applyEnv();
             if (w && h) pt.ResizeImage(w, h);
-            if (!envHdr.empty()) pt.SetEnvMapFilepath(envHdr);
             pt.SetScene(scene);
+            if (envLate) applyEnv();
             if (w && h) {  // the window was resized: Editor.cpp:203-211 rebuilds the projection from the new aspect ratio
                 FlyCamera cam(inverse(pt.GetCameraViewInverse()), inverse(pt.GetCameraProjectionInverse()));
                 cam.SetAspectRatio((float)w / (float)h); cam.SetNearFar(0.1f, 100.0f);
