@@ -214,9 +214,9 @@ typedef struct vpt_config {
  * Per context, never read from the environment: two contexts of one process cannot silently build different trees. */
 #define VPT_BUILD_SBVH 1u
 /* Keep the general instantiation of the whole-path / fused per-bounce kernels even when the scene qualifies for the class-specialised one
- * (every texture 1x1 and a black environment: k_whole<PLAIN>, k_bounce<PLAIN>, kernels_path.hip).  Images are identical; this is the A/B switch of that choice. */
+ * (every texture 1x1 and a black environment: k_whole<PLAIN>, kernels_whole.hip; k_bounce<PLAIN>, kernels_bounce.hip).  Images are identical; this is the A/B switch of that choice. */
 #define VPT_BUILD_GENERAL_KERNELS 2u
-/* Streams pipeline: never hand the rest of a batch to the one-launch finisher (kernels_path.hip k_finish), i.e. run every bounce of every batch
+/* Streams pipeline: never hand the rest of a batch to the one-launch finisher (kernels_finish.hip k_finish), i.e. run every bounce of every batch
  * through the stream stages.  By default a small batch (<= 6M samples: a frame or two per call) goes there after three bounces and a large one once
  * the host sees fewer than 262,144 paths alive: seven dependent launches per bounce on a short queue cost more than the finisher's one launch of
  * persistent waves.  Images are identical; this is the A/B switch of that choice. */
@@ -231,7 +231,7 @@ typedef struct vpt_config {
                                        * one shade launch per class, the miss and plain ones specialised.  Bit-identical; measured
                                        * 10-14 % SLOWER than STAGED on the BASELINE scenes (profiles/REJECTED.md), so AUTO never picks it */
 #define VPT_PIPELINE_WHOLE 5u  /* ONE launch per batch: persistent waves run every path from its camera ray to its end, a lane whose path has ended takes
-                               * the batch's next sample (kernels_path.hip k_whole; the reference's own shape: one RayGen thread = one whole path).
+                               * the batch's next sample (kernels_whole.hip k_whole; the reference's own shape: one RayGen thread = one whole path).
                                * For scenes whose BVH rides in LDS, no media, samples_per_frame == 1, every sample resident — VPT_ERR_UNSUPPORTED
                                * otherwise.  Bit-identical.  AUTO takes it wherever it applies: measured faster than FUSED at every batch size
                                * (Cornell box 1080p: 8.3 vs 7.4 Gsamples/s at 226 frames per batch, 3.8 vs 2.4 at one; profiles/r04_whole_ab.json) */
@@ -294,7 +294,7 @@ typedef struct vpt_stats {
     uint64_t stack_spills[2];
     double set_scene_ms;       /* wall time of the last vpt_set_scene (validation, BVH build, uploads, derived tables) */
     double bvh_build_ms;       /* of which: the host-side BVH build (bvh_build.cpp; the reference builds BLAS / TLAS on the device, PathTracer.cpp:484-505) */
-    /* Streams pipeline, the one-launch finisher (kernels_path.hip k_finish, timed under VPT_K_BOUNCE): paths it took over from the streams, and the
+    /* Streams pipeline, the one-launch finisher (kernels_finish.hip k_finish, timed under VPT_K_BOUNCE): paths it took over from the streams, and the
      * closest-hit / shadow rays it traced — both also counted in closest_rays / shadow_rays above. */
     uint64_t finish_paths;
     uint64_t finish_closest_rays;

@@ -232,7 +232,7 @@ def test_fixed_stream_batches_are_replayed_from_a_graph(vpt, oracle, scenes):
 
 @pytest.mark.parametrize("name,depth", [("cornell_box_glass", 12), ("viking_room", 6)])
 def test_small_stream_batches_finish_in_one_launch_and_large_ones_at_their_tail(vpt, oracle, scenes, name, depth):
-    """k_finish (kernels_path.hip) behind blocking batches too: a small batch runs three bounces on the streams and ONE launch for the rest, whatever
+    """k_finish (kernels_finish.hip) behind blocking batches too: a small batch runs three bounces on the streams and ONE launch for the rest, whatever
     its depth (the class-sorted pipeline likewise); ray statistics as the oracle counts them.  (Large batches hand over once the host sees fewer than
     262,144 paths alive: the 1080p cases of test_gpu_configs.py.)"""
     sc = copy.deepcopy(scenes(name))

@@ -2,7 +2,7 @@
 vpt.PathTracer and an oracle.Oracle, and after every render step the images are equal bit for bit.  The host layer (vpt_api.hip) picks a
 schedule per batch from the context's history — whole-path launch, fused k_bounce, streams with regeneration, media streams, the k_finish
 tail; the path buffers' frames_alloc / resident_alloc; media_frames, class queues, captured graphs — and every other GPU test builds a fresh
-context per configuration.  Also the four instantiations of k_finish<COUNT, STRICT> (kernels_path.hip): image, ray statistics and visit
+context per configuration.  Also the four instantiations of k_finish<COUNT, STRICT> (kernels_finish.hip): image, ray statistics and visit
 counts against the oracle and against a twin context without the finisher (VPT_BUILD_STREAMS_ONLY)."""
 import copy
 

@@ -1,4 +1,4 @@
-"""VPT_PIPELINE_WHOLE (kernels_path.hip k_whole): a batch as ONE launch — persistent waves run every path from its camera ray to its
+"""VPT_PIPELINE_WHOLE (kernels_whole.hip k_whole): a batch as ONE launch — persistent waves run every path from its camera ray to its
 end, a lane whose path has ended takes the batch's next sample.  It is the reference's own shape (one RayGen thread = one whole
 path, RayGen.slang:66-114) and must give the oracle's image bit for bit, with the per-bounce pipeline's ray statistics."""
 import copy

@@ -1,4 +1,4 @@
-"""The whole-path kernel (kernels_path.hip k_whole) generates its camera rays a full tile at a time into a wave-private buffer and hands
+"""The whole-path kernel (kernels_whole.hip k_whole) generates its camera rays a full tile at a time into a wave-private buffer and hands
 them to free lanes from there (vulkan-path-tracer_amd/csrc/whole_refill.hpp; the host side: tests/test_whole_refill_cpu.py).  Which lane
 runs which sample cannot matter — seeds come from (pixel, frame), results go to the sample's own slot — so images and ray counts must be the
 oracle's, bit for bit, at every shape of batch the tile cursor and the buffer see: ragged rows, less than a tile, row shards, split screens,

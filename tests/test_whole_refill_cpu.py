@@ -1,4 +1,4 @@
-"""How the waves of the whole-path kernel (kernels_path.hip k_whole) come by their fresh samples, on the host: the tile cursor and the wave's buffer
+"""How the waves of the whole-path kernel (kernels_whole.hip k_whole) come by their fresh samples, on the host: the tile cursor and the wave's buffer
 of generated camera rays are vulkan-path-tracer_amd/csrc/whole_refill.hpp, and tests/tools/whole_refill_driver.cpp plays a grid of waves against it —
 seeded survivor masks between refills, a seeded order in which the waves meet the shared tile counter.  For every case:
   (a) every launch index in [0, n) is handed to a lane exactly once;

@@ -1,6 +1,6 @@
 """Builds variants/<name>.so: the product library with extra -D definitions (A/B builds for tests/tools/ab_variants.sh; variants/ is git-ignored
 but travels to the GPU box).  Objects that do not see the definition are shared with the product build.
-    python tests/tools/build_variant.py <name> [-DVPT_X=1 ...] [--sources vpt_api.hip,kernels_path.hip]   (default: every source is recompiled)"""
+    python tests/tools/build_variant.py <name> [-DVPT_X=1 ...] [--sources vpt_api.hip,kernels_whole.hip]   (default: every source is recompiled)"""
 import importlib, os, shutil, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -27,6 +27,6 @@ for src, p in procs:
         raise SystemExit("hipcc failed on %s:\n%s" % (src, out))
 os.makedirs(os.path.join(ROOT, "variants"), exist_ok=True)
 lib = os.path.join(ROOT, "variants", name + ".so")
-subprocess.check_call([B.hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib", "-Wl,--strip-all"])
+B.link(lib, objs)
 open(lib + ".id", "w").write(B.source_id(["-DVPT_LAB=0"] + defs) + "\n")   # not the product's id: counters collected on this build are never attributed to the product
 print(lib)

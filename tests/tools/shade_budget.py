@@ -5,15 +5,15 @@
 2. Compiles one tiny kernel per contract / shading function and counts its instructions: what one call costs.
 
     python tests/tools/shade_budget.py [--json out.json]
-    python tests/tools/shade_budget.py --fused        # the same breakdown for the fused per-bounce kernels (kernels_path.hip)
-    python tests/tools/shade_budget.py --whole        # ... and for the whole-path launch k_whole
+    python tests/tools/shade_budget.py --fused        # the same breakdown for the fused per-bounce kernels (kernels_bounce.hip)
+    python tests/tools/shade_budget.py --whole        # ... and for the whole-path launch k_whole (kernels_whole.hip)
 """
 import collections, importlib, json, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 _build = importlib.import_module("vulkan-path-tracer_amd._build")
 CSRC = os.path.join(ROOT, "vulkan-path-tracer_amd", "csrc")
-FLAGS = [f for f in _build.FLAGS if f not in ("-fPIC",)] + _build.EXTRA_FLAGS.get("kernels_stream.hip", [])   # (kernels_path.hip has the same per-file flags)
+FLAGS = [f for f in _build.FLAGS if f not in ("-fPIC",)] + _build.EXTRA_FLAGS.get("kernels_stream.hip", [])   # (kernels_bounce.hip and kernels_whole.hip have the same per-file flags)
 
 def asm(src, extra=()):
     out = tempfile.mktemp(suffix=".s")
@@ -57,7 +57,7 @@ def shade_kernel_by_function(src="kernels_stream.hip", symbol="_ZN3vpt14k_shade_
         total[kind] += 1
         if kind == "valu": by_line[cur] += 1
     ranges = {}
-    for f in ("vpt_fp32.h", "shading.hpp", "shade_core.hpp", "kernels_stream.hip", "kernels_path.hip", "traverse.hpp", "vote.hpp", "wave.hpp", "volume.hpp", "atmosphere.hpp"):
+    for f in ("vpt_fp32.h", "shading.hpp", "shade_core.hpp", "kernels_stream.hip", "kernels_bounce.hip", "kernels_whole.hip", "traverse.hpp", "vote.hpp", "wave.hpp", "volume.hpp", "atmosphere.hpp"):
         p = os.path.join(ROOT, "include", f) if f == "vpt_fp32.h" else os.path.join(CSRC, f)
         ranges[f] = function_ranges(p)
     by_fn = collections.Counter()
@@ -107,7 +107,7 @@ def micro_costs():
 if __name__ == "__main__":
     if "--fused" in sys.argv:   # the headline's two kernels: k_bounce<LDS scene> for bounces >= 1 and its FIRST variant (camera ray + bounce 0)
         for label, sym in (("k_bounce<LDS, bounce >= 1>", "_ZN3vpt8k_bounceILb1ELb0ELb0ELb0ELb0EEE"), ("k_bounce<LDS, FIRST>", "_ZN3vpt8k_bounceILb1ELb0ELb1ELb0ELb0EEE")):
-            total, by_fn = shade_kernel_by_function("kernels_path.hip", sym)
+            total, by_fn = shade_kernel_by_function("kernels_bounce.hip", sym)
             print("%s: %d VALU, %d SALU, %d memory instructions (static)\n" % (label, total["valu"], total["salu"], total["mem"]))
             print("| source function (innermost inlined) | VALU instructions | share |\n|---|---|---|")
             for (f, n), c in by_fn.most_common(16):
@@ -116,7 +116,7 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--whole" in sys.argv:   # the whole-path launch (round 4): scene-class and general instantiation
         for label, sym in (("k_whole<PLAIN>", "_ZN3vpt7k_wholeILb0ELb0ELb1EEE"), ("k_whole<general>", "_ZN3vpt7k_wholeILb0ELb0ELb0EEE")):
-            total, by_fn = shade_kernel_by_function("kernels_path.hip", sym)
+            total, by_fn = shade_kernel_by_function("kernels_whole.hip", sym)
             print("%s: %d VALU, %d SALU, %d memory instructions (static)\n" % (label, total["valu"], total["salu"], total["mem"]))
             print("| source function (innermost inlined) | VALU instructions | share |\n|---|---|---|")
             for (f, n), c in by_fn.most_common(24):

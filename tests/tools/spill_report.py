@@ -38,7 +38,7 @@ def report(src):
                 loc = x.split(";")[-1].strip().split(" @[")[0].replace("vulkan-path-tracer_amd/csrc/", "")
             if re.match(r"^\s+scratch_", x):
                 spills[("store " if "_store" in x else "load  ") + loc] += 1
-        rows.append({"kernel": re.sub(r"\(.*", "", names[n]).replace("void ", "").replace("vpt::", ""), "vgprs": get("; NumVgprs:"), "sgprs": get("; TotalNumSgprs:"), "occupancy": get("; Occupancy:"),
+        rows.append({"kernel": re.sub(r"\(.*", "", names[n].replace("(anonymous namespace)::", "")).replace("void ", "").replace("vpt::", ""), "vgprs": get("; NumVgprs:"), "sgprs": get("; TotalNumSgprs:"), "occupancy": get("; Occupancy:"),
                      "scratch_bytes": get("; ScratchSize:"), "valu": sum(1 for x in body if re.match(r"^\s+v_", x)), "salu": sum(1 for x in body if re.match(r"^\s+s_", x)),
                      "lane_ops": sum(1 for x in body if "v_readlane" in x or "v_writelane" in x), "scratch_instr": sum(spills.values()), "where": spills})
     return rows
@@ -47,7 +47,7 @@ def report(src):
 if __name__ == "__main__":
     everything = "--all" in sys.argv
     rows = []
-    for src in ("kernels_path.hip", "kernels_stream.hip", "kernels_trace.hip", "kernels_post.hip", "kernels_media.hip"):
+    for src in [f for f in B.SOURCES if re.fullmatch(r"kernels_\w+\.hip", f)]:
         rows += [dict(r, file=src) for r in report(src)]
     rows = [r for r in rows if everything or any(r["kernel"] == m or r["kernel"].startswith(m) for m in MAIN)]
     out = ["# Registers and scratch of the shipped kernels, from the compiler's output (`tests/tools/spill_report.py`, source id %s)" % B.source_id(), "",

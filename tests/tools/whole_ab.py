@@ -1,4 +1,4 @@
-"""Probe (not a pytest): the whole-path launch (VPT_PIPELINE_WHOLE, kernels_path.hip k_whole) against the per-bounce kernels
+"""Probe (not a pytest): the whole-path launch (VPT_PIPELINE_WHOLE, kernels_whole.hip k_whole) against the per-bounce kernels
 (VPT_PIPELINE_FUSED) on the Cornell box at 1920x1080, same box, same process, alternating.
   throughput   Msamples/s at 1 / 4 / 16 / 64 / AUTO-cap frames per batch (blocking vpt_render), depth 8; the glass variant at depth 12 (general kernel)
   latency      per-frame wall clock of the blocking pair and of the asynchronous pair with 1 / 2 / 3 frames in flight, lanes 1-3

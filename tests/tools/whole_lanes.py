@@ -1,4 +1,4 @@
-"""Probe (not a pytest): how 1-frame whole-path launches (kernels_path.hip k_whole) share the chip when frames are pipelined: tile schedule
+"""Probe (not a pytest): how 1-frame whole-path launches (kernels_whole.hip k_whole) share the chip when frames are pipelined: tile schedule
 (VPT_LAB_WHOLE_SCHED) x lanes x frames in flight, steady-state wall clock per frame of vpt_render_async(1) + vpt_postprocess_device on the Cornell box at
 1920x1080 depth 8; and the launch itself under HIP events at 1 / 2 / 4 frames per batch.  Writes gpurun_out/<dir>/whole_lanes.json.
     python tests/tools/whole_lanes.py [outdir]"""

@@ -1,5 +1,5 @@
 // Host driver of vulkan-path-tracer_amd/csrc/whole_refill.hpp for tests/test_whole_refill_cpu.py: a grid of modelled waves of the whole-path
-// kernel (kernels_path.hip k_whole) that share one tile counter.  The cursor and buffer arithmetic is the header's; wave_refill restates only
+// kernel (kernels_whole.hip k_whole) that share one tile counter.  The cursor and buffer arithmetic is the header's; wave_refill restates only
 // the order in which k_whole's refill step calls it, with the launch index standing in for the camera ray an entry holds.  Between refills a
 // seeded coin decides which lanes' paths survive (the shade and trace steps), and a seeded scheduler decides which wave runs next, so the
 // waves meet the counter in every order.  Built as a shared library and driven through ctypes.

@@ -1,5 +1,5 @@
-"""Probe (not a pytest): on how many lanes the whole-path kernel (kernels_path.hip k_whole) generates its camera rays.  Needs a library built with
--DVPT_DIAG_REFILL_LANES=1 in the product's place (tests/tools/build_variant.py refill_lanes -DVPT_DIAG_REFILL_LANES=1 --sources kernels_path.hip, copied over
+"""Probe (not a pytest): on how many lanes the whole-path kernel (kernels_whole.hip k_whole) generates its camera rays.  Needs a library built with
+-DVPT_DIAG_REFILL_LANES=1 in the product's place (tests/tools/build_variant.py refill_lanes -DVPT_DIAG_REFILL_LANES=1 --sources kernels_whole.hip, copied over
 libvpt_hip.so as tests/tools/ab_variants.sh does): that build counts, per wave, the passes that ran launch_pixel + camera_ray and the lanes that were live in
 them, and reports the two sums where a counting context reports its closest-hit node visits and triangle tests (which it does not count).
 Cornell box 1920x1080 depth 8, the headline workload.  Prints one JSON line.     python tests/tools/whole_refill_lanes.py [frames]"""

@@ -1,4 +1,4 @@
-"""Probe (not a pytest): the rate of whole-path batches (kernels_path.hip k_whole) on an LDS-resident scene other than the Cornell box — tests/material_scenes.py's
+"""Probe (not a pytest): the rate of whole-path batches (kernels_whole.hip k_whole) on an LDS-resident scene other than the Cornell box — tests/material_scenes.py's
 compact variants, whose trees are deeper, or the chain of tests/whole_spill_scene.py, whose searches overflow the kernel's six LDS stack rows — at 1920x1080, depth 8.  For A/B runs of two library builds (tests/tools/ab_variants.sh copies them into the product's
 place in turn).  Prints one JSON line.     python tests/tools/whole_scene_rate.py [compact|compact_environment|chain|cornell_box] [frames per batch] [batches]"""
 import importlib, json, os, sys, time

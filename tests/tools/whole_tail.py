@@ -1,4 +1,4 @@
-"""Probe (not a pytest): what the fixed cost of a whole-path launch (kernels_path.hip k_whole) is made of.  Cornell box at 1920x1080; the launch
+"""Probe (not a pytest): what the fixed cost of a whole-path launch (kernels_whole.hip k_whole) is made of.  Cornell box at 1920x1080; the launch
 under HIP events at 1 / 2 / 4 frames per batch for max_depth 1, 2, 4, 8, 16: per depth, the marginal cost per frame and the fixed cost per
 launch (a straight line through the three sizes).  If the fixed part is the loop's own depth — the last paths' rounds on emptying waves —
 it grows with max_depth while the launch ramp does not.  Writes gpurun_out/<dir>/whole_tail.json.     python tests/tools/whole_tail.py [outdir]"""

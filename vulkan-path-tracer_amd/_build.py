@@ -10,10 +10,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvpt_hip.so")
-# The LABORATORY build: the same sources with -DVPT_LAB=1 — every kernel variant that was measured against the product kernels and found
+# The LABORATORY build: the same sources with -DVPT_LAB=1 plus LAB_SOURCES — every kernel variant that was measured against the product kernels and found
 # slower, round 1's stage kernels (VPT_PIPELINE_STAGED_R1) and the vpt_lab_* entry points of include/vpt_lab.h.  The product library has none of it.
 LIB_LAB = os.path.join(HERE, "libvpt_hip_lab.so")
-SOURCES = ["kernels_path.hip", "kernels_trace.hip", "kernels_stream.hip", "kernels_media.hip", "kernels_post.hip", "kernels_lut.hip", "vpt_api.hip", "bvh_build.cpp"]
+SOURCES = ["kernels_whole.hip", "kernels_finish.hip", "kernels_bounce.hip", "kernels_aux.hip", "kernels_trace.hip", "kernels_stream.hip", "kernels_media.hip", "kernels_post.hip", "kernels_lut.hip", "vpt_api.hip", "bvh_build.cpp"]
+LAB_SOURCES = ["kernels_lab_r1.hip"]   # compiled and linked into the laboratory library only
 HEADERS = ["device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "kernels.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp", "whole_refill.hpp",
            os.path.join("..", "..", "include", "vpt.h"), os.path.join("..", "..", "include", "vpt_lab.h"), os.path.join("..", "..", "include", "vpt_fp32.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -22,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # vectoriser turns 28 of them into 14 packed ones at the price of 20-30 register moves to pair the operands up
 # (profiles/r03_trace_isa_budget.md), a net loss in issued instructions, so it is off for that file.  Values are unaffected:
 # packed and scalar fp32 operations round identically and no contraction is allowed either way.
-EXTRA_FLAGS = {"kernels_trace.hip": ["-fno-slp-vectorize"], "kernels_stream.hip": ["-fno-slp-vectorize"], "kernels_path.hip": ["-fno-slp-vectorize"], "kernels_media.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("kernels_trace.hip", "kernels_stream.hip", "kernels_media.hip", "kernels_whole.hip", "kernels_finish.hip", "kernels_bounce.hip", "kernels_aux.hip", "kernels_lab_r1.hip")}
 
 
 def hipcc():
@@ -32,13 +33,18 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
+def _sources(lab):
+    return SOURCES + (LAB_SOURCES if lab else [])
+
+
 def source_id(defines=("-DVPT_LAB=0",)):
-    """sha256 (16 hex digits) over everything the library is compiled from: kernel sources, headers, this file's flags and the build's -D list
-    (the product's is -DVPT_LAB=0; the laboratory build and tests/tools/build_variant.py pass theirs, so a variant never carries the product's id).
+    """sha256 (16 hex digits) over everything the library is compiled from: kernel sources (LAB_SOURCES too when the -D list says -DVPT_LAB=1), headers,
+    this file's flags and the build's -D list (the product's is -DVPT_LAB=0; the laboratory build and tests/tools/build_variant.py pass theirs, so a
+    variant never carries the product's id).
     profiles/traffic.json carries the id of the build its rocprofv3 counters were collected on; bench.py copies an entry only when it equals the current one."""
     import hashlib
     h = hashlib.sha256()
-    for f in sorted(SOURCES) + sorted(HEADERS):
+    for f in sorted(_sources("-DVPT_LAB=1" in defines)) + sorted(HEADERS):
         h.update(open(os.path.join(CSRC, f), "rb").read())
     h.update(repr((FLAGS, sorted(EXTRA_FLAGS.items()), sorted(defines))).encode())
     return h.hexdigest()[:16]
@@ -50,7 +56,7 @@ def needs_build(lab=False):
         return True
     t = os.path.getmtime(lib)
     # (this file holds the compiler flags: a change here rebuilds too)
-    return os.path.getmtime(__file__) > t or any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+    return os.path.getmtime(__file__) > t or any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in _sources(lab) + HEADERS)
 
 
 def build(force=False, verbose=False, lab=False):
@@ -72,7 +78,7 @@ def _build_locked(lib, force, verbose, lab):
     objdir = os.path.join(HERE, "build", "lab" if lab else "product")
     os.makedirs(objdir, exist_ok=True)
     newest_header = max([os.path.getmtime(__file__)] + [os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS])
-    for src in SOURCES:
+    for src in _sources(lab):
         obj = os.path.join(objdir, src + ".o")
         objs.append(obj)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(newest_header, os.path.getmtime(os.path.join(CSRC, src))):
@@ -87,8 +93,17 @@ def _build_locked(lib, force, verbose, lab):
             raise RuntimeError("hipcc failed on %s:\n%s" % (src, out))
         if verbose and out.strip():
             print(out)
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib", "-Wl,--strip-all"]
-    subprocess.check_call(cmd)
+    return link(lib, objs)
+
+
+def link(lib, objs):
+    """Links objs into lib.  Only the C ABI (vpt_*, vpt_lab_*) is exported: every source file is a fat binary of its own, padded to whole 4 KB pages inside
+    the library, and the dynamic symbol table of the C++ launchers between them is what the product's size bound (tests/test_abi.py) does not have room for."""
+    exports = os.path.join(HERE, "build", "exports.map")
+    with open(exports, "w") as f:
+        f.write("{ global: vpt_*; local: *; };\n")
+    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs +
+                          ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib", "-Wl,--strip-all", "-Wl,--version-script=" + exports])
     return lib
 
 

@@ -89,7 +89,7 @@ struct EmissiveDesc {  // == EmissiveMeshEntry (PathTracer.h:321-328), 80 B
     float xform[16];
 };
 // Derived tables, filled on the device by the same expressions the shade stage would otherwise evaluate
-// per hit (kernels_path.hip k_precompute_*), so using them cannot change a bit of the result.
+// per hit (kernels_aux.hip k_precompute_*), so using them cannot change a bit of the result.
 struct MatResolved {  // Material.Initialize (Material.slang:39-87), per material: every field whose texture is 1x1 (k_precompute_materials)
     float base[3], roughness;
     float emissive[3], metallic;

@@ -15,19 +15,10 @@ int bounce_blocks_per_cu(bool lds_scene, const DeviceScene& sc, bool plain = fal
 void launch_whole(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, Counters* ctr, uint32_t n_slots,
                   uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles);
 int whole_blocks_per_cu(const DeviceScene& sc, bool plain);
-// the rest of a streams batch in one launch (kernels_path.hip k_finish): every path of queue[parity] run to its end
+// the rest of a streams batch in one launch (kernels_finish.hip k_finish): every path of queue[parity] run to its end
 void launch_finish(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, const StreamState& ss, const uint32_t* queue,
                    StreamCounters* sctr, Counters* ctr, uint32_t parity);
 int finish_blocks_per_cu(const DeviceScene& sc);
-void launch_raygen(hipStream_t s, const RenderParams& P, const PathState& ps, uint32_t* queue, Counters* ctr, uint32_t n_slots, uint32_t dispatch_base);
-void launch_prepare(hipStream_t s, Counters* ctr, uint32_t parity);
-void launch_fold(hipStream_t s, Counters* ctr);
-void launch_extend(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, const DeviceScene& sc, const PathState& ps,
-                   const uint32_t* queue, Counters* ctr, uint32_t parity);
-void launch_shade(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const RenderParams& P, const PathState& ps,
-                  const uint32_t* queue, uint32_t* queue_next, uint32_t* cqueue, Counters* ctr, uint32_t parity);
-void launch_connect(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, const DeviceScene& sc, const RenderParams& P,
-                    const PathState& ps, const uint32_t* cqueue, Counters* ctr, uint32_t parity);
 void launch_resolve(hipStream_t s, const RenderParams& P, const PathState& ps, float* image, uint32_t frames, uint32_t frame_base, const uint32_t* guard);
 void launch_trace_rays(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const vpt_ray* rays, uint32_t n, vpt_hit* hits);
 void launch_scatter_rows(hipStream_t s, const float* gathered, float* full, uint32_t w, uint32_t h, uint32_t shard_count, uint32_t stride_px);
@@ -37,8 +28,19 @@ void launch_precompute_tri_shade(hipStream_t s, const DeviceScene& sc, float4* o
 void launch_precompute_emissive(hipStream_t s, const DeviceScene& sc, EmissiveTri* out, uint32_t total);
 size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene, int stack_rows);   // stack_rows: LDS entries per lane (traverse.hpp kStackDepth; k_whole: kWholeStackRows)
 size_t stack_overflow_bytes(uint32_t blocks);  // per-thread spill region of the traversal stacks for a grid of `blocks`
+#if VPT_LAB   // round 1's stage kernels (kernels_lab_r1.hip): laboratory build only
+void launch_raygen(hipStream_t s, const RenderParams& P, const PathState& ps, uint32_t* queue, Counters* ctr, uint32_t n_slots, uint32_t dispatch_base);
+void launch_prepare(hipStream_t s, Counters* ctr, uint32_t parity);
+void launch_fold(hipStream_t s, Counters* ctr);
+void launch_extend(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, const DeviceScene& sc, const PathState& ps,
+                   const uint32_t* queue, Counters* ctr, uint32_t parity);
+void launch_shade(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const RenderParams& P, const PathState& ps,
+                  const uint32_t* queue, uint32_t* queue_next, uint32_t* cqueue, Counters* ctr, uint32_t parity);
+void launch_connect(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, const DeviceScene& sc, const RenderParams& P,
+                    const PathState& ps, const uint32_t* cqueue, Counters* ctr, uint32_t parity);
 int traverse_blocks_per_cu(bool lds_scene, const DeviceScene& sc);
 int shade_blocks_per_cu();
+#endif
 
 // ray-stream traversal kernels (kernels_trace.hip)
 struct TraceArgs {

@@ -1,0 +1,196 @@
+// kernels_aux.hip — one-pass kernels beside the integrators: the resolve (running mean over a batch's frames), shard rows -> full image, the derived scene
+// tables (k_precompute_*, k_classify_instances), the closest-hit test hook k_trace_rays, and the LDS / stack-overflow size helpers every launcher shares.
+#include "kernels.hpp"
+#include "shade_core.hpp"
+#include "traverse.hpp"
+
+namespace vpt {
+
+static inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+
+// ------------------------------------------------------------------ resolve: running mean, frames applied in order
+// frame_base = index of the first dispatch of the batch (== FrameCount when ScreenSplitCount is 1).
+// `guard`: queue size word that must be 0 (every path of the batch has finished) — the host enqueues the resolve right
+// behind the bounces it expects to be the last ones and only then looks at the counter; if paths were still alive the
+// launch does nothing and is repeated after more bounces.
+__global__ __launch_bounds__(256) void k_resolve(RenderParams P, PathState ps, float4* image, uint32_t frames, uint32_t frame_base, const uint32_t* guard) {
+    if (guard && *guard != 0u) return;
+    if (P.dispatch_base_dev) frame_base = *P.dispatch_base_dev;   // a replayed graph (see k_bounce)
+    uint32_t sp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (sp >= P.shard_pixels) return;
+    float4 px = image[sp];
+    V3 color = v3(px.x, px.y, px.z);
+    if (P.split == 1u) {
+        for (uint32_t f = 0; f < frames; f++) {
+            V3 acc = xyz(ps.ACC[f * P.shard_pixels + sp]) / (float)P.samples_per_frame;
+            uint32_t fc = frame_base + f;
+            if (fc > 0) color = lerp(color, acc, 1.0f / (float)(fc + 1u));
+            else color = acc;
+        }
+    } else {
+        // split-screen (RayGen.slang:16-25, 143-157): dispatch d touches only the pixels of its chunk; the very
+        // first dispatch also copies each rendered pixel into its whole S x S cell ("pixels that aren't rendered")
+        const uint32_t S = P.split, y = sp / P.width, x = sp - y * P.width;
+        for (uint32_t f = 0; f < frames; f++) {
+            uint32_t d = frame_base + f, c = d % (S * S), fc = d / (S * S);
+            if (x % S == c % S && y % S == c / S) {
+                V3 acc = xyz(ps.ACC[f * P.shard_pixels + sp]) / (float)P.samples_per_frame;
+                if (fc > 0) color = lerp(color, acc, 1.0f / (float)(fc + 1u));
+                else color = acc;
+            } else if (d == 0u) {
+                uint32_t ax = x - x % S, ay = y - y % S;
+                color = xyz(ps.ACC[f * P.shard_pixels + ay * P.width + ax]) / (float)P.samples_per_frame;
+            }
+        }
+    }
+    image[sp] = make_float4(color.x, color.y, color.z, 1.0f);
+}
+void launch_resolve(hipStream_t s, const RenderParams& P, const PathState& ps, float* image, uint32_t frames, uint32_t frame_base, const uint32_t* guard) {
+    hipLaunchKernelGGL(k_resolve, dim3(cdiv(P.shard_pixels, 256)), dim3(256), 0, s, P, ps, reinterpret_cast<float4*>(image), frames, frame_base, guard);
+}
+
+// shard rows <-> full image
+__global__ __launch_bounds__(256) void k_scatter_rows(const float4* gathered, float4* full, uint32_t width, uint32_t height,
+                                                      uint32_t shard_count, uint32_t shard_stride_px) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    uint32_t y = i / width, x = i - y * width;
+    uint32_t r = y % shard_count, ys = y / shard_count;
+    full[i] = gathered[(size_t)r * shard_stride_px + (size_t)ys * width + x];
+}
+void launch_scatter_rows(hipStream_t s, const float* gathered, float* full, uint32_t w, uint32_t h, uint32_t shard_count, uint32_t stride_px) {
+    hipLaunchKernelGGL(k_scatter_rows, dim3(cdiv(w * h, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(gathered),
+                       reinterpret_cast<float4*>(full), w, h, shard_count, stride_px);
+}
+
+// ------------------------------------------------------------------ derived scene tables
+__global__ __launch_bounds__(256) void k_precompute_materials(DeviceScene sc, uint32_t flags, MatResolved* out, uint32_t n) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vpt_material& m = sc.materials[i];
+    MatResolved r;
+    V2 uv; uv.x = 0.0f; uv.y = 0.0f;
+    material_resolve(sc, m, uv, flags, r);   // a field whose texture is not 1x1 holds a value nobody reads (its flag stays clear)
+    auto one = [&](uint32_t t) { return sc.textures[t].w == 1 && sc.textures[t].h == 1; };
+    r.flags = (one(m.base_color_texture) ? kMatBase : 0u) | (one(m.roughness_texture) ? kMatRoughness : 0u) |
+              (one(m.metallic_texture) ? kMatMetallic : 0u) | (one(m.emissive_texture) ? kMatEmissive : 0u);
+    if ((r.flags & (kMatBase | kMatRoughness | kMatMetallic | kMatEmissive)) == (kMatBase | kMatRoughness | kMatMetallic | kMatEmissive)) r.flags |= kMatAllValues;
+    if (one(m.normal_texture)) {
+        V4 nm = tex_sample(sc, m.normal_texture, 0.0f, 0.0f);
+        r.nmap[0] = nm.x * 2.0f - 1.0f; r.nmap[1] = nm.y * 2.0f - 1.0f; r.nmap[2] = nm.z * 2.0f - 1.0f;
+        r.flags |= kMatNormal;
+    } else { r.nmap[0] = r.nmap[1] = r.nmap[2] = 0.0f; }
+    r.pad1 = r.pad2 = 0.0f;
+    r.tex[0] = sc.textures[m.normal_texture]; r.tex[1] = sc.textures[m.base_color_texture]; r.tex[2] = sc.textures[m.roughness_texture];
+    r.tex[3] = sc.textures[m.metallic_texture]; r.tex[4] = sc.textures[m.emissive_texture];
+    out[i] = r;
+}
+// One LightSampler per emissive mesh (device_types.hpp): the fields SampleEmissiveTriangle reads through four tables, side by side.
+__global__ __launch_bounds__(64) void k_precompute_lights(DeviceScene sc, LightSampler* out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= sc.emissive_count) return;
+    const EmissiveDesc& em = sc.emissive[i];
+    const vpt_material& m = sc.materials[em.material];
+    LightSampler ls;
+    ls.tri_count = em.tri_count; ls.gid_base = sc.instances[em.instance].tri_offset; ls.tri_base = sc.emissive_tri_offset[i];
+    ls.tex = sc.textures[m.emissive_texture];
+    ls.uniform = (ls.tex.w == 1 && ls.tex.h == 1) ? 1u : 0u;
+    ls.emissive_color[0] = m.emissive_color[0]; ls.emissive_color[1] = m.emissive_color[1]; ls.emissive_color[2] = m.emissive_color[2];
+    V4 te = tex_sample(sc, m.emissive_texture, 0.0f, 0.0f);
+    ls.radiance[0] = m.emissive_color[0] * te.x; ls.radiance[1] = m.emissive_color[1] * te.y; ls.radiance[2] = m.emissive_color[2] * te.z;
+    ls.pad0 = ls.pad1 = 0.0f;
+    out[i] = ls;
+}
+__global__ __launch_bounds__(256) void k_precompute_tri_ng(DeviceScene sc, float4* out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= sc.tri_count) return;
+    const BvhTri& t = sc.tris[i];
+    V3 ng = triangle_ng(sc, sc.instances[t.inst], t.prim);
+    out[t.gid] = make_float4(ng.x, ng.y, ng.z, 0.0f);
+}
+__global__ __launch_bounds__(256) void k_precompute_tri_shade(DeviceScene sc, float4* out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= sc.tri_count) return;
+    const BvhTri& t = sc.tris[i];
+    const InstanceDesc in = sc.instances[t.inst];
+    const MeshDesc me = sc.meshes[in.mesh];
+    const uint32_t* idx = sc.indices + me.index_offset + t.prim * 3;
+    const vpt_vertex* vb = sc.vertices + me.vertex_offset;
+    float4* q = out + (size_t)t.gid * 8;
+    for (int k = 0; k < 3; k++) {
+        const float4* v = reinterpret_cast<const float4*>(vb + idx[k]);
+        q[2 * k] = v[0]; q[2 * k + 1] = v[1];
+    }
+    V3 ng = triangle_ng(sc, in, t.prim);
+    q[6] = make_float4(ng.x, ng.y, ng.z, 0.0f);
+    q[7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+__global__ __launch_bounds__(256) void k_precompute_emissive(DeviceScene sc, EmissiveTri* out, uint32_t total) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    uint32_t k = 0;
+    while (k + 1 < sc.emissive_count && sc.emissive_tri_offset[k + 1] <= i) k++;
+    EmissiveTri t;
+    emissive_tri_compute(sc, sc.emissive[k], i - sc.emissive_tri_offset[k], t);
+    out[i] = t;
+}
+// Shade class of every instance (device_types.hpp kShade*), from the resolved material table.
+__global__ __launch_bounds__(256) void k_classify_instances(DeviceScene sc, unsigned char* out, uint32_t n) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t mi = sc.instances[i].material;
+    const vpt_material& m = sc.materials[mi];
+    const MatResolved& r = sc.mat_resolved[mi];
+    const bool emissive = (r.flags & kMatEmissive) ? (r.emissive[0] > 0.0f || r.emissive[1] > 0.0f || r.emissive[2] > 0.0f)
+                                         : (m.emissive_color[0] != 0.0f || m.emissive_color[1] != 0.0f || m.emissive_color[2] != 0.0f);
+    uint32_t c = kShadeTextured;
+    if (emissive) c = kShadeEmissive;
+    else if (m.transmission > 0.0f) c = kShadeGlass;
+    else if ((r.flags & (kMatAllValues | kMatNormal)) == (kMatAllValues | kMatNormal)) c = kShadePlain;   // the promise k_shade_stream<kShadePlain> relies on: no texture of this material is ever sampled
+    out[i] = (unsigned char)c;
+}
+void launch_classify_instances(hipStream_t s, const DeviceScene& sc, unsigned char* out, uint32_t n) {
+    if (n) hipLaunchKernelGGL(k_classify_instances, dim3((n + 255) / 256), dim3(256), 0, s, sc, out, n);
+}
+// (the light table reads materials and textures too: every caller that refreshes one refreshes the other)
+void launch_precompute_materials(hipStream_t s, const DeviceScene& sc, uint32_t flags, MatResolved* out, uint32_t n) {
+    if (n) hipLaunchKernelGGL(k_precompute_materials, dim3((n + 255) / 256), dim3(256), 0, s, sc, flags, out, n);
+    if (sc.emissive_count) hipLaunchKernelGGL(k_precompute_lights, dim3((sc.emissive_count + 63) / 64), dim3(64), 0, s, sc, const_cast<LightSampler*>(sc.lights));
+}
+void launch_precompute_tri_ng(hipStream_t s, const DeviceScene& sc, float4* out) {
+    if (sc.tri_count) hipLaunchKernelGGL(k_precompute_tri_ng, dim3((sc.tri_count + 255) / 256), dim3(256), 0, s, sc, out);
+}
+void launch_precompute_tri_shade(hipStream_t s, const DeviceScene& sc, float4* out) {
+    if (sc.tri_count) hipLaunchKernelGGL(k_precompute_tri_shade, dim3((sc.tri_count + 255) / 256), dim3(256), 0, s, sc, out);
+}
+void launch_precompute_emissive(hipStream_t s, const DeviceScene& sc, EmissiveTri* out, uint32_t total) {
+    if (total) hipLaunchKernelGGL(k_precompute_emissive, dim3((total + 255) / 256), dim3(256), 0, s, sc, out, total);
+}
+
+// Test hook: the closest-hit traversal on caller-supplied rays.
+__global__ __launch_bounds__(kTraverseBlock) void k_trace_rays(DeviceScene sc, const vpt_ray* rays, uint32_t n, vpt_hit* hits) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const TravStack stack = make_stack(smem, sc.stack_overflow);
+    GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        vpt_ray r = rays[i];
+        HitRec h; TravStats st;
+        bool found = trace_closest<false>(src, v3(r.origin[0], r.origin[1], r.origin[2]), v3(r.direction[0], r.direction[1], r.direction[2]),
+                                          r.tmin, r.tmax, stack, h, st);
+        vpt_hit o; o.t = found ? h.t : -1.0f; o.u = found ? h.u : 0.0f; o.v = found ? h.v : 0.0f; o.primitive = h.prim; o.instance = h.inst;
+        hits[i] = o;
+    }
+}
+void launch_trace_rays(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const vpt_ray* rays, uint32_t n, vpt_hit* hits) {
+    uint32_t g = cdiv(n, kTraverseBlock);
+    hipLaunchKernelGGL(k_trace_rays, dim3(g < blocks ? g : blocks), dim3(kTraverseBlock), (size_t)kStackDepth * kTraverseBlock * 4, s, sc, rays, n, hits);
+}
+
+size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene, int stack_rows) {
+    size_t b = (size_t)stack_rows * kTraverseBlock * 4;
+    if (lds_scene) b += (size_t)sc.node_count * sizeof(BvhNodeWide) + (size_t)sc.tri_count * sizeof(BvhTri);
+    return b;
+}
+size_t stack_overflow_bytes(uint32_t blocks) { return (size_t)blocks * kTraverseBlock * kOverflowStride * 4; }   // (traverse.hpp: the longest per-thread region of any kernel)
+
+}  // namespace vpt

@@ -162,7 +162,7 @@ inline bool depth_bounded(const std::vector<vpt_material>& materials) {
         if (m.transmission > 0.0f && m.medium_density != 0.0f && m.medium_anisotropy != 1.0f) return false;
     return true;
 }
-// The scene class the fused kernel is specialised for (kernels_path.hip k_bounce<PLAIN>): every material's five textures are 1x1 and the
+// The scene class the fused kernel is specialised for (kernels_bounce.hip k_bounce<PLAIN>): every material's five textures are 1x1 and the
 // environment is black — what k_precompute_materials turns into MatResolved.flags == 63 for every material, and k_precompute_lights into
 // uniform light samplers.
 inline bool plain(const std::vector<vpt_material>& materials, const std::vector<unsigned char>& tex_1x1, bool env_black, uint32_t build_flags) {

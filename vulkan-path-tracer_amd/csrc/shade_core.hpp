@@ -1,7 +1,7 @@
 // shade_core.hpp — the miss / closest-hit shader and the visibility-independent tail of the reference's bounce loop for ONE
 // path, on values held in registers (ClosestHit.slang:20-378, Miss.slang:8-77, RayGen.slang:104-113, and the volume /
-// atmosphere scatter events of RayGen.slang:265-470).  Shared by the fused per-bounce kernels (kernels_path.hip) and the
-// staged shade stage (kernels_path.hip k_shade, kernels_stream.hip); the callers own every load / store of path records.
+// atmosphere scatter events of RayGen.slang:265-470).  Shared by the fused per-bounce, finishing and whole-path kernels (kernels_bounce.hip, kernels_finish.hip, kernels_whole.hip) and the
+// staged shade stage (kernels_stream.hip; the laboratory's kernels_lab_r1.hip k_shade); the callers own every load / store of path records.
 #pragma once
 #include "shading.hpp"
 #include "volume.hpp"

@@ -21,7 +21,7 @@ namespace vpt {
 constexpr int kStackDepth = 14;      // LDS entries per lane
 constexpr int kStackOverflow = 82;   // global entries per lane: 3 pushes per level x binary depth bound 30, minus the LDS part
 constexpr int kTraverseBlock = 256;
-// The whole-path kernel (kernels_path.hip k_whole) keeps fewer rows in LDS: a tree that rides in LDS is at most 3 KB (the Cornell box: three
+// The whole-path kernel (kernels_whole.hip k_whole) keeps fewer rows in LDS: a tree that rides in LDS is at most 3 KB (the Cornell box: three
 // nodes, never more than 6 entries deep), and the 8 KB it gives up hold the waves' buffers of fresh camera rays.
 constexpr int kWholeStackRows = 6;
 
@@ -381,6 +381,45 @@ __device__ inline bool closest_is(const Src& src, V3 o, V3 d, float tmin, float 
     if (!vptfp::ray_triangle(o, d, vptfp::v3(a.x, a.y, a.z), vptfp::v3(a.w, b.x, b.y), vptfp::v3(b.z, b.w, c.x), tmin, tmax, &t_e, &u, &v)) return false;
     if (src.strict && !vptfp::hit_is_local(o, d, vptfp::v3(a.x, a.y, a.z), vptfp::v3(a.w, b.x, b.y), vptfp::v3(b.z, b.w, c.x), t_e)) return false;
     return !trace_occluded<COUNT, true>(src, o, d, tmin, tmax, t_e, expect, stack, st);
+}
+
+// ------------------------------------------------------------------ the searches on a DeviceScene: tree in LDS (LDS_SCENE, staged by stage_scene) or in memory
+// (the fused, finishing and whole-path kernels' validating instantiations, k_trace_rays and the laboratory's stage kernels)
+template <bool LDS_SCENE>
+__device__ inline void stage_scene(const DeviceScene& sc, float4* lds_nodes, float4* lds_tris) {
+    if (LDS_SCENE) {
+        const float4* gn = reinterpret_cast<const float4*>(sc.nodes_wide);
+        const float4* gt = reinterpret_cast<const float4*>(sc.tris);
+        for (uint32_t i = threadIdx.x; i < sc.node_count * 8; i += blockDim.x) lds_nodes[i] = gn[i];
+        for (uint32_t i = threadIdx.x; i < sc.tri_count * 3; i += blockDim.x) lds_tris[i] = gt[i];
+        __syncthreads();
+    }
+}
+template <bool LDS_SCENE, bool COUNT, class Stack>
+__device__ inline bool trace_any(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, float tmin,
+                                 float tmax, const Stack& stack, HitRec& h, TravStats& st) {
+    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
+    GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
+    return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st);
+}
+
+// Sky visibility / light identity as exact any-hit queries (above).
+// rq: USE_RAY_QUERIES (RTCommon.slang:52-63: the direction as it is, TMin 1e-4, TMax 1e6); otherwise RTCommon.slang:64-84: normalised, TMin 1e-5, TMax 1000.
+template <bool LDS_SCENE, bool COUNT, class Stack>
+__device__ inline bool sky_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const Stack& stack, TravStats& st, bool rq) {
+    const float tmin = rq ? 0.0001f : 0.00001f, tmax = rq ? 1000000.0f : 1000.0f;
+    if (!rq) d = normalize(d);
+    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
+    GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
+    return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st);
+}
+template <bool LDS_SCENE, bool COUNT, class Stack>
+__device__ inline bool light_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const Stack& stack, TravStats& st) {
+    uint32_t slot = sc.tri_slot_of_gid[gid];
+    if (slot == 0xffffffffu) return false;  // the sampled light triangle is a sliver: nothing can hit it
+    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
+    GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
+    return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st);
 }
 
 }  // namespace vpt

@@ -125,7 +125,7 @@ struct vpt_ctx {
         uint32_t* emissive_tri_offset = nullptr;
         float4* tri_ng = nullptr;
         float4* tri_shade = nullptr;
-        unsigned char* inst_class = nullptr;   // shade class per instance (kernels_path.hip k_classify_instances)
+        unsigned char* inst_class = nullptr;   // shade class per instance (kernels_aux.hip k_classify_instances)
     } dw;
     std::vector<BvhTri> bvh_input;          // the triangles the BVH was built from (trace lab: the eight-wide tree is built from them on first use)
     bool lds_scene = false;
@@ -139,7 +139,7 @@ struct vpt_ctx {
     uint32_t frames_in_flight = 1;   // largest batch the context will render at once (the cap; vpt_config.frames_in_flight)
     uint32_t frames_cap = 0;     // upper bound of frames_in_flight after an out-of-memory failure of a size the library chose itself
     uint32_t long_factor = 4;    // batch_cap(): contexts that keep only part (or none) of a batch's paths resident take batches this many times frames_in_flight
-    int whole_blocks = 0;        // persistent grid of the whole-path kernel (kernels_path.hip k_whole), 0: the scene does not ride in LDS
+    int whole_blocks = 0;        // persistent grid of the whole-path kernel (kernels_whole.hip k_whole), 0: the scene does not ride in LDS
     uint32_t lab_whole_sched = 4u;   // how k_whole's waves get their tiles (VPT_LAB_WHOLE_SCHED): tiles per atomic | static-rounds mode << 4
     uint32_t lab_whole_frames = 0xffffffffu;   // VPT_PIPELINE_AUTO runs batches of at most this many frames as ONE whole-path launch (VPT_LAB_WHOLE_FRAMES); default: every batch
                                                // (Cornell box 1080p, Msamples/s whole vs per-bounce at 1 / 4 / 16 / 64 / 226 frames per batch: 3821 / 6413 / 7737 / 8183 / 8315 vs
@@ -1143,7 +1143,7 @@ int upload_scene(vpt_ctx* c, const vpt_scene_desc& sd, scene::HostScene& hs, con
     if ((rc = upload(c, hs.materials, &D.materials, 1, &W.materials))) return rc;
     if ((rc = upload(c, hs.textures, &D.textures))) return rc;
     if ((rc = upload(c, hs.texels, &D.texels, 4))) return rc;
-    // filled on the device (kernels_path.hip k_precompute_*) or by upload_emissive; per instance: an emissive mesh is an instance of an emissive material
+    // filled on the device (kernels_aux.hip k_precompute_*) or by upload_emissive; per instance: an emissive mesh is an instance of an emissive material
     const size_t n_inst = hs.instances.size(), n_tris = hs.total_tris;
     if ((rc = alloc_table(c, n_inst, &D.emissive, &W.emissive))) return rc;
     if ((rc = alloc_table(c, hs.materials.size(), &D.mat_resolved, &W.mat_resolved))) return rc;

@@ -1,4 +1,4 @@
-// whole_refill.hpp — how a wave of the whole-path kernel (kernels_path.hip k_whole) comes by its fresh samples: the tile cursor and the
+// whole_refill.hpp — how a wave of the whole-path kernel (kernels_whole.hip k_whole) comes by its fresh samples: the tile cursor and the
 // wave's buffer of generated camera rays.  Plain integer arithmetic on wave-uniform values, compiled for the device and — by
 // tests/tools/whole_refill_driver.cpp — for the host, where tests/test_whole_refill_cpu.py plays whole grids of waves against it.
 //
