@@ -5,7 +5,11 @@ closest-hit loop of traverse.hpp on the host.
   * the Cornell box (the headline workload): bound 4, so its searches never touch the overflow region, with 6 rows as with 14;
   * tests/material_scenes.py's compact scenes: bound 9 — the shape allows an overflow, random rays stay within 6;
   * tests/whole_spill_scene.py's chain: under 3 KB, bound above 6, and rays from the floor towards the light do go above 6 with the triangle
-    tests pruning as on the device: the scene tests/test_gpu_whole_refill.py needs to see the spill path of the shorter stack run."""
+    tests pruning as on the device: the scene tests/test_gpu_whole_refill.py needs to see the spill path of the shorter stack run;
+  * tests/whole_spill_scene.py's memory chain: above 3 KB, so its tree lives in memory, and rays from the floor towards the light go above the
+    14 rows of every other traversal kernel: the scene tests/test_gpu_spill_schedules.py needs to see their spill path run;
+  * no tree the builder makes, over inputs chosen to defeat the SAH, allows more than the kStackDepth + kStackOverflow entries a stack holds
+    (traverse.hpp TravStackT::push, vote.hpp LaneStack and kernels_trace.hip PoolStack drop a push beyond them without a word)."""
 import os
 import re
 
@@ -81,3 +85,116 @@ def test_the_chain_overflows_six_rows(lib, vpt):
     for oo, dd in ((o, d), (o2, d2)):
         for prune in (0, 1):
             assert W.ray_depths(lib, tris, oo, dd, prune).max() <= f["stack_bound"]
+
+
+def test_the_memory_chain_overflows_fourteen_rows(lib, vpt):
+    """The premise of tests/test_gpu_spill_schedules.py, checked without a GPU."""
+    tris = W.world_triangles(W.memory_chain_scene(vpt))
+    rows, capacity = constant("kStackDepth"), constant("kStackDepth") + constant("kStackOverflow")
+    rng = np.random.default_rng(6)
+    o, d = floor_to_light_rays(rng, 4000)
+    o2, d2 = random_rays(rng, tris, 20000)
+    for sbvh in (False, True):
+        f = W.tree_facts(lib, tris, sbvh)
+        print("memory chain%s: %r" % (" (SBVH)" if sbvh else "", f))
+        assert f["lds_bytes"] > LDS_SCENE_BYTES, f            # the tree lives in memory: no whole-path launch, the vote-scheduled kernels
+        assert rows < f["stack_bound"] <= capacity, f
+        for prune in (0, 1):
+            sp = W.ray_depths(lib, tris, o, d, prune, sbvh)
+            print("  floor-to-light rays, prune %d: deepest %d, %.1f %% above %d rows" % (prune, sp.max(), 100.0 * (sp > rows).mean(), rows))
+            assert sp.max() > rows and (sp > rows).mean() > 0.01, "rays through the stack should need more than %d entries: max %d" % (rows, sp.max())
+            assert sp.max() <= f["stack_bound"]
+            assert W.ray_depths(lib, tris, o2, d2, prune, sbvh).max() <= f["stack_bound"]
+            # ... and so do searches over a window that cuts the stack at both ends (the vpt_trace_rays case)
+            sp = W.ray_depths(lib, tris, o, d, prune, sbvh, *W.MID_STACK_WINDOW)
+            print("  the same over t = %g .. %g: deepest %d, %.1f %% above %d rows" % (W.MID_STACK_WINDOW + (sp.max(), 100.0 * (sp > rows).mean(), rows)))
+            assert sp.max() > rows and (sp > rows).mean() > 0.01
+
+
+def quads(z, half=1.0):
+    """Axis-aligned quads of half width `half` at the heights z, as two triangle records each."""
+    z = np.asarray(z, np.float32)
+    half = np.broadcast_to(np.asarray(half, np.float32), z.shape)
+    recs = np.zeros((len(z), 2, 12), np.float32)
+    recs[:, :, 0] = -half[:, None]; recs[:, :, 1] = -half[:, None]; recs[:, :, 2] = z[:, None]
+    recs[:, 0, 3] = 2 * half; recs[:, 0, 6] = 2 * half; recs[:, 0, 7] = 2 * half          # (-h,-h) (h,-h) (h,h)
+    recs[:, 1, 3] = 2 * half; recs[:, 1, 4] = 2 * half; recs[:, 1, 7] = 2 * half          # (-h,-h) (h,h) (-h,h)
+    return recs.reshape(-1, 12)
+
+
+def numbered(recs):
+    recs = np.ascontiguousarray(recs, np.float32)
+    n = len(recs)
+    ids = np.stack([np.arange(n), np.zeros(n), np.arange(n)], axis=1).astype(np.uint32)
+    recs[:, 9:12] = ids.view(np.float32)
+    return recs
+
+
+def chain(ratio, sheets):
+    z = -1.5 + 3.0 * float(ratio) ** (np.arange(sheets) - (sheets - 1.0))
+    return numbered(np.concatenate([quads([-4.5], 6.0), quads(z), quads([4.0], 3.0)]))
+
+
+def random_triangles(rng, centres, size):
+    recs = np.zeros((len(centres), 12), np.float32)
+    recs[:, 0:3] = centres
+    recs[:, 3:6] = rng.normal(size=(len(centres), 3)) * size[:, None]
+    recs[:, 6:9] = rng.normal(size=(len(centres), 3)) * size[:, None]
+    return recs
+
+
+def heavy_tailed(rng, n=3000):
+    """Sizes over six decades: a few triangles span the scene, most are dust — the SAH keeps peeling the large ones off."""
+    return numbered(random_triangles(rng, rng.uniform(-2, 2, (n, 3)), 10.0 ** rng.uniform(-5, 1, n)))
+
+
+def one_huge_over_many_tiny(rng, n=3000):
+    tiny = random_triangles(rng, rng.normal(size=(n, 3)) * 1e-3, np.full(n, 1e-5))
+    huge = np.zeros((1, 12), np.float32); huge[0, 0:3] = (-100, -100, 0); huge[0, 3] = 300; huge[0, 7] = 300
+    return numbered(np.concatenate([huge, tiny]))
+
+
+def diagonal_strip(n=1500):
+    """A long thin strip along (1, 1, 1): every box of consecutive quads overlaps its neighbours' on all three axes."""
+    t = np.linspace(-3, 3, n + 1).astype(np.float32)
+    recs = np.zeros((n, 2, 12), np.float32)
+    p0 = np.stack([t[:-1]] * 3, axis=1); step = np.stack([t[1:] - t[:-1]] * 3, axis=1)
+    across = np.array([1e-3, -1e-3, 0.0], np.float32)
+    recs[:, :, 0:3] = p0[:, None]
+    recs[:, 0, 3:6] = step; recs[:, 0, 6:9] = step + across
+    recs[:, 1, 3:6] = step + across; recs[:, 1, 6:9] = across
+    return numbered(recs.reshape(-1, 12))
+
+
+ADVERSARIAL = {
+    "chain_1.05x600": lambda rng: chain(1.05, 600), "chain_1.1x300": lambda rng: chain(1.1, 300), "chain_1.2x120": lambda rng: chain(1.2, 120),
+    "chain_1.3x80": lambda rng: chain(1.3, 80), "chain_3x60": lambda rng: chain(3.0, 60),
+    "coincident_quads": lambda rng: numbered(quads(np.zeros(500))),
+    "heavy_tailed_sizes": heavy_tailed, "one_huge_many_tiny": one_huge_over_many_tiny, "diagonal_strip": lambda rng: diagonal_strip(),
+}
+
+
+@pytest.mark.parametrize("sbvh", [False, True])
+@pytest.mark.parametrize("name", sorted(ADVERSARIAL))
+def test_no_tree_the_builder_makes_can_drop_a_push(lib, name, sbvh):
+    """A push beyond kStackDepth + kStackOverflow = 96 entries is dropped silently, and the only thing that keeps a search below that is the
+    builder's depth bound (bvh_build.cpp kMaxDepth: the SAH gives way to median splits before the binary tree gets deeper than 30 levels, and a
+    four-wide node leaves at most three entries per level).  Inputs chosen to make the SAH peel one triangle off at a time: geometric chains
+    (the fallback does engage: they would be hundreds of levels deep otherwise), coincident quads (no centroid extent at all), sizes over six
+    decades, one triangle that spans everything else, a thin diagonal strip; each with and without spatial splits."""
+    rng = np.random.default_rng(11)
+    tris = ADVERSARIAL[name](rng)
+    capacity = constant("kStackDepth") + constant("kStackOverflow")
+    f = W.tree_facts(lib, tris, sbvh)
+    print("%s%s: %d triangles, %r" % (name, " (SBVH)" if sbvh else "", len(tris), f))
+    assert f["stack_bound"] <= capacity, f
+    assert f["levels"] <= 30, f                                   # four-wide levels cannot outnumber the binary ones
+    if name.startswith("chain"):
+        assert f["stack_bound"] > constant("kStackDepth"), "the chain no longer defeats the SAH: %r" % (f,)
+    o, d = random_rays(rng, tris, 4000)
+    sets = [(o, d)]
+    if name.startswith("chain") or name == "coincident_quads":
+        sets.append(floor_to_light_rays(rng, 4000))               # up through every sheet
+    for oo, dd in sets:
+        for prune in (0, 1):
+            assert W.ray_depths(lib, tris, oo, dd, prune, sbvh).max() <= f["stack_bound"]

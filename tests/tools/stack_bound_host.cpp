@@ -15,10 +15,10 @@ namespace {
 struct Tree {
     std::vector<BvhNode> nodes; std::vector<BvhNodeWide> wide; std::vector<BvhTri> leaf; int depth = 0;
 };
-void build(const void* tris_in, int ntris, Tree& t) {
+void build(const void* tris_in, int ntris, int sbvh, Tree& t) {   // sbvh: with spatial splits (vpt_config.build_flags VPT_BUILD_SBVH)
     std::vector<BvhTri> tris(ntris);
     memcpy(tris.data(), tris_in, sizeof(BvhTri) * (size_t)ntris);
-    build_bvh(tris, t.nodes, t.wide, t.leaf, &t.depth, nullptr, false, false);
+    build_bvh(tris, t.nodes, t.wide, t.leaf, &t.depth, nullptr, sbvh != 0, false);
 }
 bool used(const BvhNodeWide& n, int k) { return n.minx[k] < 1.0e29f; }   // (an unused slot is an unreachable point box: bvh_build.cpp empty_wide)
 // A node with k children pushes at most k - 1 of them and goes down into the other; whichever it takes first has all its siblings below it.
@@ -36,18 +36,18 @@ int bound(const Tree& t, int node) {
 extern "C" {
 
 // out: {four-wide nodes, leaf triangles, bytes of the tree in LDS, levels of inner nodes below the root, stack bound}
-void sb_tree(const void* tris_in, int ntris, int* out) {
-    Tree t; build(tris_in, ntris, t);
+void sb_tree_ex(const void* tris_in, int ntris, int sbvh, int* out) {
+    Tree t; build(tris_in, ntris, sbvh, t);
     out[0] = (int)t.wide.size(); out[1] = (int)t.leaf.size();
     out[2] = (int)(t.wide.size() * sizeof(BvhNodeWide) + t.leaf.size() * sizeof(BvhTri));
     out[3] = t.depth; out[4] = bound(t, 0);
 }
+void sb_tree(const void* tris_in, int ntris, int* out) { sb_tree_ex(tris_in, ntris, 0, out); }
 
-// n rays (o, d: n x 3, d normalised; the kernels' closest-hit range 0.01 .. 1e5): per ray the largest number of entries its stack held.
+// n rays (o, d: n x 3, d normalised; sb_rays: the kernels' closest-hit range 0.01 .. 1e5): per ray the largest number of entries its stack held.
 // prune = 0: tlimit stays tmax (no triangle tests), what a search whose triangles all miss would do.
-void sb_rays(const void* tris_in, int ntris, int64_t n, const float* o, const float* d, int prune, int* max_sp) {
-    Tree t; build(tris_in, ntris, t);
-    const float tmin = 0.01f, tmax = 100000.0f;
+void sb_rays_ex(const void* tris_in, int ntris, int sbvh, int64_t n, const float* o, const float* d, float tmin, float tmax, int prune, int* max_sp) {
+    Tree t; build(tris_in, ntris, sbvh, t);
     for (int64_t i = 0; i < n; i++) {
         const V3 O = vptfp::v3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), D = vptfp::v3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), inv = safe_inverse(D);
         std::vector<int> stack;
@@ -83,5 +83,6 @@ void sb_rays(const void* tris_in, int ntris, int64_t n, const float* o, const fl
         max_sp[i] = (int)deepest;
     }
 }
+void sb_rays(const void* tris_in, int ntris, int64_t n, const float* o, const float* d, int prune, int* max_sp) { sb_rays_ex(tris_in, ntris, 0, n, o, d, 0.01f, 100000.0f, prune, max_sp); }
 
 }

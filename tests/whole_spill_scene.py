@@ -3,7 +3,10 @@ the whole-path kernel's shorter LDS stack (traverse.hpp kWholeStackRows = 6; tes
 Sheets stacked along z with gaps that halve towards the bottom: the SAH builder peels the lonely upper sheets off one at a time, so a four-wide
 node holds three leaves and the rest of the stack, level after level, and a ray that comes from below crosses every box, goes down the chain
 first and leaves three siblings on its stack per level.  Floor, light and camera as in tests/test_gpu_spills.py: the camera looks down at the
-floor from under the stack, so bounce rays and the rays towards the light go up through the sheets.  Not a test module."""
+floor from under the stack, so bounce rays and the rays towards the light go up through the sheets.
+memory_chain_scene is the same geometry with 40 sheets whose gaps shrink by 1.5 instead of 2: 84 triangles, too many for LDS, so the tree lives
+in memory, and deep enough that searches overflow the 14 LDS rows of every other traversal kernel too (tests/test_gpu_spill_schedules.py; its
+premise on the host: tests/test_stack_bound_cpu.py).  Not a test module."""
 import ctypes as C
 import os
 import subprocess
@@ -13,13 +16,23 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 SHEETS = 16
+MID_STACK_WINDOW = (3.3, 4.5)    # (tmin, tmax) that begin and end between memory_chain_scene's sheets for rays from the floor (a vertical one crosses them at t = 3 .. 6)
 
 
 def chain_scene(vpt, sheets=SHEETS):
+    return sheets_scene(vpt, (-1.5 + 3.0 * 0.5 ** np.arange(sheets - 1, -1, -1)).astype(F32))       # gaps 3/2, 3/4, ... from the top down
+
+
+def memory_chain_scene(vpt, sheets=40, ratio=1.5):
+    return sheets_scene(vpt, (-1.5 + 3.0 * ratio ** (np.arange(sheets) - (sheets - 1))).astype(F32))
+
+
+def sheets_scene(vpt, z):
+    """Quads of half width 1 at the heights z, over the floor and under the light."""
     S = vpt.scenes
     sc = S.Scene()
     sc.luts = S.load_luts()
-    z = (-1.5 + 3.0 * 0.5 ** np.arange(sheets - 1, -1, -1)).astype(F32)       # gaps 3/2, 3/4, ... from the top down
+    sheets = len(z)
     corners = np.array([[-1, -1], [1, -1], [1, 1], [-1, 1]], F32)
     pos = np.zeros((sheets, 4, 3), F32)
     pos[:, :, :2] = corners[None]
@@ -66,17 +79,21 @@ def stack_bound_lib(out_dir):
     L.sb_tree.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.sb_rays.restype = None
     L.sb_rays.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.sb_tree_ex.restype = None
+    L.sb_tree_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.sb_rays_ex.restype = None
+    L.sb_rays_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p]
     return L
 
 
-def tree_facts(L, tris):
+def tree_facts(L, tris, sbvh=False):
     out = np.zeros(5, np.int32)
-    L.sb_tree(tris.ctypes.data, len(tris), out.ctypes.data)
+    L.sb_tree_ex(tris.ctypes.data, len(tris), int(sbvh), out.ctypes.data)
     return dict(zip(("nodes", "leaf_tris", "lds_bytes", "levels", "stack_bound"), (int(v) for v in out)))
 
 
-def ray_depths(L, tris, o, d, prune):
+def ray_depths(L, tris, o, d, prune, sbvh=False, tmin=0.01, tmax=100000.0):
     o, d = np.ascontiguousarray(o, F32), np.ascontiguousarray(d, F32)
     sp = np.zeros(len(o), np.int32)
-    L.sb_rays(tris.ctypes.data, len(tris), len(o), o.ctypes.data, d.ctypes.data, int(prune), sp.ctypes.data)
+    L.sb_rays_ex(tris.ctypes.data, len(tris), int(sbvh), len(o), o.ctypes.data, d.ctypes.data, tmin, tmax, int(prune), sp.ctypes.data)
     return sp

@@ -17,7 +17,7 @@ namespace vpt {
 namespace {
 constexpr int kLeafSize = 4;
 constexpr int kMaxBins = 32;   // (the product builds with 16 bins, BvhBuildOptions::bins; 32 is the builder study's other setting: profiles/r06_builder_study.md)
-constexpr int kMaxDepth = 30;  // < kStackDepth (32)
+constexpr int kMaxDepth = 30;  // levels of the binary tree: a four-wide node leaves at most 3 stack entries per level, 90 <= kStackDepth + kStackOverflow (14 + 82, traverse.hpp); tests/test_stack_bound_cpu.py
 constexpr float kNodeCost = 0.7f;  // one two-box node test relative to one triangle test
 
 struct Box {
