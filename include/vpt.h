@@ -320,6 +320,24 @@ int vpt_set_scene(vpt_ctx* ctx, const vpt_scene_desc* scene);
  * if emission changed, resets accumulation. */
 int vpt_set_material(vpt_ctx* ctx, uint32_t index, const vpt_material* material);
 int vpt_get_material(const vpt_ctx* ctx, uint32_t index, vpt_material* out);
+/* Replaces the transforms of instances [first, first + count) of the installed scene (float[16] column-major each, as vpt_instance.transform)
+ * and nothing else: no tree build, no geometry upload.  The world triangles are re-transformed and the BVH is REFITTED on the device — same
+ * topology, every box recomputed bottom-up — and the tables derived from the matrices (normals, shading lines, lights) are filled again.
+ * Afterwards the context renders the scene vpt_set_scene would have installed from the same description with these transforms: with
+ * VPT_FLAG_LOCAL_HITS bit for bit at any size, without it exactly as far as two different trees agree (see that flag).  A refit does not restore
+ * the quality of a fresh build: a host that has carried things far should call vpt_set_scene again when it has the time.
+ * Accumulation is reset; lanes and spill regions, mesh and material indices, materials edited since, environment, volumes, atmosphere, camera and
+ * parameters stay; vpt_stats.set_scene_ms / bvh_build_ms keep their values and vpt_get_set_transforms_ms answers this call's.  Waits for batches in flight.
+ * VPT_ERR_NO_SCENE before the first vpt_set_scene; VPT_ERR_INVALID_ARGUMENT for a NULL array with count > 0 or a range past the instance count;
+ * count == 0 is VPT_OK and changes nothing, not even the accumulation.  The set of degenerate triangles (slivers, which the tree holds no leaf
+ * slot for) must stay what it was when the scene was installed: transforms that flatten a triangle, or revive one, return VPT_ERR_UNSUPPORTED —
+ * use vpt_set_scene.  A rejected or failed call leaves the previous transforms installed.  In the laboratory build vpt_lab_trace's
+ * VPT_TRACE_VOTE8 / VPT_TRACE_VOTE4S answer VPT_ERR_UNSUPPORTED after a move, until the next vpt_set_scene. */
+int vpt_set_instance_transforms(vpt_ctx* ctx, uint32_t first, uint32_t count, const float* transforms);
+/* Wall time of the last vpt_set_instance_transforms that moved something (re-transform, refit, derived tables); 0 before the first.  A call of its
+ * own and not a field of vpt_stats: that struct ends with set_environment_ms, and its size and layout stay what hosts were compiled against.  Reads
+ * the context only: it waits for nothing. */
+int vpt_get_set_transforms_ms(const vpt_ctx* ctx, double* out_ms);
 /* PathTracer::SetEnvMapFilepath (PathTracer.h:154) = LoadEnvironmentMap (PathTracer.cpp:1137-1332) with the .hdr already decoded by the
  * caller: replaces the environment map of the installed scene and nothing else.  env_rgba is what vpt_scene_desc.env_rgba is (RGBA32F,
  * alpha ignored, borrowed for the call); the importance, alias table and pdf are derived as vpt_set_scene derives them, so the context is

@@ -153,6 +153,13 @@ class PathTracer:
             raise ValueError("environment must be [h, w, 4], got %r" % (env.shape,))
         _check(self.lib, self.ctx, self.lib.vpt_set_environment(self.ctx, env.ctypes.data, env.shape[1], env.shape[0]), "vpt_set_environment")
 
+    def set_instance_transforms(self, first, matrices):
+        """vpt_set_instance_transforms: instances first, first + 1, ... take these 4x4 matrices (math layout, as Scene.instances holds them).  The
+        installed scene's BVH is refitted on the device: no tree build, no geometry upload."""
+        flat = [v for x in matrices for v in scenes.colmajor(x)]
+        arr = (C.c_float * max(len(flat), 1))(*flat)
+        _check(self.lib, self.ctx, self.lib.vpt_set_instance_transforms(self.ctx, first, len(matrices), arr if flat else None), "vpt_set_instance_transforms")
+
     def resize(self, w, h):
         _check(self.lib, self.ctx, self.lib.vpt_resize(self.ctx, w, h), "vpt_resize")
         self.width, self.height = w, h
@@ -235,6 +242,9 @@ class PathTracer:
         _check(self.lib, self.ctx, self.lib.vpt_get_stats(self.ctx, C.byref(s)), "vpt_get_stats")
         d = {k: getattr(s, k) for k, _ in _abi.Stats._fields_ if k not in ("kernel_launches", "kernel_ms", "stack_spills")}
         d["stack_spills"] = [int(s.stack_spills[0]), int(s.stack_spills[1])]
+        ms = C.c_double(0.0)                   # kept beside vpt_stats, not in it (vpt.h vpt_get_set_transforms_ms)
+        _check(self.lib, self.ctx, self.lib.vpt_get_set_transforms_ms(self.ctx, C.byref(ms)), "vpt_get_set_transforms_ms")
+        d["set_transforms_ms"] = ms.value
         d["kernel_launches"] = {n: int(s.kernel_launches[i]) for i, n in enumerate(_abi.KERNEL_NAMES)}
         d["kernel_ms"] = {n: float(s.kernel_ms[i]) for i, n in enumerate(_abi.KERNEL_NAMES)}
         return d

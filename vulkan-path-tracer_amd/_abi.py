@@ -208,6 +208,8 @@ PROTOTYPES = {
     "vpt_set_material": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Material)]),
     "vpt_get_material": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Material)]),
     "vpt_set_environment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "vpt_set_instance_transforms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "vpt_get_set_transforms_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "vpt_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vpt_default_atmosphere": (None, [C.POINTER(Atmosphere)]),
     "vpt_set_atmosphere": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -6,6 +6,7 @@
 // Output layout (device_types.hpp): 64 B four-wide quantised nodes (collapsed from the binary SAH tree), 48 B triangles
 // in leaf order, leaves of <= 4 triangles, binary depth bounded by kMaxDepth (bounds the traversal stack).
 #include "bvh_build.hpp"
+#include "bvh_refit.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -338,7 +339,7 @@ void build_bvh_ex(const std::vector<BvhTri>& tris_in, std::vector<BvhNode>& node
         r.tri = (uint32_t)i;
     }
     // Conservative padding so a box test can never cull a triangle the shared ray_triangle() accepts.
-    const float pad = 2.0e-5f * maxabs + 1.0e-6f;
+    const float pad = refit::pad_of(maxabs);
     auto empty_node = [&]() {
         BvhNode n; std::memset(&n, 0, sizeof(n));
         for (int a = 0; a < 3; a++) { n.set_step(a, 1u); n.lo[a] = 0xffffffffu; n.hi[a] = 0u; }  // inverted: never entered
@@ -378,37 +379,8 @@ void build_bvh_ex(const std::vector<BvhTri>& tris_in, std::vector<BvhNode>& node
     // emit: collapse the binary tree into 4-wide nodes (a node adopts its grandchildren, largest box first),
     // depth-first order; a leaf root gets a wrapper node.
     int max_depth = 0;
-    // Quantise the (padded) child boxes of one node: origin = their common lower corner, step = the smallest
-    // power of two whose 255 steps span them; lower planes round down, upper planes round up, checked in double
-    // (origin + q * step is exact there) so the decoded box is a superset of the fp32 one.
-    auto put_boxes = [&](BvhNode& n, BvhNodeWide& w, const Box* bx, int nk) {
-        for (int k = 0; k < nk; k++) {
-            w.minx[k] = bx[k].lo[0] - pad; w.miny[k] = bx[k].lo[1] - pad; w.minz[k] = bx[k].lo[2] - pad;
-            w.maxx[k] = bx[k].hi[0] + pad; w.maxy[k] = bx[k].hi[1] + pad; w.maxz[k] = bx[k].hi[2] + pad;
-        }
-        for (int a = 0; a < 3; a++) {
-            float lo = bx[0].lo[a] - pad, hi = bx[0].hi[a] + pad;
-            for (int k = 1; k < nk; k++) { lo = std::min(lo, bx[k].lo[a] - pad); hi = std::max(hi, bx[k].hi[a] + pad); }
-            const double org = lo, ext = (double)hi - (double)lo;
-            int e = 1;  // biased exponent, step = 2^(e-127)
-            if (ext > 0.0) { int ex; std::frexp(ext / 255.0, &ex); e = std::min(std::max(ex + 127, 1), 254); }
-            while (e < 254 && org + 255.0 * std::ldexp(1.0, e - 127) < (double)hi) e++;
-            const double step = std::ldexp(1.0, e - 127);
-            n.origin[a] = lo;
-            n.set_step(a, (uint32_t)e);
-            uint32_t wl = 0xffffffffu, wh = 0u;
-            for (int k = 0; k < nk; k++) {
-                const double cl = (double)(bx[k].lo[a] - pad), ch = (double)(bx[k].hi[a] + pad);
-                int ql = (int)std::floor((cl - org) / step), qh = (int)std::ceil((ch - org) / step);
-                ql = std::min(std::max(ql, 0), 255); qh = std::min(std::max(qh, 0), 255);
-                while (ql > 0 && org + ql * step > cl) ql--;
-                while (qh < 255 && org + qh * step < ch) qh++;
-                wl = (wl & ~(0xffu << (8 * k))) | (uint32_t)ql << (8 * k);
-                wh = (wh & ~(0xffu << (8 * k))) | (uint32_t)qh << (8 * k);
-            }
-            n.lo[a] = wl; n.hi[a] = wh;
-        }
-    };
+    // Quantise the (padded) child boxes of one node: bvh_refit.hpp put_boxes, the quantiser a refit on the device runs too.
+    auto put_boxes = [&](BvhNode& n, BvhNodeWide& w, const Box* bx, int nk) { refit::put_boxes(n, &w, bx, nk, pad); };
     struct Item { int tmp; int out; int depth; };
     std::vector<Item> work;
     nodes_out.push_back(empty_node()); wide_out.push_back(empty_wide());

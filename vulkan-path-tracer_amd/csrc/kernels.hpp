@@ -26,6 +26,10 @@ void launch_precompute_materials(hipStream_t s, const DeviceScene& sc, uint32_t 
 void launch_precompute_tri_ng(hipStream_t s, const DeviceScene& sc, float4* out);
 void launch_precompute_tri_shade(hipStream_t s, const DeviceScene& sc, float4* out);
 void launch_precompute_emissive(hipStream_t s, const DeviceScene& sc, EmissiveTri* out, uint32_t total);
+// vpt_set_instance_transforms (kernels_aux.hip): the leaf-ordered triangles under new matrices for instances [first, first + count) into `out`, with
+// words[0] raised if the sliver set would change and words[1] = bits of the scene extent; then one launch per height of the tree, lowest first
+void launch_retransform_tris(hipStream_t s, const DeviceScene& sc, uint32_t total_tris, uint32_t n_inst, uint32_t first, uint32_t count, const float* xf, BvhTri* out, uint32_t* words);
+void launch_refit_level(hipStream_t s, const DeviceScene& sc, const uint32_t* order, uint32_t begin, uint32_t end, const BvhTri* tris, float pad, float* boxes, BvhNode* nodes_out, BvhNodeWide* wide_out);
 size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene, int stack_rows);   // stack_rows: LDS entries per lane (traverse.hpp kStackDepth; k_whole: kWholeStackRows)
 size_t stack_overflow_bytes(uint32_t blocks);  // per-thread spill region of the traversal stacks for a grid of `blocks`
 #if VPT_LAB   // round 1's stage kernels (kernels_lab_r1.hip): laboratory build only

@@ -1,5 +1,6 @@
 // kernels_aux.hip — one-pass kernels beside the integrators: the resolve (running mean over a batch's frames), shard rows -> full image, the derived scene
-// tables (k_precompute_*, k_classify_instances), the closest-hit test hook k_trace_rays, and the LDS / stack-overflow size helpers every launcher shares.
+// tables (k_precompute_*, k_classify_instances), the refit behind vpt_set_instance_transforms (k_retransform_tris, k_refit_level), the closest-hit test hook k_trace_rays, and the LDS / stack-overflow size helpers every launcher shares.
+#include "bvh_refit.hpp"
 #include "kernels.hpp"
 #include "shade_core.hpp"
 #include "traverse.hpp"
@@ -165,6 +166,56 @@ void launch_precompute_tri_shade(hipStream_t s, const DeviceScene& sc, float4* o
 }
 void launch_precompute_emissive(hipStream_t s, const DeviceScene& sc, EmissiveTri* out, uint32_t total) {
     if (total) hipLaunchKernelGGL(k_precompute_emissive, dim3((total + 255) / 256), dim3(256), 0, s, sc, out, total);
+}
+
+// ------------------------------------------------------------------ moved instances: triangles re-transformed, boxes refitted (bvh_refit.hpp)
+// Instances [first, first + count) take the matrices at xf (16 floats each), the others keep InstanceDesc's: the installed tables are only read.
+__device__ inline void moved_triangle(const DeviceScene& sc, uint32_t inst, uint32_t prim, uint32_t first, uint32_t count, const float* xf, BvhTri& t) {
+    const InstanceDesc& in = sc.instances[inst];
+    const MeshDesc me = sc.meshes[in.mesh];
+    const uint32_t* idx = sc.indices + me.index_offset + prim * 3;
+    const vpt_vertex* vb = sc.vertices + me.vertex_offset;
+    refit::world_triangle(inst - first < count ? xf + (size_t)(inst - first) * 16 : in.xform, vb[idx[0]].position, vb[idx[1]].position, vb[idx[2]].position, t);
+}
+// Thread i: leaf slot i gets its world triangle under the new matrices (prim / inst / gid kept), and global triangle i, if it has no slot (a sliver
+// the tree was built without), is looked at too.  words[0] is raised when the sliver set would change — a slot's triangle is degenerate now, or a
+// sliver no longer is: the tree has no place for either — and words[1] takes the bits of the largest |coordinate| of the slots' triangles.
+__global__ __launch_bounds__(256) void k_retransform_tris(DeviceScene sc, uint32_t total_tris, uint32_t n_inst, uint32_t first, uint32_t count, const float* xf, BvhTri* out, uint32_t* words) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t flag = 0u, extent = 0u;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; pass++) {   // 0: leaf slot i; 1: global triangle i, when it has no slot
+        BvhTri t;
+        if (pass == 0) {
+            if (i >= sc.tri_count) continue;
+            t = sc.tris[i];
+        } else {
+            if (i >= total_tris || sc.tri_slot_of_gid[i] != 0xffffffffu) continue;
+            uint32_t lo = 0u, hi = n_inst;   // the last instance whose first triangle id is <= i
+            while (hi - lo > 1u) { const uint32_t mid = (lo + hi) / 2u; if (sc.instances[mid].tri_offset <= i) lo = mid; else hi = mid; }
+            t.inst = lo; t.prim = i - sc.instances[lo].tri_offset;
+        }
+        moved_triangle(sc, t.inst, t.prim, first, count, xf, t);
+        const bool sliver = refit::degenerate(t);
+        if (pass == 0) { out[i] = t; extent = vptfp::f2u(refit::max_abs_coord(t)); }
+        if (sliver == (pass == 0)) flag = 1u;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t e = __shfl_down(extent, o), f = __shfl_down(flag, o); extent = e > extent ? e : extent; flag |= f; }
+    if ((threadIdx.x & 63u) == 0u) { if (flag) atomicOr(&words[0], 1u); if (extent) atomicMax(&words[1], extent); }
+}
+// One height of the tree, one thread per node (bvh_refit.hpp refit_node); the launch before this one wrote the boxes of every lower node.
+__global__ __launch_bounds__(256) void k_refit_level(DeviceScene sc, const uint32_t* order, uint32_t begin, uint32_t end, const BvhTri* tris, float pad, float* boxes, BvhNode* nodes_out, BvhNodeWide* wide_out) {
+    const uint32_t j = begin + blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= end) return;
+    const uint32_t i = order[j];
+    if (i < sc.node_count) refit::refit_node(i, sc.nodes, sc.nodes_wide, sc.node_count, tris, sc.tri_count, pad, boxes, nodes_out, wide_out);
+}
+void launch_retransform_tris(hipStream_t s, const DeviceScene& sc, uint32_t total_tris, uint32_t n_inst, uint32_t first, uint32_t count, const float* xf, BvhTri* out, uint32_t* words) {
+    const uint32_t n = sc.tri_count > total_tris ? sc.tri_count : total_tris;
+    if (n) hipLaunchKernelGGL(k_retransform_tris, dim3(cdiv(n, 256)), dim3(256), 0, s, sc, total_tris, n_inst, first, count, xf, out, words);
+}
+void launch_refit_level(hipStream_t s, const DeviceScene& sc, const uint32_t* order, uint32_t begin, uint32_t end, const BvhTri* tris, float pad, float* boxes, BvhNode* nodes_out, BvhNodeWide* wide_out) {
+    if (end > begin) hipLaunchKernelGGL(k_refit_level, dim3(cdiv(end - begin, 256)), dim3(256), 0, s, sc, order, begin, end, tris, pad, boxes, nodes_out, wide_out);
 }
 
 // Test hook: the closest-hit traversal on caller-supplied rays.

@@ -1,4 +1,4 @@
-// scene_prep.hpp — everything vpt_set_scene / vpt_set_material / vpt_set_environment decide and compute on the host before a byte reaches the device: the checks
+// scene_prep.hpp — everything vpt_set_scene / vpt_set_material / vpt_set_environment / vpt_set_instance_transforms decide and compute on the host before a byte reaches the device: the checks
 // of a scene description, the pooled and flattened geometry, the texel pool, the environment's alias table and pdf, the emissive-mesh
 // list, and the predicates the grids are picked by (host arithmetic of PathTracer.cpp restated).  Plain C++ on plain values, no context and
 // no HIP call: vpt_api.hip uploads what this prepares, and tests/test_scene_prep_cpu.py holds every rejection to its code and message and
@@ -42,6 +42,20 @@ inline bool material_textures_ok(const vpt_material& m, uint32_t texture_count) 
 }
 inline bool is_emissive(const vpt_material& m) { return m.emissive_color[0] != 0.0f || m.emissive_color[1] != 0.0f || m.emissive_color[2] != 0.0f; }
 
+// What vpt_set_scene and vpt_set_instance_transforms demand of ONE instance matrix (float[16], column-major): nothing.  Any sixteen floats are
+// accepted, a singular matrix included (its triangles are slivers and are dropped, its inverse is whatever inverse3x3_from_mat4 makes of it), as
+// vpt_set_scene always has.  The one place a demand would go, so that both callers refuse the same matrices with the same message.
+inline Verdict check_instance_transform(const float* /*m*/) { return kAccepted; }
+// Every reason vpt_set_instance_transforms rejects its arguments for, in the order it reports them (instance_count: of the installed scene).
+// count == 0 passes whatever the rest says: such a call changes nothing.
+inline Verdict check_instance_transforms(uint32_t first, uint32_t count, const float* transforms, uint32_t instance_count) {
+    if (count == 0) return kAccepted;
+    if (!transforms) return {VPT_ERR_INVALID_ARGUMENT, "no instance transforms"};
+    if (first > instance_count || count > instance_count - first) return {VPT_ERR_INVALID_ARGUMENT, "instance range out of bounds"};   // (first + count may wrap)
+    for (uint32_t i = 0; i < count; i++) { const Verdict v = check_instance_transform(transforms + (size_t)i * 16); if (v.code) return v; }
+    return kAccepted;
+}
+
 // Every reason vpt_set_scene rejects a description for, in the order it reports them.  What passes here can only fail on the device.
 inline Verdict check(const vpt_scene_desc& sd) {
     if (sd.mesh_count == 0 || !sd.meshes) return {VPT_ERR_INVALID_ARGUMENT, "No meshes found in scene"};  // PathTracer.cpp:180
@@ -63,6 +77,7 @@ inline Verdict check(const vpt_scene_desc& sd) {
     for (uint32_t i = 0; i < sd.instance_count; i++) {
         if (sd.instances[i].mesh_index >= sd.mesh_count) return {VPT_ERR_INVALID_ARGUMENT, "instance mesh index out of range"};
         if (sd.instances[i].material_index >= sd.material_count) return {VPT_ERR_INVALID_ARGUMENT, "Mesh instance has invalid material index"};  // PathTracer.cpp:454
+        { const Verdict v = check_instance_transform(sd.instances[i].transform); if (v.code) return v; }
     }
     for (uint32_t t = 0; t < sd.texture_count; t++) {
         const vpt_texture& tx = sd.textures[t];

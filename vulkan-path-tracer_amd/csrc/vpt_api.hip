@@ -14,6 +14,7 @@
 #include <rccl/rccl.h>
 
 #include "bvh_build.hpp"
+#include "bvh_refit.hpp"
 #include "kernels.hpp"
 #include "path_plan.hpp"
 #include "scene_prep.hpp"
@@ -112,6 +113,10 @@ struct vpt_ctx {
     scene::EmissiveList emissive;
     uint64_t total_vertices = 0, total_indices = 0;
     uint32_t bvh_depth = 0;
+    uint32_t total_tris = 0;                // global triangle ids of the scene, slivers included
+    std::vector<uint32_t> refit_level_off;  // heights of the tree: nodes refit_order[off[h] .. off[h + 1]) have height h (bvh_refit.hpp levels)
+    const uint32_t* refit_order = nullptr;  // on the device, freed with the scene
+    bool lab_trees_stale = false;           // instances have moved since vpt_set_scene: bvh_input is gone and the trace lab's lazily built trees cannot be made
 
     DeviceScene dsc{};
     std::vector<void*> scene_allocs;
@@ -176,7 +181,7 @@ struct vpt_ctx {
     unsigned long long* d_spill_count = nullptr;
     bool spill_dirty = true;         // traversal kernels have run since the spill regions were last counted (vpt_get_stats counts lazily)
     uint64_t spill_cached[2] = {0, 0};
-    double set_scene_ms = 0.0, bvh_build_ms = 0.0, set_environment_ms = 0.0;
+    double set_scene_ms = 0.0, bvh_build_ms = 0.0, set_environment_ms = 0.0, set_transforms_ms = 0.0;
 
     int shade_media_blocks = 768, media_tail_blocks = 768;
     uint32_t class_present = 0x1fu;   // shade classes some instance of the scene belongs to (bit kShadeMiss always set): the others get no launch
@@ -214,15 +219,18 @@ struct vpt_ctx {
 
 namespace {
 
-#define HIPCHK(ctx, call)                                                                                      \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) {                                                                                \
-            char buf_[512];                                                                                    \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            (ctx)->err = buf_;                                                                                 \
-            return (e_ == hipErrorOutOfMemory) ? VPT_ERR_OUT_OF_MEMORY : VPT_ERR_DEVICE;                       \
-        }                                                                                                      \
+// A failed HIP call: its text, HIP's message and the line go to vpt_last_error (one copy of the formatting, not one per call site: the product
+// library's size is bounded, tests/test_abi.py).
+__attribute__((noinline, cold)) int hip_failed(vpt_ctx* c, hipError_t e, const char* call, int line) {
+    char buf[512];
+    snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", call, hipGetErrorString(e), __FILE__, line);
+    c->err = buf;
+    return (e == hipErrorOutOfMemory) ? VPT_ERR_OUT_OF_MEMORY : VPT_ERR_DEVICE;
+}
+#define HIPCHK(ctx, call)                                                        \
+    do {                                                                         \
+        hipError_t e_ = (call);                                                  \
+        if (e_ != hipSuccess) return hip_failed((ctx), e_, #call, __LINE__);     \
     } while (0)
 
 int fail(vpt_ctx* c, int code, const char* msg) { c->err = msg; return code; }
@@ -252,26 +260,35 @@ hipError_t memset_now(hipStream_t s, void* p, int v, size_t n) {
 
 // A scene table of n (at least one) elements, freed with the scene: DeviceScene's pointer to it and, for a table that is written after the
 // upload, the writable one (vpt_ctx::Writable) are set here, from one allocation sized by their own element type.
-template <class T>
-int alloc_table(vpt_ctx* c, size_t n, const T** out, T** writable = nullptr) {
-    T* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(T)));
+// (the work is done once, on bytes; the templates below only size and type it)
+int alloc_bytes(vpt_ctx* c, size_t bytes, void** out) {
+    void* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, bytes));
     c->scene_allocs.push_back(d);
     *out = d;
-    if (writable) *writable = d;
     return VPT_OK;
+}
+int upload_bytes(vpt_ctx* c, const void* src, size_t bytes, size_t total_bytes, void** out) {
+    int rc = alloc_bytes(c, total_bytes, out);
+    if (rc) return rc;
+    HIPCHK(c, memset_now(c->main.stream, *out, 0, total_bytes));
+    if (bytes) HIPCHK(c, hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
+    return VPT_OK;
+}
+template <class T>
+int alloc_table(vpt_ctx* c, size_t n, const T** out, T** writable = nullptr) {
+    void* d = nullptr;
+    int rc = alloc_bytes(c, std::max<size_t>(n, 1) * sizeof(T), &d);
+    if (d) { *out = (T*)d; if (writable) *writable = (T*)d; }
+    return rc;
 }
 // ... holding the n elements at src, zeros behind them up to min_elems.
 template <class T>
 int upload(vpt_ctx* c, const T* src, size_t n, const T** out, size_t min_elems = 1, T** writable = nullptr) {
-    const size_t elems = std::max(n, min_elems);
-    T* local = nullptr;
-    T** d = writable ? writable : &local;
-    int rc = alloc_table(c, elems, out, d);
-    if (rc) return rc;
-    HIPCHK(c, memset_now(c->main.stream, *d, 0, elems * sizeof(T)));
-    if (n) HIPCHK(c, hipMemcpy(*d, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return VPT_OK;
+    void* d = nullptr;
+    int rc = upload_bytes(c, src, n * sizeof(T), std::max(n, min_elems) * sizeof(T), &d);
+    if (d) { *out = (T*)d; if (writable) *writable = (T*)d; }
+    return rc;
 }
 template <class T>
 int upload(vpt_ctx* c, const std::vector<T>& v, const T** out, size_t min_elems = 1, T** writable = nullptr) {
@@ -288,6 +305,13 @@ void free_scene(vpt_ctx* c) {
     free_spill(c->main);   // (sized by the scene's grids)
     c->has_scene = false;
     c->dw = vpt_ctx::Writable{};
+}
+// Tables of the scene that have been replaced: freed now and taken out of scene_allocs (whose order means nothing: free_scene frees them all).
+void release_tables(vpt_ctx* c, std::initializer_list<const void*> gone) {
+    for (size_t i = 0; i < c->scene_allocs.size();) {
+        void*& p = c->scene_allocs[i];
+        if (p && std::find(gone.begin(), gone.end(), (const void*)p) != gone.end()) { (void)hipFree(p); p = c->scene_allocs.back(); c->scene_allocs.pop_back(); } else i++;
+    }
 }
 void free_lab(vpt_ctx* c) {
     for (void* p : {(void*)c->lab_ro, (void*)c->lab_rd, (void*)c->lab_hit, (void*)c->lab_hinst, (void*)c->lab_order}) if (p) (void)hipFree(p);
@@ -1136,6 +1160,12 @@ int upload_scene(vpt_ctx* c, const vpt_scene_desc& sd, scene::HostScene& hs, con
     D.node_count = (uint32_t)bvh.nodes.size(); D.tri_count = (uint32_t)bvh.leaf_tris.size();
     D.scene_extent = bvh_max_abs_coord(hs.tris);   // the number the builder padded the boxes by (slab.hpp: the reach of the fma box test)
     if ((rc = upload(c, scene::slot_of_gid(bvh.leaf_tris, hs.total_tris), &D.tri_slot_of_gid))) return rc;
+    {   // the order vpt_set_instance_transforms refits the nodes in
+        std::vector<uint32_t> order;
+        refit::levels(bvh.nodes, order, c->refit_level_off);
+        if ((rc = upload(c, order, &c->refit_order))) return rc;
+    }
+    c->total_tris = hs.total_tris; c->lab_trees_stale = false;
     if ((rc = upload(c, hs.verts, &D.vertices))) return rc;
     if ((rc = upload(c, hs.idx, &D.indices))) return rc;
     if ((rc = upload(c, hs.meshes, &D.meshes))) return rc;
@@ -1327,14 +1357,75 @@ int vpt_set_environment(vpt_ctx* c, const float* env_rgba, uint32_t env_width, u
     const void* old_alias = c->dsc.alias;
     int rc = upload_environment(c, env, alias, env_width, env_height, scene::env_is_black(env));
     if (rc) return rc;
-    for (size_t i = 0; i < c->scene_allocs.size();) {   // (the order of scene_allocs means nothing: free_scene frees them all)
-        void*& p = c->scene_allocs[i];
-        if (p == old_env || p == old_alias) { (void)hipFree(p); p = c->scene_allocs.back(); c->scene_allocs.pop_back(); } else i++;
-    }
+    release_tables(c, {old_env, old_alias});
     c->state_gen++;            // a captured batch holds the old tables' addresses
     update_depth_bounded(c);   // env_black is one of the conditions of the PLAIN instantiation
     reset_accum(c);
     c->set_environment_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return VPT_OK;
+}
+int vpt_set_instance_transforms(vpt_ctx* c, uint32_t first, uint32_t count, const float* transforms) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
+    const scene::Verdict verdict = scene::check_instance_transforms(first, count, transforms, (uint32_t)c->instances.size());
+    if (verdict.code) return fail(c, verdict.code, verdict.msg);
+    if (count == 0) return VPT_OK;
+    { int rd = quiesce(c); if (rd) return rd; }   // batches in flight read the tables replaced below
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceScene& D = c->dsc;
+    hipStream_t s = c->main.stream;
+    // ---- staged: the triangles under the new matrices and the refitted nodes; the installed tables are only read until both are whole
+    const size_t held = c->scene_allocs.size();
+    const BvhTri* tris = nullptr; const BvhNode* nodes = nullptr; const BvhNodeWide* wide = nullptr;
+    BvhTri* w_tris = nullptr; BvhNode* w_nodes = nullptr; BvhNodeWide* w_wide = nullptr;
+    char* scratch = nullptr;   // 2 words (sliver flag, extent) | the matrices | 6 floats per node
+    const size_t xf_bytes = (size_t)count * 64, scratch_bytes = 256 + xf_bytes + (size_t)D.node_count * 24;
+    int rc = alloc_table(c, D.tri_count, &tris, &w_tris);
+    if (!rc) rc = alloc_table(c, D.node_count, &nodes, &w_nodes);
+    if (!rc && D.nodes_wide) rc = alloc_table(c, D.node_count, &wide, &w_wide);
+    uint32_t words[2] = {0u, 0u};
+    auto staged = [&]() -> int {
+        HIPCHK(c, hipMalloc((void**)&scratch, scratch_bytes));
+        HIPCHK(c, hipMemsetAsync(scratch, 0, 256, s));
+        HIPCHK(c, hipMemcpyAsync(scratch + 256, transforms, xf_bytes, hipMemcpyHostToDevice, s));
+        launch_retransform_tris(s, D, c->total_tris, (uint32_t)c->instances.size(), first, count, (const float*)(scratch + 256), w_tris, (uint32_t*)scratch);
+        HIPCHK(c, hipMemcpyAsync(words, scratch, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (words[0]) return fail(c, VPT_ERR_UNSUPPORTED, "these transforms change which triangles are degenerate, and a refit keeps the tree's leaves: use vpt_set_scene");
+        const float pad = refit::pad_of(vptfp::u2f(words[1]));
+        for (size_t h = 0; h + 1 < c->refit_level_off.size(); h++)   // lowest first; the kernel boundaries order the heights
+            launch_refit_level(s, D, c->refit_order, c->refit_level_off[h], c->refit_level_off[h + 1], w_tris, pad, (float*)(scratch + 256 + xf_bytes), w_nodes, w_wide);
+        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipGetLastError());
+        return VPT_OK;
+    };
+    if (!rc) rc = staged();
+    if (scratch) (void)hipFree(scratch);
+    if (rc) {   // rejected or failed: the previous transforms stay installed, untouched
+        while (c->scene_allocs.size() > held) { (void)hipFree(c->scene_allocs.back()); c->scene_allocs.pop_back(); }
+        return rc;
+    }
+    // ---- swapped in
+    release_tables(c, {D.tris, D.nodes, D.nodes_wide, D.nodes8, D.nodes4s});
+    D.tris = tris; D.nodes = nodes; D.nodes_wide = wide; D.nodes8 = nullptr; D.nodes4s = nullptr;
+    D.scene_extent = vptfp::u2f(words[1]);
+    c->bvh_input = std::vector<BvhTri>(); c->lab_trees_stale = true; c->stats.bvh8_nodes = 0;   // (the trace lab's other trees were built from the old triangles)
+    c->state_gen++;   // a captured batch holds the old tables' addresses
+    for (uint32_t i = 0; i < count; i++) {
+        InstanceDesc& d = c->instances[first + i];
+        memcpy(d.xform, transforms + (size_t)i * 16, 64);
+        vptfp::inverse3x3_from_mat4(d.xform, d.inv3);
+    }
+    HIPCHK(c, hipMemcpy(const_cast<InstanceDesc*>(D.instances) + first, c->instances.data() + first, (size_t)count * sizeof(InstanceDesc), hipMemcpyHostToDevice));
+    // ---- everything derived from the instances' matrices: the per-triangle shading tables, the light tables
+    launch_precompute_tri_ng(s, D, c->dw.tri_ng);
+    launch_precompute_tri_shade(s, D, c->dw.tri_shade);
+    build_emissive(c);
+    if ((rc = upload_emissive(c))) return rc;
+    if ((rc = refresh_material_tables(c))) return rc;
+    HIPCHK(c, hipGetLastError());
+    reset_accum(c);
+    c->set_transforms_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return VPT_OK;
 }
 int vpt_get_material(const vpt_ctx* c, uint32_t index, vpt_material* out) {
@@ -1857,6 +1948,11 @@ int vpt_get_stats(vpt_ctx* c, vpt_stats* out) {
     *out = s;
     return VPT_OK;
 }
+int vpt_get_set_transforms_ms(const vpt_ctx* c, double* out_ms) {
+    if (!c || !out_ms) return VPT_ERR_INVALID_ARGUMENT;
+    *out_ms = c->set_transforms_ms;
+    return VPT_OK;
+}
 int vpt_reset_stats(vpt_ctx* c) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
     { int rd = quiesce(c); if (rd) return rd; }
@@ -2055,6 +2151,7 @@ int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t
     if (c->lds_scene) return fail(c, VPT_ERR_UNSUPPORTED, "the trace lab runs on scenes whose BVH lives in memory");
     if (c->lab_n == 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_lab_trace before vpt_lab_set_rays");
     { int rd = quiesce(c); if (rd) return rd; }
+    if ((variant == VPT_TRACE_VOTE4S || variant == VPT_TRACE_VOTE8) && c->lab_trees_stale) return fail(c, VPT_ERR_UNSUPPORTED, "instances have moved since vpt_set_scene: this variant's tree is gone until the next one");
     if (variant == VPT_TRACE_VOTE4S && !c->dsc.nodes4s) {   // split-order experiment: the same binary tree collapsed pair-wise with order tables, over the same leaf-ordered triangles
         std::vector<BvhNode> n4, n4s; std::vector<BvhNodeWide> w4; std::vector<BvhTri> lt; int d = 0;
         BvhBuildOptions opt; opt.spatial_splits = c->sbvh; opt.nodes4s = &n4s;

@@ -44,7 +44,7 @@ void PathTracer::Swap(PathTracer& o) noexcept {
     swap(m_TotalVertexCount, o.m_TotalVertexCount); swap(m_TotalIndexCount, o.m_TotalIndexCount);
     swap(m_CameraViewInverse, o.m_CameraViewInverse); swap(m_CameraProjectionInverse, o.m_CameraProjectionInverse);
     swap(m_Materials, o.m_Materials); swap(m_MaterialNames, o.m_MaterialNames); swap(m_Scene, o.m_Scene);
-    swap(m_Env, o.m_Env); swap(m_EnvW, o.m_EnvW); swap(m_EnvH, o.m_EnvH);
+    swap(m_Env, o.m_Env); swap(m_EnvW, o.m_EnvW); swap(m_EnvH, o.m_EnvH); swap(m_PendingTransforms, o.m_PendingTransforms);
     swap(m_LutR, o.m_LutR); swap(m_LutO, o.m_LutO); swap(m_LutI, o.m_LutI);
     swap(m_LookupTablePath, o.m_LookupTablePath); swap(m_EnvMapFilepath, o.m_EnvMapFilepath); swap(m_Output, o.m_Output);
     swap(m_Volumes, o.m_Volumes); swap(m_EnableAtmosphere, o.m_EnableAtmosphere); swap(m_Atmosphere, o.m_Atmosphere);
@@ -70,6 +70,8 @@ void PathTracer::SetScene(const std::string& sceneFilePath) {
 void PathTracer::SetScene(const SceneAsset& sceneIn) {
     ResetPathTracing();
     m_Scene = sceneIn;
+    for (const auto& t : m_PendingTransforms) if (t.first < m_Scene.MeshInstances.size()) m_Scene.MeshInstances[t.first].Transform = t.second;   // SetInstanceTransforms before SetScene
+    m_PendingTransforms.clear();
     if (m_Scene.Cameras.empty()) {  // PathTracer.cpp:171-178
         CameraAsset cam;
         cam.AspectRatio = 16.0f / 9.0f; cam.FOV = 45.0f;
@@ -237,6 +239,18 @@ void PathTracer::SetEnvironmentMap(const std::vector<float>& rgba, uint32_t widt
     m_Env = rgba; m_EnvW = width; m_EnvH = height;
     // with a scene installed only the environment's tables are replaced (LoadEnvironmentMap touches no BLAS / TLAS either); before SetScene the map waits for it
     if (m_Ctx) Check(vpt_set_environment(m_Ctx, m_Env.data(), m_EnvW, m_EnvH), "vpt_set_environment");
+    ResetPathTracing();
+}
+void PathTracer::SetInstanceTransforms(uint32_t first, const std::vector<Mat4>& transforms) {
+    if (!m_Ctx) {   // before SetScene the matrices wait for it, as SetEnvironmentMap's map does
+        for (size_t i = 0; i < transforms.size(); i++) m_PendingTransforms.push_back({first + (uint32_t)i, transforms[i]});
+        return;
+    }
+    if (first > m_Scene.MeshInstances.size() || transforms.size() > m_Scene.MeshInstances.size() - first) throw std::runtime_error("SetInstanceTransforms: instance range out of bounds");
+    std::vector<float> flat;
+    for (const Mat4& t : transforms) flat.insert(flat.end(), t.m, t.m + 16);
+    Check(vpt_set_instance_transforms(m_Ctx, first, (uint32_t)transforms.size(), flat.data()), "vpt_set_instance_transforms");
+    for (size_t i = 0; i < transforms.size(); i++) m_Scene.MeshInstances[first + i].Transform = transforms[i];
     ResetPathTracing();
 }
 void PathTracer::SetEnvMapFilepath(const std::string& filePath) {  // PathTracer.cpp:1137-1164 (ImportTexture of an .hdr)

@@ -11,6 +11,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/vpt.h"
@@ -144,6 +145,10 @@ public:
     // RGBA32F, width*height*4 floats (the reference loads a .hdr file: SetEnvMapFilepath, PathTracer.cpp:1137-1164)
     void SetEnvironmentMap(const std::vector<float>& rgba, uint32_t width, uint32_t height);
     void SetEnvMapFilepath(const std::string& filePath);  // PathTracer.h:154: a Radiance .hdr file
+    // EXTENSION, no upstream member (the reference rebuilds its TLAS from SetScene): mesh instances first, first + 1, ... take these transforms.  With a
+    // scene installed this is vpt_set_instance_transforms — a BVH refit on the device, no tree build, no geometry upload; before SetScene the
+    // matrices wait for the scene and replace what it holds for those instances.
+    void SetInstanceTransforms(uint32_t first, const std::vector<Mat4>& transforms);
     [[nodiscard]] const std::string& GetEnvMapFilepath() const { return m_EnvMapFilepath; }
 
     [[nodiscard]] uint32_t GetSamplesAccumulated() const { return m_SamplesAccumulated; }
@@ -198,6 +203,7 @@ private:
     std::vector<std::string> m_MaterialNames;
     SceneAsset m_Scene;
     std::vector<float> m_Env; uint32_t m_EnvW = 1, m_EnvH = 1;
+    std::vector<std::pair<uint32_t, Mat4>> m_PendingTransforms;  // SetInstanceTransforms before SetScene
     std::vector<float> m_LutR, m_LutO, m_LutI;
     std::string m_LookupTablePath;
     std::string m_EnvMapFilepath;
