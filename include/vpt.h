@@ -288,7 +288,7 @@ typedef struct vpt_stats {
     uint32_t reserved0;
     uint32_t graph_launches;   /* batches replayed from a captured hipGraph by vpt_render_async since vpt_reset_stats */
     /* Words of the traversal stacks' global SPILL regions written since vpt_set_scene (a lane's stack is 14 LDS entries, deeper entries
-     * spill to a per-thread region; vpt_api.hip keeps one region per concurrently running traversal grid): [0] the context's main
+     * spill to a per-thread region; api_context.hip keeps one region per concurrently running traversal grid): [0] the context's main
      * stream, [1] the second stream the shadow kernels of bounce k run on beside the extend of bounce k + 1.  Counted from the regions
      * themselves (they are preset to a pattern no stack entry can be), so the figure belongs to the product kernels, not to counting variants. */
     uint64_t stack_spills[2];

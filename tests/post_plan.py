@@ -1,4 +1,4 @@
-"""The fused bloom/tonemap schedule restated in plain Python: which launches enqueue_post (csrc/vpt_api.hip) makes for an image
+"""The fused bloom/tonemap schedule restated in plain Python: which launches enqueue_post (csrc/api_post.hip) makes for an image
 size and a mip_count, and the tile ranges the two chain kernels (csrc/kernels_post.hip) evaluate per block.  Written from the
 C++ rules; it never calls into the library.  The constants are parsed out of the C++ sources, so a change of one of them moves
 the plan — and the case selection of tests/test_gpu_post_shapes.py that tests/test_post_plan_cpu.py checks — with it.

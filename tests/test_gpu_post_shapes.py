@@ -1,6 +1,6 @@
 """Every shape of the fused bloom/tonemap schedule against the oracle.
 
-enqueue_post (csrc/vpt_api.hip) assembles the fused schedule per call from the image's mip sizes and mip_count; which kernels run,
+enqueue_post (csrc/api_post.hip) assembles the fused schedule per call from the image's mip sizes and mip_count; which kernels run,
 with how many levels each, is restated by tests/post_plan.py.  CASES is chosen with that restatement so that every launch kind and
 level count the schedule can produce is run here — tests/test_post_plan_cpu.py fails, naming the element, if the table stops
 covering what a sweep of sizes reaches — and each case proves on the device, through the launch counters, that it ran the launches

@@ -1,6 +1,6 @@
 """The traversal stacks' SPILL path.  A lane's stack is 14 LDS entries; deeper entries go to a per-thread region in global memory, and
 the shadow kernels of bounce k run on a second stream beside the extend kernel of bounce k + 1, each grid with a spill region of its
-own (vpt_api.hip Lane::spill2; round 2 shared one region between them: a race only a spilling scene can show).  No shipped scene
+own (api_ctx.hpp Lane::spill2; round 2 shared one region between them: a race only a spilling scene can show).  No shipped scene
 spills, so this one is built to: 40,000 triangles in 20,000 stacked sheets that every ray from the floor below crosses — a closest-hit
 search pushes up to three siblings per level on its way down to the nearest sheet, an any-hit search towards the light above likewise.
 vpt_stats.stack_spills counts the spill words the product kernels wrote (per region), so the test knows the path was taken."""

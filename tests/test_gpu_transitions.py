@@ -1,5 +1,5 @@
 """One long-lived context walked through changes of schedule class, in lockstep with the oracle: the same call sequence goes to a
-vpt.PathTracer and an oracle.Oracle, and after every render step the images are equal bit for bit.  The host layer (vpt_api.hip) picks a
+vpt.PathTracer and an oracle.Oracle, and after every render step the images are equal bit for bit.  The host layer (api_render.hip) picks a
 schedule per batch from the context's history — whole-path launch, fused k_bounce, streams with regeneration, media streams, the k_finish
 tail; the path buffers' frames_alloc / resident_alloc; media_frames, class queues, captured graphs — and every other GPU test builds a fresh
 context per configuration.  Also the four instantiations of k_finish<COUNT, STRICT> (kernels_finish.hip): image, ray statistics and visit

@@ -1,4 +1,4 @@
-"""The sizing of the path buffers (vulkan-path-tracer_amd/csrc/path_plan.hpp, the arithmetic vpt_api.hip's check_render_size / batch_cap /
+"""The sizing of the path buffers (vulkan-path-tracer_amd/csrc/path_plan.hpp, the arithmetic api_context.hip's check_render_size / batch_cap /
 ensure_path_buffers call) on the host: tests/tools/path_plan_driver.cpp wraps it in a modelled context whose device memory is a fixed number
 of bytes, and these tests walk it through the sequences an editor makes on one long-lived context — a long batch of one schedule class
 followed by a batch of another — over image sizes, free memory and explicit / library-chosen sizes.  Invariants:
@@ -45,7 +45,7 @@ def lib(tmp_path_factory):
     return L
 
 
-# what the context's scene / parameters / configuration make of the policy (vpt_api.hip policy_of, regen_allowed, whole_possible)
+# what the context's scene / parameters / configuration make of the policy (api_context.hip policy_of -> path_plan.hpp policy_of: regen, whole_frames)
 SCHEDULES = {
     "whole":   dict(regen=0, whole=WHOLE_ALL, sidx=0, media=0),   # LDS scene, AUTO: one whole-path launch per batch
     "spp2":    dict(regen=0, whole=0, sidx=1, media=0),           # LDS scene, samples_per_frame 2: fused per-bounce kernels, every sample resident

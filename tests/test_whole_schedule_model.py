@@ -1,4 +1,4 @@
-"""The tile schedule of the whole-path launch (kernels_whole.hip k_whole, vpt_api.hip batch_begin), restated: wave w of W takes tiles w, w + W, ... for
+"""The tile schedule of the whole-path launch (kernels_whole.hip k_whole, api_render.hip batch_begin), restated: wave w of W takes tiles w, w + W, ... for
 `static_rounds` rounds without an atomic, the tiles behind them come `chunk` at a time through a counter (optionally shrinking towards the end), and a wave
 alternates shade / refill / trace steps until it has nothing left.  Whatever the interleaving of the waves, the path lengths and the schedule parameters, every
 sample of the batch must be started exactly once and finished exactly once, and the hit ring (128 entries per wave) must never overflow.  CPU only: this pins
@@ -9,7 +9,7 @@ import pytest
 
 
 def static_rounds_for(n_slots, grid_blocks, mode):
-    """vpt_api.hip batch_begin: tiles of 64 samples, `rounds` per wave; mode 0 / 3: the first round static, 1: all but the last, 2: half."""
+    """api_render.hip batch_begin: tiles of 64 samples, `rounds` per wave; mode 0 / 3: the first round static, 1: all but the last, 2: half."""
     n_waves = grid_blocks * 4
     rounds = ((n_slots + 63) // 64) // n_waves
     if mode in (0, 3):

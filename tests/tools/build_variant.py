@@ -1,6 +1,6 @@
 """Builds variants/<name>.so: the product library with extra -D definitions (A/B builds for tests/tools/ab_variants.sh; variants/ is git-ignored
 but travels to the GPU box).  Objects that do not see the definition are shared with the product build.
-    python tests/tools/build_variant.py <name> [-DVPT_X=1 ...] [--sources vpt_api.hip,kernels_whole.hip]   (default: every source is recompiled)"""
+    python tests/tools/build_variant.py <name> [-DVPT_X=1 ...] [--sources api_render.hip,kernels_whole.hip]   (default: every source is recompiled)"""
 import importlib, os, shutil, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

@@ -1,6 +1,6 @@
 // Host driver of vulkan-path-tracer_amd/csrc/path_plan.hpp for tests/test_path_plan_cpu.py: one modelled context whose device memory
 // is a fixed number of bytes.  The plan's allocations succeed when the buffers they ask for fit; batch_cap, grow and fit_batch are the
-// header's; pp_next_batch restates only the order in which vpt_api.hip's next_batch calls them.  Built as a shared library and driven through ctypes.
+// header's; pp_next_batch restates only the order in which api_render.hip's next_batch calls them.  Built as a shared library and driven through ctypes.
 #include <cstdint>
 
 #include "path_plan.hpp"
@@ -49,7 +49,7 @@ void* pp_create(uint64_t px, uint32_t cfg_frames, uint32_t cfg_resident, uint64_
     return m;
 }
 void pp_destroy(void* h) { delete (Model*)h; }
-// what scene, parameters and configuration allow (vpt_api.hip policy_of) and the per-sample words the next batch touches
+// what scene, parameters and configuration allow (api_context.hip policy_of) and the per-sample words the next batch touches
 void pp_policy(void* h, int has_scene, int regen, uint32_t whole_frames, int sidx, int media) {
     Model& m = *(Model*)h;
     m.p.has_scene = has_scene != 0; m.p.regen = regen != 0; m.p.whole_frames = whole_frames;
@@ -59,7 +59,7 @@ void pp_set_avail(void* h, uint64_t bytes) { ((Model*)h)->avail = bytes; }
 void pp_resize(void* h, uint64_t px, uint64_t free_bytes) { Model& m = *(Model*)h; m.avail = free_bytes; fresh_buffers(m, px, free_bytes); }
 uint32_t pp_batch_cap(void* h) { Model& m = *(Model*)h; return batch_cap(m.p, m.s); }
 uint32_t pp_resident_for(void* h, uint32_t frames) { Model& m = *(Model*)h; return resident_frames_for(m.p, m.s.frames_in_flight, frames); }
-// vpt_api.hip next_batch: *nf frames of `left`, buffers grown for them; returns 0 or the failed allocation's AllocResult
+// api_render.hip next_batch: *nf frames of `left`, buffers grown for them; returns 0 or the failed allocation's AllocResult
 int pp_next_batch(void* h, uint32_t left, uint32_t* nf) {
     Model& m = *(Model*)h;
     *nf = 0;

@@ -1,6 +1,6 @@
 // rccl_stub — a file-backed stand-in for the five RCCL entry points libvpt_hip.so calls, for ONE purpose: running the library's
 // real vpt_comm_init / vpt_comm_gather_shards / row re-interleave with world size 2 on a box that has one GPU (RCCL itself refuses
-// two ranks on one device, so on such a box the N > 1 path of csrc/vpt_api.hip would otherwise never execute).  Test utility only:
+// two ranks on one device, so on such a box the N > 1 path of csrc/api_comm.hip would otherwise never execute).  Test utility only:
 // built on demand by tests/test_gpu_comm.py and put in front of librccl with LD_PRELOAD; nothing in the product links it.
 //
 // Rendezvous: a directory named by VPT_RCCL_STUB_DIR.  ncclGather = every rank copies its send buffer to the host and publishes

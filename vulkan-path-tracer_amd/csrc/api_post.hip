@@ -1,0 +1,152 @@
+// api_post.hip — the post-process schedule (bloom chain + tonemap, kernels_post.hip) and the RGBA8 output.
+#include "api_ctx.hpp"
+
+using namespace vpt::api;
+
+// ---- helpers of this file alone
+namespace {
+
+int ensure_post_buffers(vpt_ctx* c) {
+    const uint32_t w = c->P.width, h = c->P.height;
+    if (c->post_w == w && c->post_h == h && !c->mips.empty()) return VPT_OK;
+    for (float* m : c->mips) (void)hipFree(m);
+    c->mips.clear(); c->mip_sizes.clear();
+    if (c->post_out) (void)hipFree(c->post_out);
+    c->post_out = nullptr;
+    uint32_t cw = w, ch = h;
+    for (int i = 0; i < 10; i++) {  // PostProcessor.cpp:136-157 (MAX_BLOOM_LEVELS = 10)
+        float* m = nullptr;
+        HIPCHK(c, hipMalloc((void**)&m, (size_t)cw * ch * 16));
+        c->mips.push_back(m); c->mip_sizes.push_back({cw, ch});
+        if (cw % 2 != 0) cw -= 1;
+        if (ch % 2 != 0) ch -= 1;
+        cw /= 2; ch /= 2;
+        if (cw < 2 || ch < 2) break;
+    }
+    HIPCHK(c, hipMalloc((void**)&c->post_out, (size_t)w * h * 4));
+    c->post_w = w; c->post_h = h;
+    return VPT_OK;
+}
+
+// PostProcessor::PostProcess, PostProcessor.cpp:193-246: the launches, on the context's stream, nothing waited for.
+int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
+    int rc = ensure_post_buffers(c);
+    if (rc) return rc;
+    hipStream_t s = c->main.stream;
+    const float* hdr = whole_image(c);
+    const uint32_t W = c->P.width, H = c->P.height;
+    uint32_t mip_count = std::max(1u, std::min(pp->mip_count, (uint32_t)c->mips.size()));
+    const bool linear_tap = (c->params.flags & VPT_FLAG_TONEMAP_LINEAR_BLOOM_TAP) != 0;
+    auto MW = [&](uint32_t i) { return c->mip_sizes[i].first; };
+    auto MH = [&](uint32_t i) { return c->mip_sizes[i].second; };
+    if (pp->schedule == VPT_POST_REFERENCE_PASSES) {   // PostProcessor.cpp:193-246 pass by pass: threshold, down x (n-1), up x (n-1), tonemap
+        TIMED(c, s, VPT_K_BLOOM, launch_bloom_threshold(s, hdr, c->mips[0], W, H, pp->bloom_threshold, pp->falloff_range));
+        for (uint32_t i = 1; i < mip_count; i++)
+            TIMED(c, s, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
+        for (uint32_t i = mip_count - 1; i > 0; i--)
+            TIMED(c, s, VPT_K_BLOOM, launch_bloom_up(s, c->mips[i], MW(i), MH(i), c->mips[i - 1], MW(i - 1), MH(i - 1), pp->bloom_strength));
+        TIMED(c, s, VPT_K_TONEMAP, launch_tonemap(s, hdr, c->mips[0], c->post_out, W, H, pp->exposure, pp->gamma, linear_tap));
+    } else {
+        // Fused schedule, same values (kernels_post.hip): mip 0 is never materialised unless the caller asks for it.
+        //   T = first mip the one-launch tail keeps in LDS (<= kBloomTailMaxTexels texels, and >= 2: its base mip must exist in memory)
+        uint32_t T = mip_count;
+        for (uint32_t i = 2; i < mip_count; i++) if ((uint64_t)MW(i) * MH(i) <= kBloomTailMaxTexels) { T = i; break; }
+        if (mip_count - T > kBloomTailMaxLevels) T = mip_count;   // cannot happen with <= 10 mips; the per-pass kernels cover it
+        if (mip_count >= 2) TIMED(c, s, VPT_K_BLOOM, launch_bloom_down_first(s, hdr, W, H, c->mips[1], MW(1), MH(1), pp->bloom_strength, pp->bloom_threshold, pp->falloff_range));
+        {   // down-samples between mip 1 and the tail's base: one launch each while the levels are large, the last (up to three, at most
+            // kBloomDownChainTexels texels in the first of them) in one launch
+            const uint32_t last = std::min(T, mip_count) - 1;   // last level produced here
+            uint32_t i = 2;
+            while (i <= last) {
+                const uint32_t left = last - i + 1;
+                if (left >= 2 && left <= kBloomDownChainMax && (uint64_t)MW(i) * MH(i) <= kBloomDownChainTexels) {
+                    float* lv[kBloomDownChainMax]; uint32_t lw[kBloomDownChainMax], lh[kBloomDownChainMax];
+                    for (uint32_t k = 0; k < left; k++) { lv[k] = c->mips[i + k]; lw[k] = MW(i + k); lh[k] = MH(i + k); }
+                    TIMED(c, s, VPT_K_BLOOM, launch_bloom_down_chain(s, c->mips[i - 1], MW(i - 1), MH(i - 1), lv, lw, lh, left, pp->bloom_strength));
+                    i += left;
+                } else {
+                    TIMED(c, s, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
+                    i++;
+                }
+            }
+        }
+        uint32_t up_from = std::min(T, mip_count) - 1;   // the highest level that is final once the tail has run
+        if (T < mip_count) {
+            uint32_t tw[kBloomTailMaxLevels], th[kBloomTailMaxLevels];
+            for (uint32_t i = T; i < mip_count; i++) { tw[i - T] = MW(i); th[i - T] = MH(i); }
+            const bool staged = bloom_tail_is_staged(MW(T - 1), MH(T - 1));
+            TIMED(c, s, VPT_K_BLOOM, launch_bloom_tail(s, c->mips[T - 1], c->mips[T], MW(T - 1), MH(T - 1), tw, th, mip_count - T, pp->bloom_strength));
+            if (staged) up_from = T;   // the staged tail leaves mip T finished in memory and mip T - 1 as the down-samples left it
+        }
+        // up-samples of the levels between the tail and mip 1: up to kBloomChainMax of them per launch, only the lowest level written
+        // (the levels between are read by nothing else)
+        for (uint32_t top = up_from; top > 1;) {
+            const uint32_t n = std::min(top - 1u, kBloomChainMax), base = top - n;
+            if (n == 1) {
+                TIMED(c, s, VPT_K_BLOOM, launch_bloom_up(s, c->mips[top], MW(top), MH(top), c->mips[base], MW(base), MH(base), pp->bloom_strength));
+            } else {
+                float* lv[kBloomChainMax + 1]; uint32_t lw[kBloomChainMax + 1], lh[kBloomChainMax + 1];
+                for (uint32_t k = 0; k <= n; k++) { lv[k] = c->mips[base + k]; lw[k] = MW(base + k); lh[k] = MH(base + k); }
+                TIMED(c, s, VPT_K_BLOOM, launch_bloom_up_chain(s, lv, lw, lh, n, pp->bloom_strength));
+            }
+            top = base;
+        }
+        TIMED(c, s, VPT_K_TONEMAP, launch_post_final(s, hdr, mip_count >= 2 ? c->mips[1] : nullptr, mip_count >= 2 ? MW(1) : 0u, mip_count >= 2 ? MH(1) : 0u,
+                                                  bloom0 ? c->mips[0] : nullptr, c->post_out, W, H, pp->bloom_threshold, pp->falloff_range, pp->bloom_strength,
+                                                  pp->exposure, pp->gamma, linear_tap));
+    }
+    return VPT_OK;
+}
+int post_preconditions(vpt_ctx* c) {
+    if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
+    if (c->P.shard_count > 1 && !c->full_valid) return fail(c, VPT_ERR_INVALID_ARGUMENT, "sharded context: call vpt_assemble_shards first");
+    return VPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vpt_postprocess(vpt_ctx* c, const vpt_post_params* pp, uint8_t* out8, float* bloom0) {
+    if (!c || !pp || !out8) return VPT_ERR_INVALID_ARGUMENT;
+    int rc = post_preconditions(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if ((rc = drain(c))) return rc;
+    if ((rc = enqueue_post(c, pp, bloom0 != nullptr))) return rc;
+    const uint32_t W = c->P.width, H = c->P.height;
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    collect_timing(c);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(out8, c->post_out, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+    if (bloom0) HIPCHK(c, hipMemcpy(bloom0, c->mips[0], (size_t)W * H * 16, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
+// PostProcess(cmd) as the reference has it: recorded behind the render on the same stream, the RGBA8 image stays on the device.
+int vpt_postprocess_device(vpt_ctx* c, const vpt_post_params* pp, void* rgba8_device, uint64_t* ticket) {
+    if (!c || !pp) return VPT_ERR_INVALID_ARGUMENT;
+    int rc = post_preconditions(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if ((rc = finish_outstanding(c))) return rc;   // the image must be complete: an unfinished batch is finished first
+    if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));   // the latest frame was resolved on another lane
+    if ((rc = enqueue_post(c, pp, false))) return rc;
+    if (rgba8_device) HIPCHK(c, hipMemcpyAsync(rgba8_device, c->post_out, (size_t)c->P.width * c->P.height * 4, hipMemcpyDeviceToDevice, c->main.stream));
+    HIPCHK(c, hipEventRecord(c->ev_post, c->main.stream));
+    c->post_pending = true;
+    const uint64_t t = issue_ticket(c, c->main.stream);
+    if (ticket) *ticket = t;
+    return VPT_OK;
+}
+const void* vpt_output_device(vpt_ctx* c) { return c ? c->post_out : nullptr; }
+int vpt_get_output(vpt_ctx* c, uint8_t* out8) {
+    if (!c || !out8) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c->post_out) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_get_output before the first post-process");
+    { int rd = quiesce(c); if (rd) return rd; }
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    HIPCHK(c, hipMemcpy(out8, c->post_out, (size_t)c->post_w * c->post_h * 4, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
+}  // extern "C"

@@ -203,7 +203,7 @@ struct RenderParams {
     // dispatch_base / frame_base arguments, so that one captured batch serves every frame
     const uint32_t* dispatch_base_dev;
     // sincos_ of the four sky-rotation angles the shaders use, evaluated once per vpt_set_params with the shared fp32 contract
-    // (vpt_api.hip sync_params): {sin, cos} of azimuth, altitude (ImportanceSampleEnvMap) and of -altitude, -azimuth (Miss)
+    // (api_context.hip sync_params): {sin, cos} of azimuth, altitude (ImportanceSampleEnvMap) and of -altitude, -azimuth (Miss)
     float sky_rot[8];
 };
 
@@ -307,7 +307,7 @@ struct StreamCounters {
 };
 
 // Stream appends (vote.hpp WaveAppender): chunk size of the wave-private chunked appends, and the queue length below which a launch
-// appends exactly instead (no holes).  The host sizes the streams' slack for unwritten chunk tails by these (vpt_api.hip alloc_path_buffers).
+// appends exactly instead (no holes).  The host sizes the streams' slack for unwritten chunk tails by these (api_context.hip alloc_path_buffers).
 constexpr uint32_t kAppendChunk = 256;
 constexpr uint32_t kAppendExactBelow = 1u << 21;
 // The fused per-bounce kernel's threshold.  Measured at 2^18 (round 4, profiles/r04_latency_probe_exact18.json: the 2M-path launches of a

@@ -32,6 +32,11 @@ void launch_retransform_tris(hipStream_t s, const DeviceScene& sc, uint32_t tota
 void launch_refit_level(hipStream_t s, const DeviceScene& sc, const uint32_t* order, uint32_t begin, uint32_t end, const BvhTri* tris, float pad, float* boxes, BvhNode* nodes_out, BvhNodeWide* wide_out);
 size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene, int stack_rows);   // stack_rows: LDS entries per lane (traverse.hpp kStackDepth; k_whole: kWholeStackRows)
 size_t stack_overflow_bytes(uint32_t blocks);  // per-thread spill region of the traversal stacks for a grid of `blocks`
+// ... preset to a word no stack entry can be (a node index of 2.1e9; leaf codes are negative), so that what was spilled can be counted:
+// *out += the words of region[0 .. words) that no longer hold it
+constexpr int kSpillPatternByte = 0x7f;
+constexpr uint32_t kSpillPattern = 0x7f7f7f7f;
+void launch_count_spilled(hipStream_t s, const uint32_t* region, uint32_t words, unsigned long long* out);
 #if VPT_LAB   // round 1's stage kernels (kernels_lab_r1.hip): laboratory build only
 void launch_raygen(hipStream_t s, const RenderParams& P, const PathState& ps, uint32_t* queue, Counters* ctr, uint32_t n_slots, uint32_t dispatch_base);
 void launch_prepare(hipStream_t s, Counters* ctr, uint32_t parity);

@@ -1,5 +1,5 @@
 // kernels_aux.hip — one-pass kernels beside the integrators: the resolve (running mean over a batch's frames), shard rows -> full image, the derived scene
-// tables (k_precompute_*, k_classify_instances), the refit behind vpt_set_instance_transforms (k_retransform_tris, k_refit_level), the closest-hit test hook k_trace_rays, and the LDS / stack-overflow size helpers every launcher shares.
+// tables (k_precompute_*, k_classify_instances), the refit behind vpt_set_instance_transforms (k_retransform_tris, k_refit_level), the closest-hit test hook k_trace_rays, the LDS / stack-overflow size helpers every launcher shares, and the count of spilled stack words (k_count_spilled).
 #include "bvh_refit.hpp"
 #include "kernels.hpp"
 #include "shade_core.hpp"
@@ -243,5 +243,15 @@ size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene, int stack_rows)
     return b;
 }
 size_t stack_overflow_bytes(uint32_t blocks) { return (size_t)blocks * kTraverseBlock * kOverflowStride * 4; }   // (traverse.hpp: the longest per-thread region of any kernel)
+// What the traversal kernels have written into a spill region (vpt_get_stats).
+__global__ __launch_bounds__(256) void k_count_spilled(const uint32_t* p, uint32_t n, unsigned long long* out) {
+    unsigned long long cnt = 0ull;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) cnt += p[i] != kSpillPattern ? 1ull : 0ull;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    if ((threadIdx.x & 63u) == 0u && cnt) atomicAdd(out, cnt);
+}
+void launch_count_spilled(hipStream_t s, const uint32_t* region, uint32_t words, unsigned long long* out) {
+    hipLaunchKernelGGL(k_count_spilled, dim3(1024), dim3(256), 0, s, region, words, out);
+}
 
 }  // namespace vpt

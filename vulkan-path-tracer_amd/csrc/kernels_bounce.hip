@@ -19,7 +19,7 @@ namespace vpt {
 // then a handful of LDS reads, so a separate extend/connect stage would only move records through HBM):
 // it reads a queued path's records A, B, T, L, does the whole bounce, and writes them back for survivors.
 // PLAIN: the scene class set this instantiation serves — every material's textures are 1x1 and the environment is black (the Cornell
-// box; chosen by vpt_set_scene / vpt_set_material, vpt_api.hip scene_is_plain).  The general kernel skips the texture taps and the
+// box; chosen by vpt_set_scene / vpt_set_material / vpt_set_environment, api_scene.hip update_depth_bounded by scene_prep.hpp plain).  The general kernel skips the texture taps and the
 // environment sampler through uniform branches; here they are not compiled in at all (a quarter of the general kernel's instructions).
 template <bool LDS_SCENE, bool COUNT, bool FIRST, bool VOL, bool STRICT, bool PLAIN = false>
 __global__ __launch_bounds__(kTraverseBlock, 3) void k_bounce(DeviceScene sc, RenderParams P, PathState ps, StreamState ss, const uint32_t* queue,

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void k_tonemap(const float4* hdr, const float4
     out[(size_t)y * w + x] = make_uchar4(unorm8(c.x), unorm8(c.y), unorm8(c.z), 255);
 }
 
-// ---- fused schedule (vpt_api.hip vpt_postprocess): the same values through fewer passes over memory.
+// ---- fused schedule (api_post.hip enqueue_post): the same values through fewer passes over memory.
 //   first down-sample reads the HDR image and thresholds on the fly          (k_bloom_down<true>: mip 0 is never stored)
 //   mips small enough for one CU's LDS go down AND up inside one launch       (k_bloom_tail: 10 launches of ~8 us become 1)
 //   the last up-sample, the threshold of the texel it is added to and the tonemap are one kernel (k_post_final)

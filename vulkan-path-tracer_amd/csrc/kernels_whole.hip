@@ -175,7 +175,7 @@ __device__ __forceinline__ V3 whole_finish(const RenderParams& P, const PathStat
     return light;
 }
 // Samples are dealt in tiles of 64 (consecutive pixels of a row).  Wave w of W takes tiles w, w + W, ... for the first `static_rounds` rounds
-// without an atomic, and the tiles behind them `chunk_tiles` at a time through ctr->extend_head (the host picks both: vpt_api.hip whole_schedule).
+// without an atomic, and the tiles behind them `chunk_tiles` at a time through ctr->extend_head (the host picks both: api_render.hip batch_begin).
 // (Measured and not kept: one-wave blocks, which leave the CU as soon as THEIR paths have ended and so let the next frame's launch in earlier —
 // a 1-frame launch at 1080p 542 us against 509 us, and slower with two or three frames in flight too: profiles/r04_whole_lanes.json.)
 template <bool COUNT, bool STRICT, bool PLAIN>

@@ -1,7 +1,7 @@
 // scene_prep.hpp — everything vpt_set_scene / vpt_set_material / vpt_set_environment / vpt_set_instance_transforms decide and compute on the host before a byte reaches the device: the checks
 // of a scene description, the pooled and flattened geometry, the texel pool, the environment's alias table and pdf, the emissive-mesh
 // list, and the predicates the grids are picked by (host arithmetic of PathTracer.cpp restated).  Plain C++ on plain values, no context and
-// no HIP call: vpt_api.hip uploads what this prepares, and tests/test_scene_prep_cpu.py holds every rejection to its code and message and
+// no HIP call: api_scene.hip uploads what this prepares, and tests/test_scene_prep_cpu.py holds every rejection to its code and message and
 // every table to the oracle's own writing of it (oracle.cpp build_tris / build_env / build_emissive), bit for bit, without a device.
 #pragma once
 #include <algorithm>
