@@ -104,21 +104,26 @@ def base_scene():
     return S, copy.deepcopy(S.Scene.load(os.path.join(GOLDEN, "cornell_box_glass.npz")))
 
 
-def build(normal_map=False, emissive=False, affine=False, env=False, compact=False):
-    """The Cornell box with the glass sphere, two boxes, and whatever the flags add.  -> (scene, info).
-    compact: no sphere and one box (mirrored, non-uniformly scaled), so that the BVH is small enough to ride in LDS and the
-    whole-path / fused per-bounce kernels serve the scene."""
-    S, sc = base_scene()
-    info = dict(per_hit_normal=[], normal_1x1=[], mirrored=[], nonuniform=[], sheared=[], z_normal=[], emitters={})
-    # wall uvs on the wall's two long axes: u in [-0.12, 0.12], v in [-0.15, 0.15] (negative: REPEAT, a window round the normal map's wrap corner)
+def wall_uvs(sc, origin, span):
+    """Gives the five Cornell walls (meshes 0 .. 4, whose fixtures carry no uvs) uvs on the wall's two long axes: from `origin` to `origin + span`."""
     for mi in range(5):
         v, idx = sc.meshes[mi]
         v = v.copy()
         p = v["position"].astype(np.float64)
         axes = np.argsort(p.max(0) - p.min(0))[1:]
         lo, hi = p.min(0), p.max(0)
-        v["texcoord"] = np.array([-0.12, -0.15]) + np.array([0.24, 0.3]) * (p[:, axes] - lo[axes]) / (hi[axes] - lo[axes])
+        v["texcoord"] = np.array(origin) + np.array(span) * (p[:, axes] - lo[axes]) / (hi[axes] - lo[axes])
         sc.meshes[mi] = (v, idx)
+
+
+def build(normal_map=False, emissive=False, affine=False, env=False, compact=False):
+    """The Cornell box with the glass sphere, two boxes, and whatever the flags add.  -> (scene, info).
+    compact: no sphere and one box (mirrored, non-uniformly scaled), so that the BVH is small enough to ride in LDS and the
+    whole-path / fused per-bounce kernels serve the scene."""
+    S, sc = base_scene()
+    info = dict(per_hit_normal=[], normal_1x1=[], mirrored=[], nonuniform=[], sheared=[], z_normal=[], emitters={})
+    # u in [-0.12, 0.12], v in [-0.15, 0.15] (negative: REPEAT, a window round the normal map's wrap corner)
+    wall_uvs(sc, (-0.12, -0.15), (0.24, 0.3))
     m_box = box_mesh(sc)
     mats = sc.materials
     glass = 4

@@ -463,6 +463,28 @@ def test_depth_bounded_needs_transmission_density_and_anisotropy_together(lib, v
     assert bounded() == 1
 
 
+def test_depth_bounded_on_the_material_sweep(lib, vpt):
+    """The sets of tests/material_sweep.py, whole and member by member, and the scenes built from them: the host predicate equals the
+    restatement the GPU tests assert their premises with.  The media set holds a medium at anisotropy exactly 1 (bounded on its own),
+    at -1 and at 0 (unbounded), and one whose density is 1e-3 under transmission 0.5 (unbounded)."""
+    import material_sweep as M
+
+    def bounded(mats):
+        sc = vpt.scenes.Scene()
+        sc.materials = list(mats)
+        desc, keep = sc.to_desc()
+        return lib.sp_depth_bounded(C.cast(desc.materials, C.c_void_p), desc.material_count) == 1
+
+    for name in M.SETS:
+        mats = M.members(name)
+        assert bounded(mats) == M.depth_bounded(mats) == (name != "medium_edges"), name
+        for k, m in enumerate(mats):
+            assert bounded([m]) == M.depth_bounded([m]), (name, k)
+        for sc in (M.walls(name, "black"), M.sphere(name, 2, "lit")):
+            assert bounded(sc.materials) == M.depth_bounded(sc.materials) == (name != "medium_edges"), name
+    assert [bounded([m]) for m in M.members("medium_edges")] == [True, False, False, False, False]
+
+
 def test_rides_in_lds_up_to_3072_bytes(lib):
     node, tri = lib.sp_node_bytes(), lib.sp_tri_bytes()
     assert (node, tri) == (128, 48)
