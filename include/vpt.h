@@ -351,8 +351,9 @@ int vpt_set_environment(vpt_ctx* ctx, const float* env_rgba, uint32_t env_width,
 /* ---- participating media: homogeneous box volumes ---------------------------------
  * PathTracer::Volume / VolumeGPU (PathTracer.h:36-74, 341-400) as the shaders read it (Volume.slang:19-52).
  * corner_min / corner_max are the WORLD-space box, i.e. Position + Corner * Scale already applied
- * (PathTracer.h:395-396).  Heterogeneous volumes take their density from a DENSE grid (vpt_add_density_grid below:
- * the OpenVDB / NanoVDB tree of the reference, densified), including emission from temperature / blackbody.
+ * (PathTracer.h:395-396).  Heterogeneous volumes take their density from a grid, dense (vpt_add_density_grid below: the
+ * OpenVDB / NanoVDB tree of the reference, densified) or in the tree's own 8x8x8 leaves (vpt_add_density_bricks), including emission from
+ * temperature / blackbody.
  * The integrator side is RayGen.slang:162-380 (free-flight sampling per box,
  * nearest scatter vs. distance to geometry, NEE towards sky and emissive meshes through every box's Beer-Lambert
  * transmittance, phase-function scattering) and ClosestHit.slang:332-333,364 (volumes shadow surface NEE). */
@@ -365,7 +366,7 @@ typedef struct vpt_volume {
     float anisotropy;            /* g of Henyey-Greenstein / Draine */
     float alpha;                 /* Draine alpha */
     float droplet_size;          /* HG+Draine fit parameter d (micrometres) */
-    int32_t density_data_index;  /* -1: homogeneous; >= 0: a grid added with vpt_add_density_grid */
+    int32_t density_data_index;  /* -1: homogeneous; >= 0: a grid added with vpt_add_density_grid / _bricks */
     int32_t approximated_scattering;          /* ApproximatedScatteringForClouds: g^(1+depth), density * falloff^depth */
     float approximated_scattering_falloff;
     float grid_sharpness;                     /* GridSharpness (heterogeneous only) */
@@ -394,7 +395,36 @@ int vpt_set_volumes(vpt_ctx* ctx, const vpt_volume* volumes, uint32_t count);
  * vpt_volume.density_data_index) or a negative VPT_ERR_*.  At most VPT_MAX_DENSITY_GRIDS grids. */
 #define VPT_MAX_DENSITY_GRIDS 16
 int vpt_add_density_grid(vpt_ctx* ctx, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, const float* density);
+/* AddDensityDataToVolume (PathTracer.cpp:1347-1516) with the grid handed over as the NanoVDB tree holds it (nanovdb::LeafNode, the 8x8x8 nodes
+ * SampleNanoVDBBuffer reads through its accessor, Volume.slang:69-117): brick_count bricks of VPT_BRICK_DIM^3 voxels and a background of 0.
+ * The index box is [0, dim) as for vpt_add_density_grid; brick (bx, by, bz) covers voxels [8bx, 8bx + 8) x [8by, 8by + 8) x [8bz, 8bz + 8), its
+ * 512 values x fastest, then y, then z.  Voxels of a brick outside the index box are ignored (never read, not part of any maximum); a voxel no
+ * brick covers has density 0.  The grid IS the dense grid with those values: MaxDensityInTheGrid and the block maxima (:1425-1442) equal, bit for
+ * bit, what vpt_add_density_grid computes from the equivalent dense array, and every later image is bit-identical to that grid's — but the dense
+ * box is never formed, on the host or on the device: the work is proportional to brick_count and the device holds brick_count * 2 KB of values
+ * plus one 32-bit word per brick cell.  Returns the grid's index, in the index space of vpt_add_density_grid (both kinds count towards
+ * VPT_MAX_DENSITY_GRIDS and vpt_clear_density_grids frees both), or a negative VPT_ERR_*: VPT_ERR_INVALID_ARGUMENT for a NULL pointer, a zero
+ * dimension, a brick coordinate at or beyond ceil(dim / 8), a coordinate given twice, brick_count == 0 or no positive value inside the box;
+ * VPT_ERR_LIMIT for more than VPT_MAX_DENSITY_GRIDS grids, more than 2^26 brick cells or more than 2^22 bricks.  Waits for batches in flight; a
+ * rejected or failed call leaves the list of grids as it was. */
+#define VPT_BRICK_DIM 8u            /* a brick is 8 x 8 x 8 voxels = one NanoVDB leaf node */
+int vpt_add_density_bricks(vpt_ctx* ctx, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z,
+                           uint32_t brick_count, const uint32_t* brick_coords /* 3 per brick: bx, by, bz */,
+                           const float* brick_values /* 512 per brick, x fastest, then y, then z */);
 int vpt_clear_density_grids(vpt_ctx* ctx);   /* RemoveDensityDataFromVolume for all; volumes must not reference grids afterwards */
+/* What a grid added with either call holds (the reference keeps the same facts per volume: the NanoVDB buffer's size and
+ * MaxDensityInTheGrid, PathTracer.cpp:1416-1423). */
+typedef struct vpt_density_grid_info {
+    uint32_t dim[3];
+    uint32_t brick_count;   /* 0: dense */
+    uint64_t device_bytes;  /* values + brick table + block maxima */
+    float max_density;
+    uint32_t reserved;
+} vpt_density_grid_info;
+int vpt_get_density_grid_info(const vpt_ctx* ctx, uint32_t grid, vpt_density_grid_info* out);
+/* Test hook, like vpt_trace_rays: the raw value the device lookup (SampleNanoVDBBuffer's accessor.getValue, Volume.slang:112) returns at n voxels
+ * (ijk: 3 int32 each, host memory; clamped to the index box as the sampler clamps). */
+int vpt_read_density_grid(vpt_ctx* ctx, uint32_t grid, const int32_t* ijk, uint32_t n, float* out_host);
 /* SetPhaseFunction (PathTracer.h:106); default VPT_PHASE_HENYEY_GREENSTEIN (PathTracer.h:219).  Resets accumulation. */
 int vpt_set_phase_function(vpt_ctx* ctx, uint32_t phase_function);
 /* ---- atmosphere ----------------------------------------------------------------------

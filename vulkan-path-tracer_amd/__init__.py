@@ -75,6 +75,19 @@ def calculate_lut(kind, size, sample_count, time_ms=0, device=0):
     return out
 
 
+def bricks_of(grid):
+    """A dense float32 [z, y, x] grid as 8x8x8 bricks, every brick whose voxels are all 0 dropped: ((dim_x, dim_y, dim_z), uint32 [n, 3] coordinates
+    (bx, by, bz), float32 [n, 8, 8, 8] values [brick, z, y, x]; a partial brick's voxels outside the box hold 0) — the arguments of add_density_bricks."""
+    g = np.ascontiguousarray(grid, np.float32)
+    dz, dy, dx = g.shape
+    cz, cy, cx = (-(-n // 8) for n in g.shape)
+    padded = np.zeros((cz * 8, cy * 8, cx * 8), np.float32)
+    padded[:dz, :dy, :dx] = g
+    cells = padded.reshape(cz, 8, cy, 8, cx, 8).transpose(0, 2, 4, 1, 3, 5)   # [cell z, cell y, cell x, z, y, x]
+    bz, by, bx = np.nonzero((cells != 0).any(axis=(3, 4, 5)))
+    return (dx, dy, dz), np.stack([bx, by, bz], axis=1).astype(np.uint32), np.ascontiguousarray(cells[bz, by, bx])
+
+
 class PathTracer:
     """Mirror of the reference's PathTracer + PostProcessor call surface over the C-ABI."""
 
@@ -126,6 +139,37 @@ class PathTracer:
         if rc < 0:
             _check(self.lib, self.ctx, rc, "vpt_add_density_grid")
         return rc
+
+    def add_density_bricks(self, dims, coords, values):
+        """vpt_add_density_bricks: the grid as a NanoVDB tree holds it.  dims: (dim_x, dim_y, dim_z) of the index box; coords: uint32 [n, 3] brick
+        coordinates (bx, by, bz); values: float32 [n, 8, 8, 8] = [brick, z, y, x] raw densities -> grid index (the index space of add_density_grid)."""
+        c = np.ascontiguousarray(coords, np.uint32).reshape(-1, 3)
+        v = np.ascontiguousarray(values, np.float32).reshape(-1, 8, 8, 8)
+        if len(c) != len(v):
+            raise ValueError("%d brick coordinates for %d bricks of values" % (len(c), len(v)))
+        rc = self.lib.vpt_add_density_bricks(self.ctx, int(dims[0]), int(dims[1]), int(dims[2]), len(c), c.ctypes.data if len(c) else None, v.ctypes.data if len(c) else None)
+        if rc < 0:
+            _check(self.lib, self.ctx, rc, "vpt_add_density_bricks")
+        return rc
+
+    def add_density_grid_sparse(self, grid):
+        """add_density_grid's image from the bricks of `grid` (float32 [z, y, x]) that hold a value other than 0: see bricks_of."""
+        return self.add_density_bricks(*bricks_of(grid))
+
+    def density_grid_info(self, index):
+        """vpt_get_density_grid_info -> {"dim": (x, y, z), "brick_count" (0: dense), "device_bytes", "max_density"}."""
+        i = _abi.DensityGridInfo()
+        _check(self.lib, self.ctx, self.lib.vpt_get_density_grid_info(self.ctx, index, C.byref(i)), "vpt_get_density_grid_info")
+        return {"dim": tuple(i.dim), "brick_count": i.brick_count, "device_bytes": i.device_bytes, "max_density": np.float32(i.max_density)}
+
+    def read_density_grid(self, index, ijk):
+        """vpt_read_density_grid (test hook): the raw values the device lookup returns at voxels ijk (int32 [..., 3] = x, y, z; clamped to the index box)."""
+        q = np.ascontiguousarray(ijk, np.int32)
+        if q.ndim < 1 or q.shape[-1] != 3:
+            raise ValueError("ijk must be [..., 3], got %r" % (q.shape,))
+        out = np.zeros(q.shape[:-1], np.float32)
+        _check(self.lib, self.ctx, self.lib.vpt_read_density_grid(self.ctx, index, q.ctypes.data, out.size, out.ctypes.data), "vpt_read_density_grid")
+        return out
 
     def clear_density_grids(self):
         _check(self.lib, self.ctx, self.lib.vpt_clear_density_grids(self.ctx), "vpt_clear_density_grids")

@@ -199,6 +199,10 @@ class Hit(C.Structure):
                 ("instance", C.c_uint32)]
 
 
+class DensityGridInfo(C.Structure):
+    _fields_ = [("dim", C.c_uint32 * 3), ("brick_count", C.c_uint32), ("device_bytes", C.c_uint64), ("max_density", C.c_float), ("reserved", C.c_uint32)]
+
+
 # every symbol include/vpt.h declares, with (restype, argtypes)
 PROTOTYPES = {
     "vpt_create": (C.c_void_p, [C.POINTER(Config), C.POINTER(C.c_int)]),
@@ -214,7 +218,10 @@ PROTOTYPES = {
     "vpt_default_atmosphere": (None, [C.POINTER(Atmosphere)]),
     "vpt_set_atmosphere": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_add_density_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "vpt_add_density_bricks": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vpt_clear_density_grids": (C.c_int, [C.c_void_p]),
+    "vpt_get_density_grid_info": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(DensityGridInfo)]),
+    "vpt_read_density_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vpt_set_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "vpt_set_phase_function": (C.c_int, [C.c_void_p, C.c_uint32]),
     "vpt_set_params": (C.c_int, [C.c_void_p, C.POINTER(Params)]),

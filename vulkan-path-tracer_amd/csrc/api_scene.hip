@@ -1,11 +1,12 @@
 // api_scene.hip — everything that installs or edits what a batch only reads: vpt_set_scene (what scene_prep.hpp prepares on the host and
-// bvh_build.cpp builds, uploaded), its partial updates (material, environment, instance transforms by a device refit: bvh_refit.hpp), the media,
-// and the closest-hit test hook.
+// bvh_build.cpp builds, uploaded), its partial updates (material, environment, instance transforms by a device refit: bvh_refit.hpp), the media
+// (density grids as grid_prep.hpp prepares them), and the test hooks.
 #include <chrono>
 
 #include "api_ctx.hpp"
 #include "bvh_build.hpp"
 #include "bvh_refit.hpp"
+#include "grid_prep.hpp"
 
 using namespace vpt::api;
 
@@ -171,6 +172,32 @@ void size_grids(vpt_ctx* c) {
     c->shadow_blocks = trace_shadow_blocks_per_cu() * c->cu_count;
     c->vote_blocks = std::min(trace_blocks_per_cu(VPT_TRACE_VOTE, false), trace_blocks_per_cu(VPT_TRACE_VOTE, true)) * c->cu_count;
     c->max_blocks = std::max(std::max(std::max(std::max(c->trav_blocks, c->shade_blocks), std::max(c->primary_blocks, c->whole_blocks)), c->vote_blocks), std::max(std::max(c->shade_stream_blocks, c->finish_blocks), c->shadow_blocks));
+}
+
+// The upload both kinds of grid share: values, the brick table (bricked grids only), the block maxima and the grown list of grids, all allocated and
+// filled before the context changes — a failure frees them and leaves the list as it was.  g: dim / cells / brick_count set by the caller.
+int install_grid(vpt_ctx* c, DensityGrid g, const float* values, size_t n_values, const std::vector<uint32_t>* table, const grid::Maxima& m) {
+    { int rd = quiesce(c); if (rd) return rd; }
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    float *dv = nullptr, *db = nullptr; uint32_t* dt = nullptr; DensityGrid* dl = nullptr;
+    std::vector<DensityGrid> list = c->grids;
+    bool ok = hipMalloc((void**)&dv, n_values * 4) == hipSuccess && hipMalloc((void**)&db, grid::kBlockTable * 4) == hipSuccess &&
+              (!table || hipMalloc((void**)&dt, table->size() * 4) == hipSuccess) && hipMalloc((void**)&dl, (list.size() + 1) * sizeof(DensityGrid)) == hipSuccess;
+    g.values = dv; g.block_max = db; g.bricks = dt; g.max_density = m.max_density;
+    list.push_back(g);
+    ok = ok && hipMemcpy(dv, values, n_values * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(db, m.block_max.data(), grid::kBlockTable * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         (!table || hipMemcpy(dt, table->data(), table->size() * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+         hipMemcpy(dl, list.data(), list.size() * sizeof(DensityGrid), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        (void)hipFree(dv); (void)hipFree(db); (void)hipFree(dt); (void)hipFree(dl);
+        return fail(c, VPT_ERR_OUT_OF_MEMORY, "density grid upload");
+    }
+    c->state_gen++;
+    c->grids.swap(list);
+    if (c->d_grids) (void)hipFree(c->d_grids);
+    c->d_grids = dl; c->dsc.grids = dl;
+    return (int)c->grids.size() - 1;
 }
 
 }  // namespace
@@ -384,37 +411,52 @@ int vpt_set_volumes(vpt_ctx* c, const vpt_volume* v, uint32_t count) {
 }
 // AddDensityDataToVolume, PathTracer.cpp:1390-1442, on a dense grid
 int vpt_add_density_grid(vpt_ctx* c, uint32_t dx, uint32_t dy, uint32_t dz, const float* d) {
-    if (!c || !d || dx == 0 || dy == 0 || dz == 0 || (uint64_t)dx * dy * dz > (1ull << 31)) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c || !d || dx == 0 || dy == 0 || dz == 0 || (uint64_t)dx * dy * dz > grid::kMaxDenseVoxels) return VPT_ERR_INVALID_ARGUMENT;
     if (c->grids.size() >= VPT_MAX_DENSITY_GRIDS) return fail(c, VPT_ERR_LIMIT, "more than VPT_MAX_DENSITY_GRIDS density grids");
-    const size_t n = (size_t)dx * dy * dz;
-    float mx = 0.0f;
-    for (size_t i = 0; i < n; i++) mx = std::max(mx, d[i]);
-    if (!(mx > 0.0f)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "density grid has no positive value");
-    std::vector<float> block_max(32768, 0.0f);
-    for (uint32_t z = 0; z < dz; z++)
-        for (uint32_t y = 0; y < dy; y++)
-            for (uint32_t x = 0; x < dx; x++) {
-                const float raw = d[(size_t)x + (size_t)(dy - 1 - y) * dx + (size_t)z * dx * dy];  // "Y has to be flipped for vulkan" (:1435)
-                const float dens = vptfp::clamp_(raw / mx, 0.0f, 1.0f);
-                const uint32_t bi = ((x * 32u) / dx) + ((y * 32u) / dy) * 32u + ((z * 32u) / dz) * 1024u;
-                if (block_max[bi] < dens) block_max[bi] = dens;
-            }
-    { int rd = quiesce(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    c->state_gen++;
+    grid::Maxima m;
+    const grid::Verdict v = grid::dense_maxima(dx, dy, dz, d, m);
+    if (v.code) return fail(c, v.code, v.msg);
     DensityGrid g{};
-    float *dv = nullptr, *db = nullptr;
-    HIPCHK(c, hipMalloc((void**)&dv, n * 4));
-    if (hipMalloc((void**)&db, 32768 * 4) != hipSuccess) { (void)hipFree(dv); return fail(c, VPT_ERR_OUT_OF_MEMORY, "hipMalloc block maxima"); }
-    HIPCHK(c, hipMemcpy(dv, d, n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(db, block_max.data(), 32768 * 4, hipMemcpyHostToDevice));
-    g.values = dv; g.block_max = db; g.dim[0] = dx; g.dim[1] = dy; g.dim[2] = dz; g.max_density = mx;
-    c->grids.push_back(g);
-    if (c->d_grids) (void)hipFree(c->d_grids);
-    HIPCHK(c, hipMalloc((void**)&c->d_grids, c->grids.size() * sizeof(DensityGrid)));
-    HIPCHK(c, hipMemcpy(c->d_grids, c->grids.data(), c->grids.size() * sizeof(DensityGrid), hipMemcpyHostToDevice));
-    c->dsc.grids = c->d_grids;
-    return (int)c->grids.size() - 1;
+    g.dim[0] = dx; g.dim[1] = dy; g.dim[2] = dz;
+    return install_grid(c, g, d, (size_t)dx * dy * dz, nullptr, m);
+}
+// ... and on the tree's own leaves (grid_prep.hpp): the same grid, never densified
+int vpt_add_density_bricks(vpt_ctx* c, uint32_t dx, uint32_t dy, uint32_t dz, uint32_t n, const uint32_t* coords, const float* values) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    grid::Maxima m;
+    std::vector<uint32_t> table;
+    grid::Verdict v = grid::check_bricks(dx, dy, dz, n, coords, values, c->grids.size());
+    if (!v.code) v = grid::brick_table(dx, dy, dz, n, coords, table);
+    if (!v.code) v = grid::brick_maxima(dx, dy, dz, n, coords, values, m);
+    if (v.code) return fail(c, v.code, v.msg);
+    DensityGrid g{};
+    g.dim[0] = dx; g.dim[1] = dy; g.dim[2] = dz; g.brick_count = n;
+    g.cells[0] = grid::cells_along(dx); g.cells[1] = grid::cells_along(dy); g.cells[2] = grid::cells_along(dz);
+    return install_grid(c, g, values, (size_t)n * grid::kBrickVoxels, &table, m);
+}
+int vpt_get_density_grid_info(const vpt_ctx* c, uint32_t gi, vpt_density_grid_info* out) {
+    if (!c || !out || gi >= c->grids.size()) return VPT_ERR_INVALID_ARGUMENT;
+    const DensityGrid& g = c->grids[gi];
+    *out = vpt_density_grid_info{{g.dim[0], g.dim[1], g.dim[2]}, g.brick_count, grid::device_bytes(g), g.max_density, 0u};
+    return VPT_OK;
+}
+int vpt_read_density_grid(vpt_ctx* c, uint32_t gi, const int32_t* ijk, uint32_t n, float* out) {
+    if (!c || gi >= c->grids.size() || (n && (!ijk || !out))) return VPT_ERR_INVALID_ARGUMENT;
+    if (n == 0) return VPT_OK;
+    { int rd = quiesce(c); if (rd) return rd; }
+    int32_t* di = nullptr; float* dout = nullptr;
+    HIPCHK(c, hipMalloc((void**)&di, (size_t)n * 12));
+    if (hipMalloc((void**)&dout, (size_t)n * 4) != hipSuccess) { (void)hipFree(di); return fail(c, VPT_ERR_OUT_OF_MEMORY, "hipMalloc grid values"); }
+    int rc = VPT_OK;
+    if (hipMemcpy(di, ijk, (size_t)n * 12, hipMemcpyHostToDevice) != hipSuccess) rc = VPT_ERR_DEVICE;
+    if (!rc) {
+        launch_read_density_grid(c->main.stream, c->grids[gi], di, n, dout);
+        if (hipStreamSynchronize(c->main.stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = VPT_ERR_DEVICE;
+    }
+    if (!rc && hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = VPT_ERR_DEVICE;
+    (void)hipFree(di); (void)hipFree(dout);
+    if (rc) c->err = "vpt_read_density_grid: device error";
+    return rc;
 }
 int vpt_clear_density_grids(vpt_ctx* c) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
@@ -422,7 +464,7 @@ int vpt_clear_density_grids(vpt_ctx* c) {
     { int rd = quiesce(c); if (rd) return rd; }
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->state_gen++;
-    for (DensityGrid& g : c->grids) { (void)hipFree((void*)g.values); (void)hipFree((void*)g.block_max); }
+    for (DensityGrid& g : c->grids) { (void)hipFree((void*)g.values); (void)hipFree((void*)g.block_max); (void)hipFree((void*)g.bricks); }
     c->grids.clear();
     if (c->d_grids) { (void)hipFree(c->d_grids); c->d_grids = nullptr; }
     c->dsc.grids = nullptr;

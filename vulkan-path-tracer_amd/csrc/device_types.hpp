@@ -135,13 +135,20 @@ struct AliasEntry {  // == AliasMapEntry (Bindings.slang:1-5)
     float importance;
 };
 
-// A heterogeneous volume's density: dense raw values (x fastest) + the 32^3 table of per-block maxima of value/max.
+// A heterogeneous volume's density: raw values + the 32^3 table of per-block maxima of value/max.  Dense (bricks == nullptr): every voxel of the
+// index box [0, dim), x fastest.  Bricked: brick_count x 512 values, one 8x8x8 brick after the other (x fastest inside a brick), and `bricks`, one
+// word per brick cell of the box (cells = ceil(dim / 8), x fastest): 0xffffffff for an empty cell, else the brick's ordinal.  Read through
+// grid::grid_value (grid_prep.hpp) only.
 struct DensityGrid {
     const float* values;
     const float* block_max;
+    const uint32_t* bricks;
     uint32_t dim[3];
     float max_density;
+    uint32_t cells[3];
+    uint32_t brick_count;
 };
+static_assert(sizeof(DensityGrid) == 56, "DensityGrid is 56 B");
 
 struct DeviceScene {
     const BvhNode* nodes;

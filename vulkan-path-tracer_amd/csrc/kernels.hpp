@@ -21,6 +21,8 @@ void launch_finish(hipStream_t s, uint32_t blocks, bool count, const DeviceScene
 int finish_blocks_per_cu(const DeviceScene& sc);
 void launch_resolve(hipStream_t s, const RenderParams& P, const PathState& ps, float* image, uint32_t frames, uint32_t frame_base, const uint32_t* guard);
 void launch_trace_rays(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const vpt_ray* rays, uint32_t n, vpt_hit* hits);
+// vpt_read_density_grid: out[i] = the value the samplers' lookup returns at voxel ijk[3i .. 3i + 2] of g (device pointers inside g, ijk and out on the device)
+void launch_read_density_grid(hipStream_t s, const DensityGrid& g, const int32_t* ijk, uint32_t n, float* out);
 void launch_scatter_rows(hipStream_t s, const float* gathered, float* full, uint32_t w, uint32_t h, uint32_t shard_count, uint32_t stride_px);
 void launch_precompute_materials(hipStream_t s, const DeviceScene& sc, uint32_t flags, MatResolved* out, uint32_t n);
 void launch_precompute_tri_ng(hipStream_t s, const DeviceScene& sc, float4* out);

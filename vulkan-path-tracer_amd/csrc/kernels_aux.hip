@@ -1,5 +1,5 @@
 // kernels_aux.hip — one-pass kernels beside the integrators: the resolve (running mean over a batch's frames), shard rows -> full image, the derived scene
-// tables (k_precompute_*, k_classify_instances), the refit behind vpt_set_instance_transforms (k_retransform_tris, k_refit_level), the closest-hit test hook k_trace_rays, the LDS / stack-overflow size helpers every launcher shares, and the count of spilled stack words (k_count_spilled).
+// tables (k_precompute_*, k_classify_instances), the refit behind vpt_set_instance_transforms (k_retransform_tris, k_refit_level), the test hooks k_trace_rays (closest hit) and k_read_density_grid (a density grid's lookup), the LDS / stack-overflow size helpers every launcher shares, and the count of spilled stack words (k_count_spilled).
 #include "bvh_refit.hpp"
 #include "kernels.hpp"
 #include "shade_core.hpp"
@@ -235,6 +235,18 @@ __global__ __launch_bounds__(kTraverseBlock) void k_trace_rays(DeviceScene sc, c
 void launch_trace_rays(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const vpt_ray* rays, uint32_t n, vpt_hit* hits) {
     uint32_t g = cdiv(n, kTraverseBlock);
     hipLaunchKernelGGL(k_trace_rays, dim3(g < blocks ? g : blocks), dim3(kTraverseBlock), (size_t)kStackDepth * kTraverseBlock * 4, s, sc, rays, n, hits);
+}
+
+// Test hook: the samplers' lookup (grid_prep.hpp grid_value) at caller-supplied voxels, clamped to the index box as sample_density_grid clamps.
+__global__ __launch_bounds__(256) void k_read_density_grid(DensityGrid g, const int32_t* ijk, uint32_t n, float* out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int cx = min(max(ijk[(size_t)i * 3], 0), (int)g.dim[0] - 1), cy = min(max(ijk[(size_t)i * 3 + 1], 0), (int)g.dim[1] - 1), cz = min(max(ijk[(size_t)i * 3 + 2], 0), (int)g.dim[2] - 1);
+        out[i] = grid::grid_value(g, (uint32_t)cx, (uint32_t)cy, (uint32_t)cz);
+    }
+}
+void launch_read_density_grid(hipStream_t s, const DensityGrid& g, const int32_t* ijk, uint32_t n, float* out) {
+    const uint32_t b = cdiv(n, 256);
+    hipLaunchKernelGGL(k_read_density_grid, dim3(b < 1024u ? b : 1024u), dim3(256), 0, s, g, ijk, n, out);
 }
 
 size_t traverse_lds_bytes(const DeviceScene& sc, bool lds_scene, int stack_rows) {

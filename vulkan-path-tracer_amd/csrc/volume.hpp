@@ -4,6 +4,7 @@
 // Sampler.slang:168-284 (HG / Draine / HG+Draine sampling), RTCommon.slang:213-227 (phase pdfs).
 // Expression order is part of the parity contract (compiled with -ffp-contract=off, vpt_fp32.h math).
 #pragma once
+#include "grid_prep.hpp"
 #include "shading.hpp"
 
 namespace vpt {
@@ -93,12 +94,12 @@ __device__ inline float volume_phase(uint32_t phase, const vpt_volume& v, V3 V, 
     HgDraineFit f = hg_draine_fit(v.droplet_size);
     return lerp(phase_hg(V, L, f.ghg), phase_draine(V, L, f.gd, f.alpha_d), f.w_d);
 }
-// ---- heterogeneous boxes: density from a dense grid (the reference's NanoVDB tree, densified) --------------------
+// ---- heterogeneous boxes: density from a grid, dense or in 8x8x8 bricks (the reference's NanoVDB tree: its leaves) -----
 __device__ inline float effective_density(const vpt_volume& v, float base, float depth) {  // Volume.slang:149-156
     if (v.approximated_scattering != 0) return base * pow_(v.approximated_scattering_falloff, depth);
     return base;
 }
-// SampleNanoVDBBuffer, Volume.slang:69-117, on a dense grid whose index box is [0, dim)
+// SampleNanoVDBBuffer, Volume.slang:69-117, on a grid whose index box is [0, dim); the one fetch is grid::grid_value (grid_prep.hpp)
 __device__ inline float sample_density_grid(const DeviceScene& sc, const vpt_volume& v, Rng& r, V3 x) {
     const DensityGrid& g = sc.grids[v.density_data_index];
     V3 n = (x - ld3(v.corner_min)) / (ld3(v.corner_max) - ld3(v.corner_min));
@@ -109,7 +110,7 @@ __device__ inline float sample_density_grid(const DeviceScene& sc, const vpt_vol
     r.s = pcg_hash(r.s); cy += (int)(r.s % 3u) - 1;
     r.s = pcg_hash(r.s); cz += (int)(r.s % 3u) - 1;
     cx = min(max(cx, 0), (int)g.dim[0] - 1); cy = min(max(cy, 0), (int)g.dim[1] - 1); cz = min(max(cz, 0), (int)g.dim[2] - 1);
-    float value = g.values[(size_t)cx + (size_t)cy * g.dim[0] + (size_t)cz * g.dim[0] * g.dim[1]];
+    float value = grid::grid_value(g, (uint32_t)cx, (uint32_t)cy, (uint32_t)cz);
     return clamp_(value / g.max_density * v.grid_sharpness, 0.0f, 1.0f);
 }
 struct VolBlock { int index; V3 lo, hi; };

@@ -154,6 +154,14 @@ void PathTracer::AddDensityDataToVolume(uint32_t volumeIndex, uint32_t dx, uint3
     m_Volumes[volumeIndex].DensityDataIndex = idx;
     UploadVolumes();
 }
+void PathTracer::AddDensityDataToVolume(uint32_t volumeIndex, uint32_t dx, uint32_t dy, uint32_t dz, uint32_t brickCount, const uint32_t* brickCoords, const float* brickValues) {
+    if (volumeIndex >= m_Volumes.size()) throw std::runtime_error("AddDensityDataToVolume: index out of range");
+    if (!m_Ctx) throw std::runtime_error("AddDensityDataToVolume before SetScene");
+    int idx = vpt_add_density_bricks(m_Ctx, dx, dy, dz, brickCount, brickCoords, brickValues);
+    if (idx < 0) Check(idx, "vpt_add_density_bricks");
+    m_Volumes[volumeIndex].DensityDataIndex = idx;
+    UploadVolumes();
+}
 void PathTracer::RemoveDensityDataFromVolume(uint32_t volumeIndex) {  // the grid itself stays allocated until the context goes
     if (volumeIndex >= m_Volumes.size()) throw std::runtime_error("RemoveDensityDataFromVolume: index out of range");
     m_Volumes[volumeIndex].DensityDataIndex = -1;

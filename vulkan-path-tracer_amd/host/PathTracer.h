@@ -6,8 +6,9 @@
 //   * the seed is explicit (SetSeed): the reference draws it from the wall clock (PathTracer.cpp:127-140);
 //   * errors throw std::runtime_error where the reference VH_ASSERT-aborts.
 // Box volumes (AddVolume / SetVolume / RemoveVolume / SetPhaseFunction) and the atmosphere members (SetEnableAtmosphere, SetPlanetRadius,
-// ...) are in; heterogeneous volumes take their density as a dense grid of decoded voxels (the C-ABI's vpt_add_density_grid): reading
-// .vdb / NanoVDB files (AddDensityDataToVolume, PathTracer.cpp:1347-1516) is the one member that is absent.
+// ...) are in; heterogeneous volumes take their density as a dense grid of decoded voxels (the C-ABI's vpt_add_density_grid) or as the 8x8x8
+// leaf nodes of a NanoVDB tree the caller holds (vpt_add_density_bricks): both AddDensityDataToVolume overloads below.  What stays absent is
+// READING a .vdb / .nvdb file (the file half of AddDensityDataToVolume, PathTracer.cpp:1347-1389): no decoder is linked.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -93,6 +94,9 @@ public:
     // AddDensityDataToVolume (PathTracer.h:165, PathTracer.cpp:1347-1516) with the .vdb already decoded into a dense grid of
     // raw densities (x fastest, file index order).  The box corners stay as the caller set them.
     void AddDensityDataToVolume(uint32_t volumeIndex, uint32_t dimX, uint32_t dimY, uint32_t dimZ, const float* density);
+    // ... or with the grid as the NanoVDB tree holds it: brickCount leaf nodes of 8 x 8 x 8 voxels (brickCoords: bx, by, bz per brick; brickValues:
+    // 512 per brick, x fastest) inside the index box [0, dim), background 0 — the C-ABI's vpt_add_density_bricks.  The dense box is never formed.
+    void AddDensityDataToVolume(uint32_t volumeIndex, uint32_t dimX, uint32_t dimY, uint32_t dimZ, uint32_t brickCount, const uint32_t* brickCoords, const float* brickValues);
     void RemoveDensityDataFromVolume(uint32_t volumeIndex);
     [[nodiscard]] uint32_t GetVolumesCount() const { return (uint32_t)m_Volumes.size(); }
     [[nodiscard]] const std::vector<Volume>& GetVolumes() const { return m_Volumes; }

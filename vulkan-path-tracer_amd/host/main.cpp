@@ -5,6 +5,8 @@
 //              [--env-hdr sky.hdr] [--png out.png] [--atmosphere] [--sun altitude,azimuth]
 //              [--env-late]   apply --env-constant / --env-hdr after SetScene instead of before (the Editor's order of calls: the map is swapped on the installed scene)
 //              [--volume minx,miny,minz,maxx,maxy,maxz,density,g,r,g,b]... [--phase hg|draine|hg+draine]
+//              [--density-bricks FILE]   AddDensityDataToVolume on the last --volume, from 8x8x8 bricks: FILE = u32 dim_x, dim_y, dim_z, bricks; u32[3 * bricks]
+//                                        coordinates (bx, by, bz); float[512 * bricks] values (x fastest)
 //              [--async]   one PathTraceAsync + PostProcessAsync per frame with a one-frame fence lag (the reference's Editor loop) instead of blocking batches
 //              [--async-step N]   dispatches per PathTraceAsync call (default 1)
 //              [--no-ray-queries]   SetUseRayQueries(false): the TraceRay forms of the shadow / distance queries (RTCommon.slang:64-84)
@@ -38,7 +40,7 @@ static void write_file(const std::string& path, const void* data, size_t bytes) 
 
 int main(int argc, char** argv) {
     std::string scene, luts, radiance, camera, ppm, png, envHdr, dumpEnv, pngTest, decodeImage, dumpImage, dump, makeLut, lutOut;
-    std::vector<PathTracer::Volume> volumes; int phase = 0; bool atmosphere = false; float sunAlt = 0.0f, sunAz = 0.0f;
+    std::vector<PathTracer::Volume> volumes; std::vector<std::pair<uint32_t, std::string>> brickFiles; int phase = 0; bool atmosphere = false; float sunAlt = 0.0f, sunAz = 0.0f;
     uint32_t lutSamples = 10000000u, lutTime = 0; UVec3 lutSize{0, 0, 0};
     uint32_t w = 0, h = 0, spp = 16, depth = 8, seed = 1, split = 1, gpus = 1; std::vector<int> devices;
     bool async = false, rayQueries = true, envLate = false; uint32_t asyncStep = 1;
@@ -77,6 +79,10 @@ int main(int argc, char** argv) {
             if (sscanf(s.c_str(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f", &f[0], &f[1], &f[2], &f[3], &f[4], &f[5], &f[6], &f[7], &f[8], &f[9], &f[10]) != 11) { fprintf(stderr, "--volume needs 11 numbers\n"); return 2; }
             v.CornerMin = Vec3(f[0], f[1], f[2]); v.CornerMax = Vec3(f[3], f[4], f[5]); v.Density = f[6]; v.Anisotropy = f[7]; v.Color = Vec3(f[8], f[9], f[10]);
             volumes.push_back(v);
+        }
+        else if (a == "--density-bricks") {
+            if (volumes.empty()) { fprintf(stderr, "--density-bricks follows the --volume it fills\n"); return 2; }
+            brickFiles.push_back({(uint32_t)volumes.size() - 1u, next()});
         }
         else if (a == "--phase") { std::string s = next(); phase = s == "hg" ? 0 : s == "draine" ? 1 : s == "hg+draine" ? 2 : -1; if (phase < 0) { fprintf(stderr, "--phase hg|draine|hg+draine\n"); return 2; } }
         else if (a == "--atmosphere") atmosphere = true;
@@ -206,6 +212,15 @@ int main(int argc, char** argv) {
             if (!rayQueries) pt.SetUseRayQueries(false);
             if (phase != 0) pt.SetPhaseFunction((PathTracer::PhaseFunction)phase);
             for (const auto& v : volumes) pt.AddVolume(v);
+            for (const auto& bf : brickFiles) {
+                std::ifstream f(bf.second, std::ios::binary);
+                uint32_t hd[4] = {0, 0, 0, 0};
+                if (!f.read((char*)hd, sizeof(hd)) || hd[3] > (1u << 22)) throw std::runtime_error("cannot read the brick header of " + bf.second);
+                std::vector<uint32_t> coords((size_t)hd[3] * 3); std::vector<float> values((size_t)hd[3] * 512);
+                if (hd[3] && (!f.read((char*)coords.data(), (std::streamsize)(coords.size() * 4)) || !f.read((char*)values.data(), (std::streamsize)(values.size() * 4))))
+                    throw std::runtime_error("short brick file " + bf.second);
+                pt.AddDensityDataToVolume(bf.first, hd[0], hd[1], hd[2], hd[3], coords.data(), values.data());
+            }
             if (sunAlt != 0.0f || sunAz != 0.0f) { pt.SetSkyAltitude(sunAlt); pt.SetSkyAzimuth(sunAz); }
             if (atmosphere) pt.SetEnableAtmosphere(true);
         }
