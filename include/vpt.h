@@ -554,6 +554,40 @@ typedef struct vpt_ray { float origin[3]; float tmin; float direction[3]; float 
 typedef struct vpt_hit { float t; float u; float v; uint32_t primitive; uint32_t instance; } vpt_hit;
 int vpt_trace_rays(vpt_ctx* ctx, const vpt_ray* rays_host, uint32_t n, vpt_hit* hits_host);
 
+/* ---- picking and guide buffers ------------------------------------------------------------------------------------------
+ * What the camera sees FIRST through every pixel: the inputs of a denoiser or an edge-aware filter (depth, shading normal, albedo)
+ * and what an editor's viewport picks (instance, primitive, material, mesh).  The reference has no counterpart: its only such views
+ * are the commented-out normal / validity outputs of ClosestHit.slang:69-71,206-218.  One kernel runs the integrator's camera-ray
+ * closest-hit query (RayGen.slang:70: tmin 0.01, tmax 100000) and the head of ClosestHit.slang — SurfaceFrame (Surface.slang:26-147)
+ * and Material.Initialize's base colour (Material.slang:44) — and stops there.
+ *   camera and state  the current camera, flags (VPT_FLAG_LOCAL_HITS, _GEOMETRY_NORMALS, _FURNACE included), materials edited
+ *                     (vpt_set_material) and instances moved (vpt_set_instance_transforms) since the scene was installed all apply.
+ *   media             volumes and the atmosphere are ignored: the buffers describe the first SURFACE.
+ *   coverage          always the WHOLE width x height image, on a shard context too (every context holds the whole scene).
+ *   VPT_FEATURES_SAMPLE  the RNG state is the one the integrator gives sample 0 of pixel (x, y) in dispatch `frame`, the ray is the
+ *                     integrator's camera ray (jitter and lens offset included), bit for bit.
+ *   VPT_FEATURES_CENTER  the same expressions with both jitter draws equal to 0.5 and a zero lens offset; `frame` is ignored.
+ *   side effects      waits for work in flight; does NOT reset or touch the accumulation, the frame counters or any vpt_stats field
+ *                     (beyond the recount of stack_spills every traversal causes, as vpt_trace_rays does).
+ *   errors            VPT_ERR_NO_SCENE before vpt_set_scene; VPT_ERR_INVALID_ARGUMENT for a NULL ctx or out, an unknown mode, all
+ *                     four pointers NULL, or (vpt_pick) a pixel outside the image.  A failed call leaves the caller's buffers
+ *                     unspecified and the context usable. */
+#define VPT_FEATURES_CENTER 0u  /* the ray through the pixel centre, no lens offset */
+#define VPT_FEATURES_SAMPLE 1u  /* the camera ray of sample 0 of dispatch `frame`, exactly as the integrator draws it */
+typedef struct vpt_feature_buffers {   /* any pointer may be NULL: that buffer is not produced */
+    float*    depth;   /* width*height     : t of the closest hit along the ray, -1 on a miss */
+    uint32_t* ids;     /* width*height*4   : instance, primitive, material, mesh; 0xffffffff x4 on a miss */
+    float*    normal;  /* width*height*4   : SurfaceFrame N (after normal map and the two corrections; Ng under VPT_FLAG_GEOMETRY_NORMALS), w = 1 inside / 0 outside; 0 on a miss */
+    float*    albedo;  /* width*height*4   : Material.Initialize base colour at the hit's uv (1,1,1 under VPT_FLAG_FURNACE), w = transmission; 0 on a miss */
+    uint32_t  device;  /* 0: host pointers; 1: device pointers on the context's device */
+    uint32_t  reserved;
+} vpt_feature_buffers;
+int vpt_render_features(vpt_ctx* ctx, uint32_t mode, uint32_t frame, const vpt_feature_buffers* out);
+/* The VPT_FEATURES_CENTER ray of ONE pixel: the same launch with one ray, so ids and t equal the CENTER buffers' at (x, y) bit for bit.
+ * u, v: the hit's barycentrics; position = origin + t * direction.  A miss is VPT_OK with ids 0xffffffff, t = -1 and the rest 0. */
+typedef struct vpt_pick_result { uint32_t instance, primitive, material, mesh; float t, u, v; float position[3]; } vpt_pick_result;
+int vpt_pick(vpt_ctx* ctx, uint32_t x, uint32_t y, vpt_pick_result* out);   /* CENTER ray of one pixel; a miss is VPT_OK with ids 0xffffffff and t = -1 */
+
 /* ---- energy-compensation lookup tables -------------------------------------------
  * Replaces LookupTableCalculator::CalculateTable(tableSize, sampleCount) (LookupTableCalculator.cpp:44-157)
  * with its shaders LookupReflect.slang / LookupRefract.slang (+ ABOVE_SURFACE / BELOW_SURFACE): sampleCount/20

@@ -12,6 +12,7 @@ import numpy as np
 from . import _abi, imagefiles, scenes  # noqa: F401
 from ._abi import default_params, default_post_params, volume, atmosphere  # noqa: F401
 from ._abi import PHASE_HENYEY_GREENSTEIN, PHASE_DRAINE, PHASE_HENYEY_GREENSTEIN_PLUS_DRAINE  # noqa: F401
+from ._abi import FEATURES_CENTER, FEATURES_SAMPLE  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -301,6 +302,35 @@ class PathTracer:
         hits = np.zeros(len(rays), HIT_DTYPE)
         _check(self.lib, self.ctx, self.lib.vpt_trace_rays(self.ctx, rays.ctypes.data, len(rays), hits.ctypes.data), "vpt_trace_rays")
         return hits
+
+    # ---- picking and guide buffers (include/vpt.h vpt_render_features / vpt_pick)
+    FEATURES = ("depth", "ids", "normal", "albedo")
+
+    def render_features(self, mode=FEATURES_CENTER, frame=0, which=FEATURES):
+        """vpt_render_features to host memory: {name: array} for the names in `which` — depth float32 [h, w] (t, -1 on a miss), ids uint32 [h, w, 4]
+        (instance, primitive, material, mesh; 0xffffffff on a miss), normal and albedo float32 [h, w, 4].  Always the whole image."""
+        which = tuple(which)
+        bad = [n for n in which if n not in self.FEATURES]
+        if bad:
+            raise ValueError("unknown feature buffers %r (known: %r)" % (bad, self.FEATURES))
+        out = {n: np.zeros((self.height, self.width) + (() if n == "depth" else (4,)), np.uint32 if n == "ids" else np.float32) for n in which}
+        fb = _abi.FeatureBuffers(**{n: a.ctypes.data for n, a in out.items()})
+        _check(self.lib, self.ctx, self.lib.vpt_render_features(self.ctx, mode, frame, C.byref(fb)), "vpt_render_features")
+        return out
+
+    def render_features_device(self, mode=FEATURES_CENTER, frame=0, depth=None, ids=None, normal=None, albedo=None):
+        """vpt_render_features into device memory of the context's device: each argument is a device pointer (e.g. a torch tensor's data_ptr()) to
+        width*height floats (depth) or width*height*4 words (the others, 16-byte aligned), or None."""
+        fb = _abi.FeatureBuffers(depth, ids, normal, albedo, 1, 0)
+        _check(self.lib, self.ctx, self.lib.vpt_render_features(self.ctx, mode, frame, C.byref(fb)), "vpt_render_features")
+
+    def pick(self, x, y):
+        """vpt_pick: what the FEATURES_CENTER ray of pixel (x, y) hits first -> {"instance", "primitive", "material", "mesh", "t", "u", "v", "position"};
+        a miss has the four ids 0xffffffff and t = -1."""
+        r = _abi.PickResult()
+        _check(self.lib, self.ctx, self.lib.vpt_pick(self.ctx, x, y, C.byref(r)), "vpt_pick")
+        return {"instance": r.instance, "primitive": r.primitive, "material": r.material, "mesh": r.mesh, "t": np.float32(r.t), "u": np.float32(r.u),
+                "v": np.float32(r.v), "position": np.array(list(r.position), np.float32)}
 
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("primitive", "<u4"), ("instance", "<u4")])

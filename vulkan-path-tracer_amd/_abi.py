@@ -203,6 +203,18 @@ class DensityGridInfo(C.Structure):
     _fields_ = [("dim", C.c_uint32 * 3), ("brick_count", C.c_uint32), ("device_bytes", C.c_uint64), ("max_density", C.c_float), ("reserved", C.c_uint32)]
 
 
+FEATURES_CENTER, FEATURES_SAMPLE = 0, 1
+
+
+class FeatureBuffers(C.Structure):  # vpt_feature_buffers
+    _fields_ = [("depth", C.c_void_p), ("ids", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("device", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PickResult(C.Structure):  # vpt_pick_result
+    _fields_ = [("instance", C.c_uint32), ("primitive", C.c_uint32), ("material", C.c_uint32), ("mesh", C.c_uint32),
+                ("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("position", C.c_float * 3)]
+
+
 # every symbol include/vpt.h declares, with (restype, argtypes)
 PROTOTYPES = {
     "vpt_create": (C.c_void_p, [C.POINTER(Config), C.POINTER(C.c_int)]),
@@ -252,6 +264,8 @@ PROTOTYPES = {
     "vpt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "vpt_reset_stats": (C.c_int, [C.c_void_p]),
     "vpt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "vpt_render_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(FeatureBuffers)]),
+    "vpt_pick": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PickResult)]),
     "vpt_lab_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "vpt_lab_set_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "vpt_lab_trace": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),

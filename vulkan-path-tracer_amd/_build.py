@@ -25,6 +25,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # (profiles/r03_trace_isa_budget.md), a net loss in issued instructions, so it is off for that file.  Values are unaffected:
 # packed and scalar fp32 operations round identically and no contraction is allowed either way.
 EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("kernels_trace.hip", "kernels_stream.hip", "kernels_media.hip", "kernels_whole.hip", "kernels_finish.hip", "kernels_bounce.hip", "kernels_aux.hip", "kernels_lab_r1.hip")}
+# The host layer (no kernel in these files, nothing in them is timed) is compiled for size: the product library's size bound (tests/test_abi.py) is a few
+# KB away, and -Os on these five takes ~10 KB off it.
+EXTRA_FLAGS.update({f: ["-Os"] for f in ("api_context.hip", "api_scene.hip", "api_render.hip", "api_post.hip", "api_comm.hip")})
 
 
 def hipcc():

@@ -523,4 +523,53 @@ int vpt_trace_rays(vpt_ctx* c, const vpt_ray* rays, uint32_t n, vpt_hit* hits) {
     return rc;
 }
 
+// vpt_render_features and vpt_pick: one launch of k_first_hit over camera rays on the main lane — the whole image, or the one pixel *pixel, whose
+// barycentrics and position come back in pick8 (kernels.hpp FirstHitArgs::pick).  Host buffers are filled through ONE staging allocation, freed before
+// the return; device buffers are written by the kernel itself.  Nothing of the context changes but spill_dirty.
+static int first_hit_camera(vpt_ctx* c, uint32_t mode, uint32_t frame, const vpt_feature_buffers* out, const uint32_t* pixel, float* pick8) {
+    if (!c || !out || mode > VPT_FEATURES_SAMPLE || (!out->depth && !out->ids && !out->normal && !out->albedo)) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
+    const bool host = out->device == 0u;
+    void* const dst[4] = {out->ids, out->normal, out->albedo, out->depth};
+    if (!host) for (int k = 0; k < 3; k++) if (((uintptr_t)dst[k] & 15u) != 0u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "device ids / normal / albedo buffers must be 16-byte aligned");
+    { int rd = quiesce(c); if (rd) return rd; }
+    const uint32_t w = c->P.width, h = c->P.height;
+    const size_t npx = pixel ? 1u : (size_t)w * h;
+    const size_t bytes[4] = {npx * 16, npx * 16, npx * 16, npx * 4};
+    size_t total = pixel ? 32u : 0u;
+    if (host) for (int k = 0; k < 4; k++) if (dst[k]) total += bytes[k];
+    char* stage = nullptr;
+    if (total) HIPCHK(c, hipMalloc((void**)&stage, total));
+    void* dev[4]; size_t off = pixel ? 32u : 0u;
+    for (int k = 0; k < 4; k++) { dev[k] = dst[k]; if (host && dst[k]) { dev[k] = stage + off; off += bytes[k]; } }
+    FirstHitArgs a{};
+    a.n = pixel ? 1u : ((w + 7u) / 8u) * ((h + 7u) / 8u) * 64u;   // 8 x 8 pixel tiles, a wave each
+    a.mode = mode; a.frame = frame;
+    a.ids = (uint4*)dev[0]; a.normal = (float4*)dev[1]; a.albedo = (float4*)dev[2]; a.depth = (float*)dev[3];
+    if (pixel) { a.pick = (float4*)stage; a.pixel = *pixel; }
+    int rc = VPT_OK;
+    c->spill_dirty = true;   // a traversal kernel runs: vpt_get_stats recounts the spill regions
+    launch_first_hit(c->main.stream, (uint32_t)c->max_blocks, lane_scene(c, c->main), c->P, a);
+    if (hipStreamSynchronize(c->main.stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = VPT_ERR_DEVICE;
+    if (!rc && pixel && hipMemcpy(pick8, stage, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = VPT_ERR_DEVICE;
+    for (int k = 0; k < 4; k++) if (!rc && host && dst[k] && hipMemcpy(dst[k], dev[k], bytes[k], hipMemcpyDeviceToHost) != hipSuccess) rc = VPT_ERR_DEVICE;
+    if (stage) (void)hipFree(stage);
+    if (rc) c->err = "vpt_render_features: device error";
+    return rc;
+}
+int vpt_render_features(vpt_ctx* c, uint32_t mode, uint32_t frame, const vpt_feature_buffers* out) {
+    return first_hit_camera(c, mode, frame, out, nullptr, nullptr);
+}
+int vpt_pick(vpt_ctx* c, uint32_t x, uint32_t y, vpt_pick_result* out) {
+    if (!c || !out) return VPT_ERR_INVALID_ARGUMENT;
+    if (x >= c->P.width || y >= c->P.height) return fail(c, VPT_ERR_INVALID_ARGUMENT, "pixel outside the image");
+    uint32_t ids[4]; float t, uvp[8];
+    vpt_feature_buffers fb{}; fb.depth = &t; fb.ids = ids;
+    const uint32_t pixel = y * c->P.width + x;
+    int rc = first_hit_camera(c, VPT_FEATURES_CENTER, 0u, &fb, &pixel, uvp);
+    if (rc) return rc;
+    *out = vpt_pick_result{ids[0], ids[1], ids[2], ids[3], t, uvp[0], uvp[1], {uvp[4], uvp[5], uvp[6]}};
+    return VPT_OK;
+}
+
 }  // extern "C"

@@ -20,6 +20,16 @@ void launch_finish(hipStream_t s, uint32_t blocks, bool count, const DeviceScene
                    StreamCounters* sctr, Counters* ctr, uint32_t parity);
 int finish_blocks_per_cu(const DeviceScene& sc);
 void launch_resolve(hipStream_t s, const RenderParams& P, const PathState& ps, float* image, uint32_t frames, uint32_t frame_base, const uint32_t* guard);
+// The first hit of a set of rays and what lies there (kernels_aux.hip k_first_hit), behind vpt_trace_rays, vpt_render_features and vpt_pick.  The rays are
+// the caller's (rays != nullptr: n of them, hits[i] is all that is written) or the camera's: every pixel of the image in 8 x 8 tiles, or, with
+// pick != nullptr, the one pixel `pixel` (y * width + x), whose outputs land at index 0.  All pointers are device memory; a null output is not written.
+struct FirstHitArgs {
+    const vpt_ray* rays; vpt_hit* hits; uint32_t n;
+    uint32_t mode, frame;   // VPT_FEATURES_*; the dispatch whose sample 0 a VPT_FEATURES_SAMPLE ray is
+    float* depth; uint4* ids; float4* normal; float4* albedo;   // vpt_feature_buffers
+    float4* pick; uint32_t pixel;   // pick[0] = u, v, 0, 0; pick[1] = origin + t * direction, 0
+};
+void launch_first_hit(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const RenderParams& P, const FirstHitArgs& a);
 void launch_trace_rays(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const vpt_ray* rays, uint32_t n, vpt_hit* hits);
 // vpt_read_density_grid: out[i] = the value the samplers' lookup returns at voxel ijk[3i .. 3i + 2] of g (device pointers inside g, ijk and out on the device)
 void launch_read_density_grid(hipStream_t s, const DensityGrid& g, const int32_t* ijk, uint32_t n, float* out);

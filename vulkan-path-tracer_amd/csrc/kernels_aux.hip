@@ -1,5 +1,5 @@
 // kernels_aux.hip — one-pass kernels beside the integrators: the resolve (running mean over a batch's frames), shard rows -> full image, the derived scene
-// tables (k_precompute_*, k_classify_instances), the refit behind vpt_set_instance_transforms (k_retransform_tris, k_refit_level), the test hooks k_trace_rays (closest hit) and k_read_density_grid (a density grid's lookup), the LDS / stack-overflow size helpers every launcher shares, and the count of spilled stack words (k_count_spilled).
+// tables (k_precompute_*, k_classify_instances), the refit behind vpt_set_instance_transforms (k_retransform_tris, k_refit_level), k_first_hit (the closest hit of caller-supplied or camera rays and the guide buffers there: vpt_trace_rays, vpt_render_features, vpt_pick), the test hook k_read_density_grid (a density grid's lookup), the LDS / stack-overflow size helpers every launcher shares, and the count of spilled stack words (k_count_spilled).
 #include "bvh_refit.hpp"
 #include "kernels.hpp"
 #include "shade_core.hpp"
@@ -218,23 +218,109 @@ void launch_refit_level(hipStream_t s, const DeviceScene& sc, const uint32_t* or
     if (end > begin) hipLaunchKernelGGL(k_refit_level, dim3(cdiv(end - begin, 256)), dim3(256), 0, s, sc, order, begin, end, tris, pad, boxes, nodes_out, wide_out);
 }
 
-// Test hook: the closest-hit traversal on caller-supplied rays.
-__global__ __launch_bounds__(kTraverseBlock) void k_trace_rays(DeviceScene sc, const vpt_ray* rays, uint32_t n, vpt_hit* hits) {
+// camera_ray (shading.hpp) with its four draws handed in — the jitter pair and random_circle's point — instead of drawn: the same expressions in the same
+// order, so with the integrator's draws it is the integrator's ray bit for bit, and with (0.5, 0.5) and (0, 0) it is the ray through the pixel centre
+// with no lens offset.  Only k_first_hit calls it: the integrators keep camera_ray.
+__device__ inline void camera_ray_with(const RenderParams& P, float j0, float j1, V2 rc, uint32_t x, uint32_t y, V3& origin, V3& direction) {
+    float cx = ((float)x + 0.5f) + (j0 * (0.5f - -0.5f) + -0.5f);
+    float cy = ((float)y + 0.5f) + (j1 * (0.5f - -0.5f) + -0.5f);
+    float dx = (cx / (float)P.width) * 2.0f - 1.0f, dy = (cy / (float)P.height) * 2.0f - 1.0f;
+    V4 o4 = mat_v4(P.view_inv, v4(0.0f, 0.0f, 0.0f, 1.0f));
+    origin = v3(o4.x, o4.y, o4.z);
+    V4 tg = mat_v4(P.proj_inv, v4(dx, dy, 1.0f, 1.0f));
+    V3 tn = normalize(v3(tg.x, tg.y, tg.z));
+    V4 dd = mat_v4(P.view_inv, v4(tn.x, tn.y, tn.z, 0.0f));
+    direction = v3(dd.x, dd.y, dd.z);
+    V3 focus = origin + direction * max_(P.focus_distance, 0.001f);
+    float rox = rc.x * 0.5f * P.dof_strength, roy = rc.y * 0.5f * P.dof_strength;
+    V3 right = v3(P.view_inv[0], P.view_inv[1], P.view_inv[2]);
+    V3 upv = v3(P.view_inv[4], P.view_inv[5], P.view_inv[6]);
+    origin = origin + (rox * right + roy * upv);
+    direction = normalize(focus - origin);
+}
+// The closest hit of a ray and, for a camera ray, what lies there (kernels.hpp FirstHitArgs): vpt_trace_rays' test hook on caller-supplied rays, and the
+// guide buffers of vpt_render_features / vpt_pick — the integrator's camera-ray query (RayGen.slang:70: direction normalised, tmin 0.01, tmax 100000)
+// followed by the head of ClosestHit.slang (SurfaceFrame, :45-71; Material.Initialize's base colour, Material.slang:44) and nothing after it.  In camera
+// mode work item i is lane i % 64 of tile i / 64 and a tile is 8 x 8 pixels: a wave's rays stay together in the tree and its texel taps in a few lines.
+// The in-memory tree serves every scene (an LDS-resident one has it too).  One traversal is compiled in for both ray sources: a second kernel would
+// carry a second copy of it.  No barrier in the loop: lanes outside the image skip their item.
+__global__ __launch_bounds__(kTraverseBlock) void k_first_hit(DeviceScene sc, RenderParams P, FirstHitArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const TravStack stack = make_stack(smem, sc.stack_overflow);
     GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        vpt_ray r = rays[i];
+    const uint32_t tiles_x = (P.width + 7u) / 8u;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
+        V3 o, d; float tmin = 0.01f, tmax = 100000.0f;
+        uint32_t px = 0u;
+        if (a.rays) {
+            vpt_ray r = a.rays[i];
+            o = v3(r.origin[0], r.origin[1], r.origin[2]); d = v3(r.direction[0], r.direction[1], r.direction[2]); tmin = r.tmin; tmax = r.tmax;
+        } else {
+            uint32_t x, y;
+            if (a.pick) { y = a.pixel / P.width; x = a.pixel - y * P.width; }
+            else {
+                const uint32_t tile = i >> 6, ty = tile / tiles_x;
+                x = (tile - ty * tiles_x) * 8u + (i & 7u); y = ty * 8u + ((i >> 3) & 7u);
+                if (x >= P.width || y >= P.height) continue;
+                px = y * P.width + x;
+            }
+            float j0 = 0.5f, j1 = 0.5f; V2 rc; rc.x = 0.0f; rc.y = 0.0f;
+            if (a.mode == VPT_FEATURES_SAMPLE) {
+                Rng r; r.s = y + P.width * x + pcg_hash(P.base_seed + a.frame);   // RayGen.slang:28, PathTracer.cpp:139: sample 0 of the pixel in dispatch `frame`
+                j0 = r.uf(); j1 = r.uf(); rc = random_circle(r);
+            }
+            camera_ray_with(P, j0, j1, rc, x, y, o, d);
+            d = normalize(d);
+        }
         HitRec h; TravStats st;
-        bool found = trace_closest<false>(src, v3(r.origin[0], r.origin[1], r.origin[2]), v3(r.direction[0], r.direction[1], r.direction[2]),
-                                          r.tmin, r.tmax, stack, h, st);
-        vpt_hit o; o.t = found ? h.t : -1.0f; o.u = found ? h.u : 0.0f; o.v = found ? h.v : 0.0f; o.primitive = h.prim; o.instance = h.inst;
-        hits[i] = o;
+        bool found = trace_closest<false>(src, o, d, tmin, tmax, stack, h, st);
+        if (a.rays) {
+            vpt_hit q; q.t = found ? h.t : -1.0f; q.u = found ? h.u : 0.0f; q.v = found ? h.v : 0.0f; q.primitive = h.prim; q.instance = h.inst;
+            a.hits[i] = q;
+            continue;
+        }
+        float t = -1.0f;
+        uint4 id = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+        float4 nrm = make_float4(0.0f, 0.0f, 0.0f, 0.0f), alb = nrm, uv = nrm, pos = nrm;
+        if (found) {
+            const InstanceDesc& in = sc.instances[h.inst];
+            const vpt_material& m = sc.materials[in.material];
+            const MatResolved& mr = sc.mat_resolved[in.material];
+            const bool geo_only = (P.flags & VPT_FLAG_GEOMETRY_NORMALS) != 0;
+            t = h.t; id = make_uint4(h.inst, h.prim, in.material, in.mesh);
+            uv.x = h.u; uv.y = h.v;
+            V3 at = o + h.t * d; pos = make_float4(at.x, at.y, at.z, 0.0f);
+            SurfaceFrame s;
+            surface_geom(sc, s, in, h.gid, h.u, h.v, d, geo_only);
+            TexTaps nt, bt;   // the two taps in flight together
+            const bool base_tap = a.albedo && !(mr.flags & kMatBase);
+            if (!geo_only && !(mr.flags & kMatNormal)) tex_issue(sc.texels, mr.tex[0], s.uv.x, s.uv.y, nt);
+            if (base_tap) tex_issue(sc.texels, mr.tex[1], s.uv.x, s.uv.y, bt);
+            surface_frame(s, d, geo_only, mr, nt);
+            nrm = make_float4(s.N.x, s.N.y, s.N.z, s.inside ? 1.0f : 0.0f);
+            float b[3] = {mr.base[0], mr.base[1], mr.base[2]};   // 1x1 texture: material_resolve's value (VPT_FLAG_FURNACE included), from the table
+            if (base_tap) {                                       // otherwise its expression on this hit's texels (material_finish)
+                const V4 tb = tex_finish(bt);
+                const float c[3] = {tb.x, tb.y, tb.z};
+#pragma unroll 1
+                for (int k = 0; k < 3; k++) b[k] = (P.flags & VPT_FLAG_FURNACE) ? 1.0f : m.base_color[k] * pow_(c[k], 2.2f);
+            }
+            alb = make_float4(b[0], b[1], b[2], m.transmission);
+        }
+        if (a.depth) a.depth[px] = t;
+        if (a.ids) a.ids[px] = id;
+        if (a.normal) a.normal[px] = nrm;
+        if (a.albedo) a.albedo[px] = alb;
+        if (a.pick) { a.pick[0] = uv; a.pick[1] = pos; }
     }
 }
+void launch_first_hit(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const RenderParams& P, const FirstHitArgs& a) {
+    uint32_t g = cdiv(a.n, kTraverseBlock);
+    hipLaunchKernelGGL(k_first_hit, dim3(g < blocks ? g : blocks), dim3(kTraverseBlock), (size_t)kStackDepth * kTraverseBlock * 4, s, sc, P, a);
+}
 void launch_trace_rays(hipStream_t s, uint32_t blocks, const DeviceScene& sc, const vpt_ray* rays, uint32_t n, vpt_hit* hits) {
-    uint32_t g = cdiv(n, kTraverseBlock);
-    hipLaunchKernelGGL(k_trace_rays, dim3(g < blocks ? g : blocks), dim3(kTraverseBlock), (size_t)kStackDepth * kTraverseBlock * 4, s, sc, rays, n, hits);
+    FirstHitArgs a{}; a.rays = rays; a.hits = hits; a.n = n;
+    launch_first_hit(s, blocks, sc, RenderParams{}, a);   // (the camera is not looked at)
 }
 
 // Test hook: the samplers' lookup (grid_prep.hpp grid_value) at caller-supplied voxels, clamped to the index box as sample_density_grid clamps.

@@ -269,4 +269,25 @@ void PathTracer::SetEnvMapFilepath(const std::string& filePath) {  // PathTracer
 }
 void PathTracer::ResetPathTracing() { m_SamplesAccumulated = 0; m_DispatchCount = 0; if (m_Ctx) vpt_reset(m_Ctx); }
 
+PathTracer::Features PathTracer::RenderFeatures(uint32_t mode, uint32_t frame, bool depth, bool ids, bool normal, bool albedo) {
+    if (!m_Ctx) throw std::runtime_error("RenderFeatures before SetScene");
+    const size_t n = (size_t)m_Width * m_Height;
+    Features f;
+    if (depth) f.Depth.resize(n);
+    if (ids) f.Ids.resize(n * 4);
+    if (normal) f.Normal.resize(n * 4);
+    if (albedo) f.Albedo.resize(n * 4);
+    vpt_feature_buffers fb{};
+    fb.depth = depth ? f.Depth.data() : nullptr; fb.ids = ids ? f.Ids.data() : nullptr;
+    fb.normal = normal ? f.Normal.data() : nullptr; fb.albedo = albedo ? f.Albedo.data() : nullptr;
+    Check(vpt_render_features(m_Ctx, mode, frame, &fb), "vpt_render_features");
+    return f;
+}
+vpt_pick_result PathTracer::Pick(uint32_t x, uint32_t y) {
+    if (!m_Ctx) throw std::runtime_error("Pick before SetScene");
+    vpt_pick_result r{};
+    Check(vpt_pick(m_Ctx, x, y, &r), "vpt_pick");
+    return r;
+}
+
 }  // namespace vpthost

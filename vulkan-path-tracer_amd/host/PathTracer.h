@@ -181,6 +181,18 @@ public:
 
     void ResetPathTracing();  // PathTracer.h:183
 
+    // EXTENSION, no upstream member (the reference's only such views are the commented-out outputs of ClosestHit.slang:69-71,206-218): what the camera
+    // sees first through every pixel (vpt_render_features) or through one (vpt_pick).  mode: VPT_FEATURES_CENTER (`frame` ignored) or VPT_FEATURES_SAMPLE
+    // (the camera ray of sample 0 of dispatch `frame`).  Only the buffers asked for are produced; the accumulated image and the counters are untouched.
+    struct Features {
+        std::vector<float> Depth;     // width*height: t of the first hit, -1 on a miss
+        std::vector<uint32_t> Ids;    // width*height*4: instance, primitive, material, mesh; 0xffffffff on a miss
+        std::vector<float> Normal;    // width*height*4: shading normal, w = 1 inside
+        std::vector<float> Albedo;    // width*height*4: base colour, w = transmission
+    };
+    [[nodiscard]] Features RenderFeatures(uint32_t mode = VPT_FEATURES_CENTER, uint32_t frame = 0, bool depth = true, bool ids = true, bool normal = true, bool albedo = true);
+    [[nodiscard]] vpt_pick_result Pick(uint32_t x, uint32_t y);
+
     [[nodiscard]] vpt_ctx* Context() const { return m_Ctx; }  // for PostProcessor
 
 private:

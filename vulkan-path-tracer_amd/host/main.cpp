@@ -3,6 +3,8 @@
 //   vpt_render --scene S.gltf --luts lookup_tables.bin [--size WxH] [--spp N] [--depth D] [--seed K] [--split S]
 //              [--env-constant r,g,b] [--radiance out.f32] [--camera out.f32] [--ppm out.ppm] [--info] [--dump-scene out.bin]
 //              [--env-hdr sky.hdr] [--png out.png] [--atmosphere] [--sun altitude,azimuth]
+//              [--aov PREFIX]   after the render, the guide buffers of the pixel-centre rays (PathTracer::RenderFeatures, VPT_FEATURES_CENTER) as
+//                               PREFIX_normal.png (n * 0.5 + 0.5) and PREFIX_albedo.png, each clamped to [0, 1], (uint8)(v * 255 + 0.5), alpha 255
 //              [--env-late]   apply --env-constant / --env-hdr after SetScene instead of before (the Editor's order of calls: the map is swapped on the installed scene)
 //              [--volume minx,miny,minz,maxx,maxy,maxz,density,g,r,g,b]... [--phase hg|draine|hg+draine]
 //              [--density-bricks FILE]   AddDensityDataToVolume on the last --volume, from 8x8x8 bricks: FILE = u32 dim_x, dim_y, dim_z, bricks; u32[3 * bricks]
@@ -39,7 +41,7 @@ static void write_file(const std::string& path, const void* data, size_t bytes) 
 }
 
 int main(int argc, char** argv) {
-    std::string scene, luts, radiance, camera, ppm, png, envHdr, dumpEnv, pngTest, decodeImage, dumpImage, dump, makeLut, lutOut;
+    std::string scene, luts, radiance, camera, ppm, png, aov, envHdr, dumpEnv, pngTest, decodeImage, dumpImage, dump, makeLut, lutOut;
     std::vector<PathTracer::Volume> volumes; std::vector<std::pair<uint32_t, std::string>> brickFiles; int phase = 0; bool atmosphere = false; float sunAlt = 0.0f, sunAz = 0.0f;
     uint32_t lutSamples = 10000000u, lutTime = 0; UVec3 lutSize{0, 0, 0};
     uint32_t w = 0, h = 0, spp = 16, depth = 8, seed = 1, split = 1, gpus = 1; std::vector<int> devices;
@@ -65,6 +67,7 @@ int main(int argc, char** argv) {
         else if (a == "--camera") camera = next();
         else if (a == "--ppm") ppm = next();
         else if (a == "--png") png = next();                 // Editor::SaveToFile
+        else if (a == "--aov") aov = next();
         else if (a == "--env-hdr") envHdr = next();          // SetEnvMapFilepath
         else if (a == "--env-late") envLate = true;
         else if (a == "--dump-env") dumpEnv = next();        // with --env-hdr: decoded RGBA32F (no device needed)
@@ -263,6 +266,21 @@ int main(int argc, char** argv) {
         if (!png.empty()) {
             std::string err;
             if (!SavePNG(png, post.GetOutputImage().data(), pt.GetWidth(), pt.GetHeight(), err)) throw std::runtime_error(err);
+        }
+        if (!aov.empty()) {
+            const PathTracer::Features f = pt.RenderFeatures(VPT_FEATURES_CENTER, 0, false, false, true, true);
+            const size_t n = (size_t)pt.GetWidth() * pt.GetHeight();
+            std::vector<uint8_t> px(n * 4);
+            for (int which = 0; which < 2; which++) {
+                const std::vector<float>& src = which == 0 ? f.Normal : f.Albedo;
+                for (size_t i = 0; i < n * 4; i++) {
+                    float v = which == 0 ? src[i] * 0.5f + 0.5f : src[i];
+                    v = v < 0.0f ? 0.0f : v > 1.0f ? 1.0f : v;
+                    px[i] = (i & 3) == 3 ? 255 : (uint8_t)(v * 255.0f + 0.5f);
+                }
+                std::string err;
+                if (!SavePNG(aov + (which == 0 ? "_normal.png" : "_albedo.png"), px.data(), pt.GetWidth(), pt.GetHeight(), err)) throw std::runtime_error(err);
+            }
         }
         printf("{\"width\": %u, \"height\": %u, \"gpus\": %u, \"samples\": %u, \"seconds\": %.4f, \"msamples_per_s\": %.2f, \"vertices\": %llu, \"indices\": %llu}\n", pt.GetWidth(), pt.GetHeight(),
                gpus, pt.GetSamplesAccumulated(), sec, (double)pt.GetWidth() * pt.GetHeight() * pt.GetSamplesAccumulated() / sec / 1e6,
