@@ -33,6 +33,12 @@ namespace vpt {
 #ifndef VPT_DIAG_REFILL_LANES
 #define VPT_DIAG_REFILL_LANES 0
 #endif
+// A/B switch (tests/tools/build_variant.py -DVPT_WHOLE_CAM_LDS=0: the kernel before it): the camera lives in LDS between two refills and in no
+// register, and one-sample frames are a compile-time fact.  Cornell 1080p, same box, alternating: 8827-8833 Msamples/s against 8641-8658
+// (profiles/r11_whole_uniform_ab.md).
+#ifndef VPT_WHOLE_CAM_LDS
+#define VPT_WHOLE_CAM_LDS 1
+#endif
 constexpr int kWalkDone = 0x7fffffff;
 template <class Stack>
 __device__ __forceinline__ int walk_pop(Stack& stack) { return stack.sp ? (int)stack.pop() : kWalkDone; }
@@ -183,12 +189,29 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                                                             uint32_t static_rounds, uint32_t chunk_tiles) {
     sc.strict_hits = STRICT ? 1u : 0u;
     if (PLAIN) { sc.all_plain = 1u; sc.env_black = 1u; } else sc.all_plain = 0u;
+#if VPT_WHOLE_CAM_LDS
+    // the planner gives this kernel one-sample frames only (path_plan.hpp whole_possible): a compile-time fact here, so shade_core's "next sample of the
+    // pixel" branch — the other reader of the camera's matrices — drops out and nothing of the camera is live outside the refill step
+    P.samples_per_frame = 1u;
+#endif
     if (P.dispatch_base_dev) dispatch_base = *P.dispatch_base_dev;   // a replayed graph: the batch's first dispatch index lives in device memory
     const bool rq = (P.flags & VPT_FLAG_RAY_QUERIES) != 0u;
     extern __shared__ __align__(16) unsigned char smem[];
     const TravStackT<kWholeStackRows> stack = make_stack<kWholeStackRows>(smem, sc.stack_overflow);
     float4* lds_nodes = reinterpret_cast<float4*>(smem + kWholeStackRows * kTraverseBlock * 4);
     float4* lds_tris = lds_nodes + sc.node_count * 8;
+#if VPT_WHOLE_CAM_LDS
+    // camera_ray's part of P, read once per tile of 64 samples: from LDS there (a uniform address broadcasts) instead of ~40 scalar registers held
+    // across the shade and trace steps; staged behind stage_scene's barrier
+    __shared__ CameraBlock cam;
+    if (threadIdx.x == 0u) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) { cam.view_inv[i] = P.view_inv[i]; cam.proj_inv[i] = P.proj_inv[i]; }
+        cam.width = P.width; cam.height = P.height; cam.focus_distance = P.focus_distance; cam.dof_strength = P.dof_strength;
+    }
+#else
+    const RenderParams& cam = P;
+#endif
     stage_scene<true>(sc, lds_nodes, lds_tris);
     constexpr uint32_t kWaves = kTraverseBlock / 64u;
     __shared__ uint32_t r_slot[kWaves][128], r_prim[kWaves][128], r_inst[kWaves][128];
@@ -298,7 +321,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                         const uint32_t seed = pcg_hash(P.base_seed + dispatch_base + f);  // PathTracer.cpp:139 with an explicit seed
                         Rng r; r.s = y + P.width * x + seed;                              // RayGen.slang:28
                         V3 go, gd;
-                        camera_ray(P, r, x, y, go, gd);
+                        camera_ray(cam, r, x, y, go, gd);
                         const uint32_t j = lane_id();
                         f_slot[wave][j] = gslot; f_rng[wave][j] = r.s;
                         f_ox[wave][j] = go.x; f_oy[wave][j] = go.y; f_oz[wave][j] = go.z;

@@ -512,8 +512,16 @@ __device__ inline void sample_emissive(const DeviceScene& sc, Rng& r, V3 pos, V3
     to_light_out = to_light; cpdf_out = cpdf;
 }
 
-// Camera ray + AA jitter + DOF, RayGen.slang:35-50 (4 draws, the DOF pair always drawn).
-__device__ inline void camera_ray(const RenderParams& P, Rng& r, uint32_t x, uint32_t y, V3& origin, V3& direction) {
+// What camera_ray reads of RenderParams, field for field: the whole-path kernel keeps a copy per block in LDS (kernels_whole.hip), where it
+// costs no scalar registers between two refills.
+struct CameraBlock {
+    float view_inv[16], proj_inv[16];
+    uint32_t width, height;
+    float focus_distance, dof_strength;
+};
+// Camera ray + AA jitter + DOF, RayGen.slang:35-50 (4 draws, the DOF pair always drawn).  Cam: RenderParams or CameraBlock.
+template <class Cam>
+__device__ inline void camera_ray(const Cam& P, Rng& r, uint32_t x, uint32_t y, V3& origin, V3& direction) {
     float j0 = r.uf(), j1 = r.uf();
     float cx = ((float)x + 0.5f) + (j0 * (0.5f - -0.5f) + -0.5f);
     float cy = ((float)y + 0.5f) + (j1 * (0.5f - -0.5f) + -0.5f);
