@@ -10,6 +10,8 @@
 namespace vpt {
 // tris_in: world-space triangles in instance-major order (gid = index). Produces 128 B four-wide nodes
 // (root = node 0) and the triangles permuted into leaf order.
+// Numbering contract: every inner child's index is greater than its parent's, refits included (a refit keeps the topology), so one pass in ascending
+// index order meets a parent before its children and one in descending order a child before its parent (bvh_refit.hpp levels; tests/test_whole_walk_cpu.py).
 // nodes8_out (optional): the same binary tree collapsed eight-wide with octant-ordered slots, over the same tris_out.
 void build_bvh(const std::vector<BvhTri>& tris_in, std::vector<BvhNode>& nodes_out, std::vector<BvhNodeWide>& wide_out, std::vector<BvhTri>& tris_out, int* depth_out,
                std::vector<BvhNode8>* nodes8_out = nullptr, bool spatial_splits = false, bool parallel = true);

@@ -284,12 +284,19 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                     if (vis) E = E + o.clight;
                     nrays++;
                 }
-                const V3 light = whole_finish(P, ps, slot, E, in_.thr_prev, light_prev, o);
-                alive = o.alive;
-                if (alive) {
-                    has_ray = true;
-                    rng_s = o.rng; porg = o.new_o; pdir = o.new_d; depth = o.new_depth; in_medium = o.in_medium; thr = o.thr; pdf = o.new_pdf; lightp = light;
-                }
+                // contribution and the survivor's registers: the same statements as a closure called once.  Nothing else differs, and why the compiler
+                // then allocates better is not understood: the PLAIN instantiation keeps 232 instead of 270 scalar-spill lane operations and 1584 instead
+                // of 1703 SALU instructions (VALU 5491 / 5486), and Cornell 1080p runs at 8926-8945 against 8818-8831 Msamples/s, same box, alternating
+                // (profiles/r12_whole_walk_ab.md; a compiler update may take it back: tests/tools/spill_report.py shows the counts)
+                auto finish = [&]() {
+                    const V3 light = whole_finish(P, ps, slot, E, in_.thr_prev, light_prev, o);
+                    alive = o.alive;
+                    if (alive) {
+                        has_ray = true;
+                        rng_s = o.rng; porg = o.new_o; pdir = o.new_d; depth = o.new_depth; in_medium = o.in_medium; thr = o.thr; pdf = o.new_pdf; lightp = light;
+                    }
+                };
+                finish();
             }
             hit_head += cnt; hit_count -= cnt;
             w_rays += (uint32_t)__popcll(__ballot(nrays >= 1u)) + (uint32_t)__popcll(__ballot(nrays >= 2u));
