@@ -56,7 +56,7 @@ __device__ __forceinline__ bool lds_closest_vote(const LdsSceneSrc& src, V3 o, V
         const bool node_wins = 4u * nn > kVoteWeight4 * nl;   // a node step retires about twice the work of a triangle step
         if (node_wins & at_node) {
             NodeDataWide n;
-            src.node(cur, n);
+            load_node(src, slab, cur, n);
             if (COUNT) st.nodes++;
             float t0, t1, t2, t3;
             node_entries(n, slab, tmin, best.t, t0, t1, t2, t3);
@@ -104,7 +104,7 @@ __device__ __forceinline__ bool lds_occluded_vote(const LdsSceneSrc& src, V3 o, 
         const bool node_wins = 4u * nn > kVoteWeight4 * nl;
         if (node_wins & at_node) {
             NodeDataWide n;
-            src.node(cur, n);
+            load_node(src, slab, cur, n);
             if (COUNT) st.nodes++;
             float t0, t1, t2, t3;
             node_entries(n, slab, tmin, tlimit, t0, t1, t2, t3);

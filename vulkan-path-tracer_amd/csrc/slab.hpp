@@ -27,6 +27,19 @@
 // through a distance below tlimit, as before.
 // Rays the guard turns away — a camera farther than 16 scene sizes out, an origin whose product with a clamped reciprocal overflows — take
 // the subtract form, whose error does not grow with |o|.  Both forms are conservative, so hits do not depend on which one ran.
+//
+//   box_entry_dir  the same six fmas on planes the CALLER has sorted: near = the min plane of an axis where inv > 0, the max plane where inv < 0
+//                  (decided once per search, traverse.hpp make_slab), far = the other one — no min / max per axis
+//
+// WHY ITS VALUES ARE box_entry_fma's (and, on planes moved to the origin with oi = 0, box_entry's): b -> fl(b * inv - oi) is monotone — rising
+// for inv >= 0, falling for inv < 0; the exact value is, and rounding keeps order — and a box has min <= max on every axis (the builder and the refit
+// write them so; an unused slot has min = max), so the near plane's distance IS fmin(t0, t1) and the far plane's IS fmax(t0, t1), the very floats;
+// moving both planes by the same o keeps min <= max, since rounding a difference keeps order too.  Where t0 = t1 (an unused slot, a flat box,
+// inv = +-0) either choice is the same float.  No NaN is there to make min / max differ from a choice: oi is finite in the fma form (the guard) and
+// 0 in the subtract form, reciprocals are clamped, planes are finite — inf - inf and 0 * inf cannot arise, in either function alike.  Only the SIGN of a zero
+// may differ (fmin(+0, -0) against the plane picked), and tn >= tmin > 0 in every caller, so a zero never is tn and tf = +-0 rejects either way.
+// (An INVERTED box, min > max — neither the builder nor the refit writes one into an fp32 node — is the one input on which the two would differ.)
+// tests/test_box_entry_dir_cpu.py compares the two float for float.
 #pragma once
 #include "../../include/vpt_fp32.h"
 
@@ -57,6 +70,15 @@ VPT_HD float box_entry_fma(float bx0, float by0, float bz0, float bx1, float by1
     float t0z = __builtin_fmaf(bz0, inv.z, -oi.z), t1z = __builtin_fmaf(bz1, inv.z, -oi.z);
     float tn = fmax_(fmax_(fmin_(t0x, t1x), fmin_(t0y, t1y)), fmax_(fmin_(t0z, t1z), tmin));
     float tf = fmin_(fmin_(fmax_(t0x, t1x), fmax_(t0y, t1y)), fmin_(fmax_(t0z, t1z), tlimit));
+    return (tn <= tf * 1.0000005f) ? tn : kMissT;
+}
+// The same on planes sorted by the ray's direction (above): n* = the plane of the axis the ray meets first, f* = the other one.
+VPT_HD float box_entry_dir(float nx, float ny, float nz, float fx, float fy, float fz, V3 oi, V3 inv, float tmin, float tlimit) {
+    float tnx = __builtin_fmaf(nx, inv.x, -oi.x), tfx = __builtin_fmaf(fx, inv.x, -oi.x);
+    float tny = __builtin_fmaf(ny, inv.y, -oi.y), tfy = __builtin_fmaf(fy, inv.y, -oi.y);
+    float tnz = __builtin_fmaf(nz, inv.z, -oi.z), tfz = __builtin_fmaf(fz, inv.z, -oi.z);
+    float tn = fmax_(fmax_(tnx, tny), fmax_(tnz, tmin));
+    float tf = fmin_(fmin_(tfx, tfy), fmin_(tfz, tlimit));
     return (tn <= tf * 1.0000005f) ? tn : kMissT;
 }
 // The subtract form, for every ray: the planes are moved to the ray's origin first and the shared code runs with oi = 0 — fma(b - o, inv, -0)

@@ -81,8 +81,16 @@ __device__ inline void unpack_node(const uint4& w0, const uint4& w1, const uint4
     n.c0 = (int)w3.x; n.c1 = (int)w3.y; n.c2 = (int)w3.z; n.c3 = (int)w3.w;
 }
 
+// A/B switch of the LDS-tree node step (tests/tools/build_variant.py -DVPT_LDS_PLANES_BY_SIGN=0: the kernels before it, instruction for instruction):
+// load_node reads each axis' near and far plane vectors by the sign of the ray's direction and the box test sorts nothing (slab.hpp box_entry_dir).
+// Cornell 1080p, same box, alternating: 9110-9125 Msamples/s against 8932-8935 (profiles/r13_lds_node_step_ab.md).
+#ifndef VPT_LDS_PLANES_BY_SIGN
+#define VPT_LDS_PLANES_BY_SIGN 1
+#endif
+// near* / far*: the planes of the four children this ray meets first / last on each axis (load_node picks them by the sign of inv).
+// With -DVPT_LDS_PLANES_BY_SIGN=0 they are the min and the max planes as stored, and the box test sorts them per axis.
 struct NodeDataWide {
-    float4 minx, miny, minz, maxx, maxy, maxz;
+    float4 nearx, neary, nearz, farx, fary, farz;
     int c0, c1, c2, c3;
 };
 
@@ -107,9 +115,9 @@ struct LdsSceneSrc {
     const float4* tris;   // LDS
     bool strict;          // DeviceScene::strict_hits
     float reach;          // kSlabFmaReach * DeviceScene::scene_extent: origins within it may take the fma form of the box test (slab.hpp)
-    __device__ inline void node(int i, NodeDataWide& n) const {
+    __device__ inline void node(int i, NodeDataWide& n) const {   // planes as stored: near* = min, far* = max
         const float4* p = nodes + i * 8;
-        n.minx = p[0]; n.miny = p[1]; n.minz = p[2]; n.maxx = p[3]; n.maxy = p[4]; n.maxz = p[5];
+        n.nearx = p[0]; n.neary = p[1]; n.nearz = p[2]; n.farx = p[3]; n.fary = p[4]; n.farz = p[5];
         float4 c = p[6];
         n.c0 = __float_as_int(c.x); n.c1 = __float_as_int(c.y); n.c2 = __float_as_int(c.z); n.c3 = __float_as_int(c.w);
     }
@@ -136,16 +144,33 @@ template <bool STRICT> __device__ inline RaySlab make_slab(const GlobalSceneSrc&
 // `fused` is decided for the WAVE — every lane in the search has an origin the guard admits (slab.hpp slab_fma_ok) — so the choice is a
 // scalar branch per node step; either form is conservative, so a ray's hits do not depend on its neighbours' origins.  The validating (STRICT)
 // instantiations keep the subtract form and carry no guard: they are not where the time goes, and the library stays under its size bound.
+// selx / sely / selz: where in a node (BvhNodeWide: float4 0..2 = min x y z, 3..5 = max x y z) this ray's NEAR plane vector of the axis is — the max
+// one for a negative reciprocal, as RaySlab::neg* picks the plane byte of a quantised node; the far one is the other of the pair (load_node).
 struct RaySlabWide {
     V3 o, inv, oi;
     bool fused;
+    int selx, sely, selz;
 };
 template <bool STRICT> __device__ inline RaySlabWide make_slab(const LdsSceneSrc& src, V3 o, V3 d) {
     RaySlabWide r;
     r.o = o; r.inv = safe_inverse(d); r.oi = slab_oi(o, r.inv);
+    r.selx = r.inv.x < 0.0f ? 3 : 0; r.sely = r.inv.y < 0.0f ? 4 : 1; r.selz = r.inv.z < 0.0f ? 5 : 2;
     r.fused = !STRICT && __ballot(!slab_fma_ok(o, r.oi, src.reach)) == 0ull;
     if (!r.fused) r.oi = vptfp::v3(0.0f, 0.0f, 0.0f);   // the subtract form: planes moved to the origin per node, then the same code (slab.hpp box_entry)
     return r;
+}
+// The node a search stands at.  Quantised nodes as they are; fp32 nodes in LDS with every axis' near and far plane vectors read from the min or
+// the max vector by per-lane address (the node is 128-byte aligned data either way: six 16-byte reads and the child word, as before).
+__device__ inline void load_node(const GlobalSceneSrc& src, const RaySlab&, int i, NodeData& n) { src.node(i, n); }
+__device__ inline void load_node(const LdsSceneSrc& src, const RaySlabWide& r, int i, NodeDataWide& n) {
+#if VPT_LDS_PLANES_BY_SIGN
+    const float4* p = src.nodes + i * 8;
+    n.nearx = p[r.selx]; n.neary = p[r.sely]; n.nearz = p[r.selz]; n.farx = p[3 - r.selx]; n.fary = p[5 - r.sely]; n.farz = p[7 - r.selz];
+    float4 c = p[6];
+    n.c0 = __float_as_int(c.x); n.c1 = __float_as_int(c.y); n.c2 = __float_as_int(c.z); n.c3 = __float_as_int(c.w);
+#else
+    src.node(i, n);
+#endif
 }
 template <int K> __device__ inline float byte_f(uint32_t w) { return (float)((w >> (8 * K)) & 0xffu); }  // v_cvt_f32_ubyteK
 
@@ -195,18 +220,24 @@ __device__ inline void node_entries_pk(const NodeData& n, const RaySlab& r, floa
     const vpt_f2 s01 = tf01 * slack, s23 = tf23 * slack;
     t0 = (tn0 <= s01.x) ? tn0 : kMissT; t1 = (tn1 <= s01.y) ? tn1 : kMissT; t2 = (tn2 <= s23.x) ? tn2 : kMissT; t3 = (tn3 <= s23.y) ? tn3 : kMissT;
 }
-// fp32 nodes: the plain slab test (slab.hpp), one fma per plane (24 instead of 48 fp32 operations per node step) when the wave's origins allow it.
+// fp32 nodes: the plain slab test (slab.hpp), one fma per plane (24 instead of 48 fp32 operations per node step) when the wave's origins allow it,
+// on planes load_node has sorted by the ray's direction (box_entry_dir: the values of box_entry_fma without its six min / max per box).
+// (Measured and not taken: skipping the tests of slots 2 and 3 where no lane of the wave stands at a node that uses them — the Cornell tree's nodes 1 and 2
+// have two unused slots each — behind a ballot on the loaded plane: it issues fewer VALU instructions and is slower, profiles/REJECTED.md.)
 __device__ inline void node_entries(const NodeDataWide& n, const RaySlabWide& r, float tmin, float tlimit, float& t0, float& t1, float& t2, float& t3) {
-    float4 minx = n.minx, miny = n.miny, minz = n.minz, maxx = n.maxx, maxy = n.maxy, maxz = n.maxz;
+    float4 nx = n.nearx, ny = n.neary, nz = n.nearz, fx = n.farx, fy = n.fary, fz = n.farz;
     if (!r.fused) {   // box_entry(): the 24 subtractions here, oi == 0 behind them
-        minx.x -= r.o.x; minx.y -= r.o.x; minx.z -= r.o.x; minx.w -= r.o.x; maxx.x -= r.o.x; maxx.y -= r.o.x; maxx.z -= r.o.x; maxx.w -= r.o.x;
-        miny.x -= r.o.y; miny.y -= r.o.y; miny.z -= r.o.y; miny.w -= r.o.y; maxy.x -= r.o.y; maxy.y -= r.o.y; maxy.z -= r.o.y; maxy.w -= r.o.y;
-        minz.x -= r.o.z; minz.y -= r.o.z; minz.z -= r.o.z; minz.w -= r.o.z; maxz.x -= r.o.z; maxz.y -= r.o.z; maxz.z -= r.o.z; maxz.w -= r.o.z;
+        nx.x -= r.o.x; nx.y -= r.o.x; nx.z -= r.o.x; nx.w -= r.o.x; fx.x -= r.o.x; fx.y -= r.o.x; fx.z -= r.o.x; fx.w -= r.o.x;
+        ny.x -= r.o.y; ny.y -= r.o.y; ny.z -= r.o.y; ny.w -= r.o.y; fy.x -= r.o.y; fy.y -= r.o.y; fy.z -= r.o.y; fy.w -= r.o.y;
+        nz.x -= r.o.z; nz.y -= r.o.z; nz.z -= r.o.z; nz.w -= r.o.z; fz.x -= r.o.z; fz.y -= r.o.z; fz.z -= r.o.z; fz.w -= r.o.z;
     }
-    t0 = box_entry_fma(minx.x, miny.x, minz.x, maxx.x, maxy.x, maxz.x, r.oi, r.inv, tmin, tlimit);
-    t1 = box_entry_fma(minx.y, miny.y, minz.y, maxx.y, maxy.y, maxz.y, r.oi, r.inv, tmin, tlimit);
-    t2 = box_entry_fma(minx.z, miny.z, minz.z, maxx.z, maxy.z, maxz.z, r.oi, r.inv, tmin, tlimit);
-    t3 = box_entry_fma(minx.w, miny.w, minz.w, maxx.w, maxy.w, maxz.w, r.oi, r.inv, tmin, tlimit);
+#if VPT_LDS_PLANES_BY_SIGN
+#define VPT_BOX(C) box_entry_dir(nx.C, ny.C, nz.C, fx.C, fy.C, fz.C, r.oi, r.inv, tmin, tlimit)
+#else
+#define VPT_BOX(C) box_entry_fma(nx.C, ny.C, nz.C, fx.C, fy.C, fz.C, r.oi, r.inv, tmin, tlimit)
+#endif
+    t0 = VPT_BOX(x); t1 = VPT_BOX(y); t2 = VPT_BOX(z); t3 = VPT_BOX(w);
+#undef VPT_BOX
 }
 __device__ inline void cswap(float& ta, int& ca, float& tb, int& cb) {
     bool sw = tb < ta;
@@ -227,7 +258,7 @@ __device__ inline bool trace_closest_pass(const Src& src, V3 o, V3 d, float tmin
     while (true) {
         if (cur >= 0) {
             typename Src::Node n;
-            src.node(cur, n);
+            load_node(src, slab, cur, n);
             if (COUNT) st.nodes++;
             float t0, t1, t2, t3;
             node_entries(n, slab, tmin, best.t, t0, t1, t2, t3);
@@ -316,7 +347,7 @@ __device__ inline bool trace_occluded_pass(const Src& src, V3 o, V3 d, float tmi
     while (true) {
         if (cur >= 0) {
             typename Src::Node n;
-            src.node(cur, n);
+            load_node(src, slab, cur, n);
             if (COUNT) st.nodes++;
             float t0, t1, t2, t3;
             node_entries(n, slab, tmin, tlimit, t0, t1, t2, t3);
