@@ -588,6 +588,44 @@ int vpt_render_features(vpt_ctx* ctx, uint32_t mode, uint32_t frame, const vpt_f
 typedef struct vpt_pick_result { uint32_t instance, primitive, material, mesh; float t, u, v; float position[3]; } vpt_pick_result;
 int vpt_pick(vpt_ctx* ctx, uint32_t x, uint32_t y, vpt_pick_result* out);   /* CENTER ray of one pixel; a miss is VPT_OK with ids 0xffffffff and t = -1 */
 
+/* ---- denoising -----------------------------------------------------------------------------------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010, as SVGF uses it) over the accumulation image, steered by the
+ * VPT_FEATURES_CENTER guide images above, on the device, in the context's stream: what turns a 1-4 spp viewport frame into something
+ * to show.  The reference has no counterpart.  Every call traces the guides anew (camera, scene, materials, instance transforms, flags
+ * and size as they stand), prepares, and runs `iterations` passes of 5 x 5 taps at steps 1, 2, 4 ...; the arithmetic, tap by tap, is
+ * csrc/denoise.hpp's, and the device result equals a host compile of that header bit for bit.
+ *   hit pixels        e' = sum k w e / sum k w over the taps that are inside the image and hits; w = exp(-(dn + dz + dc)) with
+ *                     dn = max(0, 1 - n_p.n_q) / sigma_normal, dz = |t_p - t_q| / (sigma_depth step max(t_p, 1e-6)),
+ *                     dc = |e_p - e_q|^2 / (sigma_color 2^-pass)^2; w = 1 at the centre.
+ *   VPT_DENOISE_DEMODULATE  the filter runs on colour / max(albedo, 1e-3) and the last pass multiplies it back: texture detail survives.
+ *   miss pixels       (nothing hit: environment) keep their input bit for bit and are never a tap of another pixel.
+ *   iterations == 0   the output is a copy of the input.
+ *   non-finite input  propagates to every pixel whose weight for it is not exactly 0; there is no guard.
+ *   result            an RGBA32F image kept in the context (alpha copied from the input) — a SNAPSHOT: later renders do not update it —
+ *                     and, if the pointer is not NULL, copied to the caller (width*height*16 bytes; a device pointer 16-byte aligned).
+ *   memory            on first use, 84 bytes per pixel (36 of guides, three RGBA32F images); re-made after vpt_resize.
+ *   side effects      like vpt_render_features: the accumulation, the frame counters and vpt_stats are untouched (stack_spills is recounted).
+ *   vpt_denoise       blocking.  vpt_denoise_device: enqueued behind the frames in flight like vpt_postprocess_device, with a ticket.
+ *   errors            VPT_ERR_NO_SCENE before vpt_set_scene; VPT_ERR_INVALID_ARGUMENT for a NULL ctx or params, iterations >
+ *                     VPT_DENOISE_MAX_ITERATIONS, a sigma that is not > 0, unknown flag bits, an unaligned device pointer, a sharded
+ *                     context before vpt_assemble_shards.  A failed call leaves the context usable and the previous result valid.
+ * vpt_set_post_source: which image vpt_postprocess / vpt_postprocess_device read.  VPT_POST_SOURCE_DENOISED: the latest denoised image;
+ * without one of the current size (never denoised, or resized since) they return VPT_ERR_INVALID_ARGUMENT. */
+#define VPT_DENOISE_DEMODULATE 1u
+#define VPT_DENOISE_MAX_ITERATIONS 6u
+typedef struct vpt_denoise_params {
+    uint32_t iterations;
+    float sigma_color, sigma_normal, sigma_depth;
+    uint32_t flags;      /* VPT_DENOISE_* */
+    uint32_t reserved;
+} vpt_denoise_params;
+void vpt_default_denoise_params(vpt_denoise_params* out);   /* 5 iterations, VPT_DENOISE_DEMODULATE, sigma_color 1 (in units of radiance), sigma_normal 0.1, sigma_depth 0.05 */
+int vpt_denoise(vpt_ctx* ctx, const vpt_denoise_params* params, float* rgba_host);
+int vpt_denoise_device(vpt_ctx* ctx, const vpt_denoise_params* params, void* rgba_device, uint64_t* ticket);
+#define VPT_POST_SOURCE_RADIANCE 0u   /* the accumulation image (default) */
+#define VPT_POST_SOURCE_DENOISED 1u   /* the image the latest vpt_denoise / vpt_denoise_device left in the context */
+int vpt_set_post_source(vpt_ctx* ctx, uint32_t source);
+
 /* ---- energy-compensation lookup tables -------------------------------------------
  * Replaces LookupTableCalculator::CalculateTable(tableSize, sampleCount) (LookupTableCalculator.cpp:44-157)
  * with its shaders LookupReflect.slang / LookupRefract.slang (+ ABOVE_SURFACE / BELOW_SURFACE): sampleCount/20

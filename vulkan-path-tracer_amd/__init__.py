@@ -13,6 +13,7 @@ from . import _abi, imagefiles, scenes  # noqa: F401
 from ._abi import default_params, default_post_params, volume, atmosphere  # noqa: F401
 from ._abi import PHASE_HENYEY_GREENSTEIN, PHASE_DRAINE, PHASE_HENYEY_GREENSTEIN_PLUS_DRAINE  # noqa: F401
 from ._abi import FEATURES_CENTER, FEATURES_SAMPLE  # noqa: F401
+from ._abi import default_denoise_params, DENOISE_DEMODULATE, DENOISE_MAX_ITERATIONS, POST_SOURCE_RADIANCE, POST_SOURCE_DENOISED  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -331,6 +332,27 @@ class PathTracer:
         _check(self.lib, self.ctx, self.lib.vpt_pick(self.ctx, x, y, C.byref(r)), "vpt_pick")
         return {"instance": r.instance, "primitive": r.primitive, "material": r.material, "mesh": r.mesh, "t": np.float32(r.t), "u": np.float32(r.u),
                 "v": np.float32(r.v), "position": np.array(list(r.position), np.float32)}
+
+    # ---- denoising (include/vpt.h vpt_denoise / vpt_denoise_device / vpt_set_post_source)
+    def denoise(self, params=None):
+        """vpt_denoise: the accumulation image through the edge-avoiding a-trous filter -> float32 [h, w, 4].  The image also stays in the context
+        (a snapshot) for set_post_source(POST_SOURCE_DENOISED)."""
+        dp = params or default_denoise_params()
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _check(self.lib, self.ctx, self.lib.vpt_denoise(self.ctx, C.byref(dp), out.ctypes.data), "vpt_denoise")
+        return out
+
+    def denoise_device(self, params=None, ptr=None):
+        """vpt_denoise_device: enqueued behind the frames in flight; the image is copied to device pointer `ptr` (16-byte aligned, or None) on the
+        context's device; returns the ticket."""
+        dp = params or default_denoise_params()
+        ticket = C.c_uint64(0)
+        _check(self.lib, self.ctx, self.lib.vpt_denoise_device(self.ctx, C.byref(dp), ptr, C.byref(ticket)), "vpt_denoise_device")
+        return int(ticket.value)
+
+    def set_post_source(self, source):
+        """vpt_set_post_source: POST_SOURCE_RADIANCE (default) or POST_SOURCE_DENOISED — the image postprocess / postprocess_device read."""
+        _check(self.lib, self.ctx, self.lib.vpt_set_post_source(self.ctx, source), "vpt_set_post_source")
 
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("primitive", "<u4"), ("instance", "<u4")])

@@ -215,6 +215,25 @@ class PickResult(C.Structure):  # vpt_pick_result
                 ("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("position", C.c_float * 3)]
 
 
+DENOISE_DEMODULATE, DENOISE_MAX_ITERATIONS = 1, 6
+POST_SOURCE_RADIANCE, POST_SOURCE_DENOISED = 0, 1
+
+
+class DenoiseParams(C.Structure):  # vpt_denoise_params
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def default_denoise_params(**kw):
+    """vpt_default_denoise_params: 5 iterations, albedo demodulation, sigma_color 1, sigma_normal 0.1, sigma_depth 0.05."""
+    p = DenoiseParams(5, 1.0, 0.1, 0.05, DENOISE_DEMODULATE, 0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 # every symbol include/vpt.h declares, with (restype, argtypes)
 PROTOTYPES = {
     "vpt_create": (C.c_void_p, [C.POINTER(Config), C.POINTER(C.c_int)]),
@@ -266,6 +285,10 @@ PROTOTYPES = {
     "vpt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vpt_render_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(FeatureBuffers)]),
     "vpt_pick": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PickResult)]),
+    "vpt_default_denoise_params": (None, [C.POINTER(DenoiseParams)]),
+    "vpt_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]),
+    "vpt_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vpt_set_post_source": (C.c_int, [C.c_void_p, C.c_uint32]),
     "vpt_lab_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "vpt_lab_set_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "vpt_lab_trace": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),

@@ -43,6 +43,8 @@ void free_render_buffers(vpt_ctx* c) {
     c->mips.clear(); c->mip_sizes.clear();
     if (c->post_out) (void)hipFree(c->post_out);
     c->post_out = nullptr; c->post_w = c->post_h = 0;
+    if (c->dn_block) (void)hipFree(c->dn_block);   // the denoiser's images: re-made by the next vpt_denoise*, whose result is gone with them
+    c->dn_block = nullptr; c->dn_w = c->dn_h = 0; c->dn_valid = false;
 }
 
 // Size checks of a (width, height) before anything is freed or changed; *frames_out = the largest batch this context will render.

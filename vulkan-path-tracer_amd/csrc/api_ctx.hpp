@@ -212,6 +212,12 @@ struct vpt_ctx {
     std::vector<std::pair<uint32_t, uint32_t>> mip_sizes;
     uint8_t* post_out = nullptr;
     uint32_t post_w = 0, post_h = 0;
+    // denoise (api_post.hip): allocated on the first vpt_denoise*, freed with the render buffers (vpt_resize, vpt_destroy)
+    float* dn_block = nullptr;       // one allocation: guide (normal, then packed) | albedo | ping | pong | out | depth
+    float *dn_guide = nullptr, *dn_albedo = nullptr, *dn_depth = nullptr, *dn_ping = nullptr, *dn_pong = nullptr, *dn_out = nullptr;
+    uint32_t dn_w = 0, dn_h = 0;     // size the block was made for
+    bool dn_valid = false;           // dn_out holds a denoised image of dn_w x dn_h
+    uint32_t post_source = VPT_POST_SOURCE_RADIANCE;
 
     // profiling events
     std::vector<hipEvent_t> ev_pool;
@@ -270,6 +276,8 @@ void collect_timing(vpt_ctx* c);   // call after a stream sync
 // api_scene.hip
 void free_scene(vpt_ctx* c);
 int refresh_material_tables(vpt_ctx* c);
+// One launch of k_first_hit on the main lane's stream, nothing waited for (vpt_render_features, vpt_pick, vpt_denoise): every pointer of `a` is device memory.
+void enqueue_first_hit(vpt_ctx* c, const FirstHitArgs& a);
 // A scene table holding the n elements at src, zeros behind them up to min_elems (at least one element), freed with the scene: DeviceScene's
 // pointer to it and, for a table that is written after the upload, the writable one (vpt_ctx::Writable) are set here, from one allocation sized by
 // their own element type.  (the work is done once, on bytes; the templates only size and type it)

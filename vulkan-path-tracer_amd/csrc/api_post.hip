@@ -33,7 +33,7 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
     int rc = ensure_post_buffers(c);
     if (rc) return rc;
     hipStream_t s = c->main.stream;
-    const float* hdr = whole_image(c);
+    const float* hdr = c->post_source == VPT_POST_SOURCE_DENOISED ? c->dn_out : whole_image(c);   // (post_source_ready has been asked)
     const uint32_t W = c->P.width, H = c->P.height;
     uint32_t mip_count = std::max(1u, std::min(pp->mip_count, (uint32_t)c->mips.size()));
     const bool linear_tap = (c->params.flags & VPT_FLAG_TONEMAP_LINEAR_BLOOM_TAP) != 0;
@@ -102,15 +102,109 @@ int post_preconditions(vpt_ctx* c) {
     if (c->P.shard_count > 1 && !c->full_valid) return fail(c, VPT_ERR_INVALID_ARGUMENT, "sharded context: call vpt_assemble_shards first");
     return VPT_OK;
 }
+// VPT_POST_SOURCE_DENOISED needs a denoised image of the current size: never denoised, or resized since, is the caller's error.
+int post_source_ready(vpt_ctx* c) {
+    if (c->post_source == VPT_POST_SOURCE_DENOISED && !(c->dn_valid && c->dn_w == c->P.width && c->dn_h == c->P.height))
+        return fail(c, VPT_ERR_INVALID_ARGUMENT, "post source is the denoised image and there is none of this size: call vpt_denoise first");
+    return VPT_OK;
+}
+
+// ---- vpt_denoise
+int check_denoise(vpt_ctx* c, const vpt_denoise_params* dp, const void* device_out) {
+    if (!c || !dp) return VPT_ERR_INVALID_ARGUMENT;
+    if (dp->iterations > VPT_DENOISE_MAX_ITERATIONS) return fail(c, VPT_ERR_INVALID_ARGUMENT, "more than VPT_DENOISE_MAX_ITERATIONS iterations");
+    if (!(dp->sigma_color > 0.0f) || !(dp->sigma_normal > 0.0f) || !(dp->sigma_depth > 0.0f)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "every sigma must be > 0");
+    if (dp->flags & ~VPT_DENOISE_DEMODULATE) return fail(c, VPT_ERR_INVALID_ARGUMENT, "unknown denoise flag bits");
+    if (((uintptr_t)device_out & 15u) != 0u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "the device image must be 16-byte aligned");
+    if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
+    return post_preconditions(c);
+}
+int ensure_denoise_buffers(vpt_ctx* c) {
+    const uint32_t w = c->P.width, h = c->P.height;
+    if (c->dn_block && c->dn_w == w && c->dn_h == h) return VPT_OK;
+    if (c->dn_block) (void)hipFree(c->dn_block);
+    c->dn_block = nullptr; c->dn_valid = false; c->dn_w = c->dn_h = 0;
+    const size_t npx = (size_t)w * h;
+    HIPCHK(c, hipMalloc((void**)&c->dn_block, npx * (5 * 16 + 4)));   // five RGBA32F images, then the depths: every image 16-byte aligned
+    float* p = c->dn_block;
+    c->dn_guide = p; c->dn_albedo = p + npx * 4; c->dn_ping = p + npx * 8; c->dn_pong = p + npx * 12; c->dn_out = p + npx * 16; c->dn_depth = p + npx * 20;
+    c->dn_w = w; c->dn_h = h;
+    return VPT_OK;
+}
+// Guides, prepare, passes: the launches on the main lane's stream, nothing waited for.  The image is whole_image(c) as the stream finds it.
+int enqueue_denoise(vpt_ctx* c, const vpt_denoise_params* dp) {
+    int rc = ensure_denoise_buffers(c);
+    if (rc) return rc;
+    hipStream_t s = c->main.stream;
+    const uint32_t W = c->P.width, H = c->P.height;
+    const float* src = whole_image(c);
+    if (dp->iterations == 0) {
+        HIPCHK(c, hipMemcpyAsync(c->dn_out, src, (size_t)W * H * 16, hipMemcpyDeviceToDevice, s));
+    } else {
+        const bool demodulate = (dp->flags & VPT_DENOISE_DEMODULATE) != 0;
+        FirstHitArgs a{};
+        a.n = ((W + 7u) / 8u) * ((H + 7u) / 8u) * 64u;
+        a.mode = VPT_FEATURES_CENTER;
+        a.depth = c->dn_depth; a.normal = (float4*)c->dn_guide; a.albedo = (float4*)c->dn_albedo;
+        enqueue_first_hit(c, a);
+        launch_denoise_prepare(s, src, c->dn_depth, c->dn_albedo, c->dn_guide, c->dn_ping, W, H, demodulate);
+        const float* in = c->dn_ping;
+        for (uint32_t i = 0; i < dp->iterations; i++) {
+            const bool last = i + 1 == dp->iterations;
+            float* out = last ? c->dn_out : (in == c->dn_ping ? c->dn_pong : c->dn_ping);
+            launch_denoise_atrous(s, in, c->dn_guide, c->dn_albedo, out, W, H, denoise::pass_of(i, dp->sigma_color, dp->sigma_normal, dp->sigma_depth), last && demodulate);
+            in = out;
+        }
+    }
+    c->dn_valid = true;
+    return VPT_OK;
+}
 
 }  // namespace
 
 extern "C" {
 
+void vpt_default_denoise_params(vpt_denoise_params* p) {
+    if (p) *p = vpt_denoise_params{5u, 1.0f, 0.1f, 0.05f, VPT_DENOISE_DEMODULATE, 0u};
+}
+int vpt_denoise(vpt_ctx* c, const vpt_denoise_params* dp, float* rgba_host) {
+    int rc = check_denoise(c, dp, nullptr);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if ((rc = drain(c))) return rc;
+    if ((rc = enqueue_denoise(c, dp))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    HIPCHK(c, hipGetLastError());
+    if (rgba_host) HIPCHK(c, hipMemcpy(rgba_host, c->dn_out, (size_t)c->dn_w * c->dn_h * 16, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+// Behind the frames in flight on the context's stream, like vpt_postprocess_device: the next frame's resolve waits for it (it reads the image).
+int vpt_denoise_device(vpt_ctx* c, const vpt_denoise_params* dp, void* rgba_device, uint64_t* ticket) {
+    int rc = check_denoise(c, dp, rgba_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if ((rc = finish_outstanding(c))) return rc;
+    if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));
+    if ((rc = enqueue_denoise(c, dp))) return rc;
+    if (rgba_device) HIPCHK(c, hipMemcpyAsync(rgba_device, c->dn_out, (size_t)c->dn_w * c->dn_h * 16, hipMemcpyDeviceToDevice, c->main.stream));
+    HIPCHK(c, hipEventRecord(c->ev_post, c->main.stream));
+    c->post_pending = true;
+    const uint64_t t = issue_ticket(c, c->main.stream);
+    if (ticket) *ticket = t;
+    return VPT_OK;
+}
+int vpt_set_post_source(vpt_ctx* c, uint32_t source) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    if (source > VPT_POST_SOURCE_DENOISED) return fail(c, VPT_ERR_INVALID_ARGUMENT, "unknown post source");
+    c->post_source = source;
+    return VPT_OK;
+}
+
 int vpt_postprocess(vpt_ctx* c, const vpt_post_params* pp, uint8_t* out8, float* bloom0) {
     if (!c || !pp || !out8) return VPT_ERR_INVALID_ARGUMENT;
     int rc = post_preconditions(c);
     if (rc) return rc;
+    if ((rc = post_source_ready(c))) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((rc = drain(c))) return rc;
     if ((rc = enqueue_post(c, pp, bloom0 != nullptr))) return rc;
@@ -128,6 +222,7 @@ int vpt_postprocess_device(vpt_ctx* c, const vpt_post_params* pp, void* rgba8_de
     if (!c || !pp) return VPT_ERR_INVALID_ARGUMENT;
     int rc = post_preconditions(c);
     if (rc) return rc;
+    if ((rc = post_source_ready(c))) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((rc = finish_outstanding(c))) return rc;   // the image must be complete: an unfinished batch is finished first
     if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));   // the latest frame was resolved on another lane

@@ -230,6 +230,10 @@ int refresh_material_tables(vpt_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return update_class_present(c);
 }
+void enqueue_first_hit(vpt_ctx* c, const FirstHitArgs& a) {
+    c->spill_dirty = true;   // a traversal kernel runs: vpt_get_stats recounts the spill regions
+    launch_first_hit(c->main.stream, (uint32_t)c->max_blocks, lane_scene(c, c->main), c->P, a);
+}
 
 }  // namespace api
 }  // namespace vpt
@@ -548,8 +552,7 @@ static int first_hit_camera(vpt_ctx* c, uint32_t mode, uint32_t frame, const vpt
     a.ids = (uint4*)dev[0]; a.normal = (float4*)dev[1]; a.albedo = (float4*)dev[2]; a.depth = (float*)dev[3];
     if (pixel) { a.pick = (float4*)stage; a.pixel = *pixel; }
     int rc = VPT_OK;
-    c->spill_dirty = true;   // a traversal kernel runs: vpt_get_stats recounts the spill regions
-    launch_first_hit(c->main.stream, (uint32_t)c->max_blocks, lane_scene(c, c->main), c->P, a);
+    enqueue_first_hit(c, a);
     if (hipStreamSynchronize(c->main.stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = VPT_ERR_DEVICE;
     if (!rc && pixel && hipMemcpy(pick8, stage, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = VPT_ERR_DEVICE;
     for (int k = 0; k < 4; k++) if (!rc && host && dst[k] && hipMemcpy(dst[k], dev[k], bytes[k], hipMemcpyDeviceToHost) != hipSuccess) rc = VPT_ERR_DEVICE;

@@ -1,6 +1,7 @@
 // kernels.hpp — host-callable launch wrappers of the HIP stages (definitions in kernels_*.hip).
 #pragma once
 #include "device_types.hpp"
+#include "denoise.hpp"
 #include "../../include/vpt_lab.h"   // VPT_TRACE_* / VPT_LAB_* constants (the functions exist in the laboratory build only)
 #ifndef VPT_LAB
 #define VPT_LAB 0
@@ -142,5 +143,10 @@ void launch_post_final(hipStream_t s, const float* hdr, const float* mip1, uint3
 constexpr uint32_t kBloomTailMaxTexels = 2048, kBloomTailMaxLevels = 8;   // largest mip the one-launch tail keeps in LDS; levels it can hold
 void launch_tonemap(hipStream_t s, const float* hdr, const float* bloom0, uint8_t* out, uint32_t w, uint32_t h, float exposure,
                     float gamma, bool linear_tap);
+// vpt_denoise (denoise.hpp holds the arithmetic).  prepare: e = the (demodulated) colour of c; `guide` holds the first-hit normal image on entry and the
+// packed (n.xyz, t) on exit.  atrous: one pass in -> out at ps.step (steps 1 and 2 through an LDS tile, larger ones from memory); remodulate: the last pass
+// of a demodulated run, which reads `albedo`.  All images RGBA32F of w x h but depth (one float per pixel).
+void launch_denoise_prepare(hipStream_t s, const float* c, const float* depth, const float* albedo, float* guide, float* e, uint32_t w, uint32_t h, bool demodulate);
+void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, const float* albedo, float* out, uint32_t w, uint32_t h, const denoise::Pass& ps, bool remodulate);
 
 }  // namespace vpt

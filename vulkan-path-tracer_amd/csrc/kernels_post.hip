@@ -532,6 +532,83 @@ __global__ __launch_bounds__(256) void k_post_final(const float4* hdr, const flo
     out[(size_t)y * w + x] = make_uchar4(unorm8(c.x), unorm8(c.y), unorm8(c.z), 255);
 }
 
+// ---- vpt_denoise (api_post.hip enqueue_denoise): the edge-avoiding a-trous filter of denoise.hpp, whose per-pixel functions do all the arithmetic; the
+// kernels only decide where a value is read from, so both instantiations give the bits of the host compile (tests/test_gpu_denoise.py).
+namespace dn = denoise;
+
+// One thread per pixel: e = the (demodulated) colour, and the guide packed in place — `guide` holds k_first_hit's normal on entry and (n.xyz, t) on exit
+// (every thread reads and writes its own pixel only).
+__global__ __launch_bounds__(256) void k_denoise_prepare(const dn::F4* c, const float* depth, const dn::F4* albedo, dn::F4* guide, dn::F4* e, uint32_t n, int demodulate) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float t = depth[i];
+    e[i] = dn::prepare_pixel(c[i], albedo[i], t, demodulate != 0);
+    guide[i] = dn::pack_guide(guide[i], t);
+}
+
+// A 64 x 4 tile per block, a wave per row (the bloom kernels' geometry).  TILED (steps 1 and 2): colour and guide of the tile plus its halo of 2 * step
+// pixels — at most 72 x 12 entries of 32 B = 27 KB — are staged in LDS; otherwise the halo would exceed the tile and the taps come from memory: a wave's
+// 64 lanes read 64 consecutive pixels of a row, one coalesced 1 KB request per image and tap.
+// LDS banks (ds_read_b128 is served in four groups of 16 lanes, bank = dword address mod 64): a wave reads 64 CONSECUTIVE float4 of one tile row for
+// every tap — the tap offset is the same for all lanes — so each group's 16 lanes cover 16 distinct 16-byte slots mod 256 B whatever the row pitch is.
+// No padding is needed and none is there; the staging stores walk the tile linearly and are conflict-free for the same reason.
+constexpr int kDnMaxHalo = 4, kDnTW = kTileW + 2 * kDnMaxHalo, kDnTH = kTileH + 2 * kDnMaxHalo;
+struct DnMemorySrc {
+    const dn::F4* e; const dn::F4* g; int w;
+    __device__ __forceinline__ dn::F4 color(int x, int y) const { return e[(size_t)y * w + x]; }
+    __device__ __forceinline__ dn::F4 guide(int x, int y) const { return g[(size_t)y * w + x]; }
+};
+template <int N>
+struct DnTileSrc {
+    const dn::F4 (&e)[N]; const dn::F4 (&g)[N]; int ox, oy;   // image position of tile entry (0, 0)
+    __device__ __forceinline__ dn::F4 color(int x, int y) const { return e[(y - oy) * kDnTW + (x - ox)]; }
+    __device__ __forceinline__ dn::F4 guide(int x, int y) const { return g[(y - oy) * kDnTW + (x - ox)]; }
+};
+template <bool TILED>
+__global__ __launch_bounds__(256) void k_denoise_atrous(const dn::F4* in, const dn::F4* guide, const dn::F4* albedo, dn::F4* out, int w, int h, dn::Pass ps, int remodulate) {
+    constexpr int N = TILED ? kDnTW * kDnTH : 1;
+    __shared__ dn::F4 s_e[N];
+    __shared__ dn::F4 s_g[N];
+    const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
+    const int halo = 2 * ps.step;   // TILED: <= kDnMaxHalo (the launcher's choice)
+    if (TILED) {
+        const int tw = kTileW + 2 * halo, th = kTileH + 2 * halo;
+        for (int i = threadIdx.x; i < tw * th; i += 256) {
+            const int ty = i / tw, tx = i - ty * tw;
+            const int gx = x0 - halo + tx, gy = y0 - halo + ty;
+            if (gx < 0 || gx >= w || gy < 0 || gy >= h) continue;   // never read: atrous_pixel skips taps outside the image
+            s_e[ty * kDnTW + tx] = in[(size_t)gy * w + gx];
+            s_g[ty * kDnTW + tx] = guide[(size_t)gy * w + gx];
+        }
+        __syncthreads();
+    }
+    const int x = x0 + (int)(threadIdx.x & 63u), y = y0 + (int)(threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    dn::F4 alb = dn::f4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (remodulate) alb = albedo[p];
+    if (TILED) {
+        const DnTileSrc<N> src{s_e, s_g, x0 - halo, y0 - halo};
+        out[p] = dn::atrous_pixel(src, x, y, w, h, ps, src.color(x, y), src.guide(x, y), remodulate != 0, alb);
+    } else {
+        const DnMemorySrc src{in, guide, w};
+        out[p] = dn::atrous_pixel(src, x, y, w, h, ps, in[p], guide[p], remodulate != 0, alb);
+    }
+}
+
+void launch_denoise_prepare(hipStream_t s, const float* c, const float* depth, const float* albedo, float* guide, float* e, uint32_t w, uint32_t h, bool demodulate) {
+    const uint32_t n = w * h;
+    hipLaunchKernelGGL(k_denoise_prepare, dim3(cdiv_(n, 256)), dim3(256), 0, s, reinterpret_cast<const dn::F4*>(c), depth, reinterpret_cast<const dn::F4*>(albedo),
+                       reinterpret_cast<dn::F4*>(guide), reinterpret_cast<dn::F4*>(e), n, demodulate ? 1 : 0);
+}
+void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, const float* albedo, float* out, uint32_t w, uint32_t h, const denoise::Pass& ps, bool remodulate) {
+    const dim3 g(cdiv_(w, kTileW), cdiv_(h, kTileH)), b(256);
+#define VPT_DN(T) hipLaunchKernelGGL(k_denoise_atrous<T>, g, b, 0, s, reinterpret_cast<const dn::F4*>(in), reinterpret_cast<const dn::F4*>(guide), reinterpret_cast<const dn::F4*>(albedo), \
+                                     reinterpret_cast<dn::F4*>(out), (int)w, (int)h, ps, remodulate ? 1 : 0)
+    if (2 * ps.step <= kDnMaxHalo) VPT_DN(true); else VPT_DN(false);
+#undef VPT_DN
+}
+
 void launch_bloom_threshold(hipStream_t s, const float* in, float* out, uint32_t w, uint32_t h, float threshold, float falloff) {
     uint32_t n = w * h;
     hipLaunchKernelGGL(k_bloom_threshold, dim3(cdiv_(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(in), reinterpret_cast<float4*>(out), n, threshold, falloff);

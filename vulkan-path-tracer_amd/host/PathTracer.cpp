@@ -289,5 +289,15 @@ vpt_pick_result PathTracer::Pick(uint32_t x, uint32_t y) {
     Check(vpt_pick(m_Ctx, x, y, &r), "vpt_pick");
     return r;
 }
+std::vector<float> PathTracer::Denoise(const vpt_denoise_params& params, bool download) {
+    if (!m_Ctx) throw std::runtime_error("Denoise before SetScene");
+    std::vector<float> out(download ? (size_t)m_Width * m_Height * 4 : 0);
+    Check(vpt_denoise(m_Ctx, &params, download ? out.data() : nullptr), "vpt_denoise");
+    return out;
+}
+void PathTracer::SetPostSource(uint32_t source) {
+    if (!m_Ctx) throw std::runtime_error("SetPostSource before SetScene");
+    Check(vpt_set_post_source(m_Ctx, source), "vpt_set_post_source");
+}
 
 }  // namespace vpthost

@@ -193,6 +193,13 @@ public:
     [[nodiscard]] Features RenderFeatures(uint32_t mode = VPT_FEATURES_CENTER, uint32_t frame = 0, bool depth = true, bool ids = true, bool normal = true, bool albedo = true);
     [[nodiscard]] vpt_pick_result Pick(uint32_t x, uint32_t y);
 
+    // EXTENSION, no upstream member: the accumulation image through the edge-avoiding a-trous filter over the guide buffers (vpt_denoise; blocking).  The
+    // result stays in the context as a snapshot — SetPostSource(VPT_POST_SOURCE_DENOISED) makes a PostProcessor read it — and is returned (width*height*4
+    // floats) unless download is false.  The accumulated image and the counters are untouched.
+    static vpt_denoise_params DefaultDenoiseParams() { vpt_denoise_params p; vpt_default_denoise_params(&p); return p; }
+    std::vector<float> Denoise(const vpt_denoise_params& params = DefaultDenoiseParams(), bool download = true);
+    void SetPostSource(uint32_t source);   // VPT_POST_SOURCE_RADIANCE (default) / VPT_POST_SOURCE_DENOISED
+
     [[nodiscard]] vpt_ctx* Context() const { return m_Ctx; }  // for PostProcessor
 
 private:

@@ -5,6 +5,8 @@
 //              [--env-hdr sky.hdr] [--png out.png] [--atmosphere] [--sun altitude,azimuth]
 //              [--aov PREFIX]   after the render, the guide buffers of the pixel-centre rays (PathTracer::RenderFeatures, VPT_FEATURES_CENTER) as
 //                               PREFIX_normal.png (n * 0.5 + 0.5) and PREFIX_albedo.png, each clamped to [0, 1], (uint8)(v * 255 + 0.5), alpha 255
+//              [--denoise [ITERATIONS]]   PathTracer::Denoise with the default parameters (ITERATIONS 0..6, default 5) after the render; --ppm / --png then come
+//                                         from the denoised image through the normal post chain (SetPostSource(VPT_POST_SOURCE_DENOISED))
 //              [--env-late]   apply --env-constant / --env-hdr after SetScene instead of before (the Editor's order of calls: the map is swapped on the installed scene)
 //              [--volume minx,miny,minz,maxx,maxy,maxz,density,g,r,g,b]... [--phase hg|draine|hg+draine]
 //              [--density-bricks FILE]   AddDensityDataToVolume on the last --volume, from 8x8x8 bricks: FILE = u32 dim_x, dim_y, dim_z, bricks; u32[3 * bricks]
@@ -45,7 +47,7 @@ int main(int argc, char** argv) {
     std::vector<PathTracer::Volume> volumes; std::vector<std::pair<uint32_t, std::string>> brickFiles; int phase = 0; bool atmosphere = false; float sunAlt = 0.0f, sunAz = 0.0f;
     uint32_t lutSamples = 10000000u, lutTime = 0; UVec3 lutSize{0, 0, 0};
     uint32_t w = 0, h = 0, spp = 16, depth = 8, seed = 1, split = 1, gpus = 1; std::vector<int> devices;
-    bool async = false, rayQueries = true, envLate = false; uint32_t asyncStep = 1;
+    bool async = false, rayQueries = true, envLate = false; uint32_t asyncStep = 1; int denoise = -1;
     bool info = false, selftest = false; float env[3] = {0, 0, 0}; bool haveEnv = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -68,6 +70,11 @@ int main(int argc, char** argv) {
         else if (a == "--ppm") ppm = next();
         else if (a == "--png") png = next();                 // Editor::SaveToFile
         else if (a == "--aov") aov = next();
+        else if (a == "--denoise") {
+            denoise = 5;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise = atoi(argv[++i]);
+            if (denoise > (int)VPT_DENOISE_MAX_ITERATIONS) { fprintf(stderr, "--denoise 0..%u\n", VPT_DENOISE_MAX_ITERATIONS); return 2; }
+        }
         else if (a == "--env-hdr") envHdr = next();          // SetEnvMapFilepath
         else if (a == "--env-late") envLate = true;
         else if (a == "--dump-env") dumpEnv = next();        // with --env-hdr: decoded RGBA32F (no device needed)
@@ -254,6 +261,11 @@ int main(int argc, char** argv) {
         }
         double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const std::vector<float>& img = pt.GetOutputImage();
+        if (denoise >= 0) {   // the post chain reads the denoised image; --radiance stays the accumulation image
+            vpt_denoise_params dp; vpt_default_denoise_params(&dp); dp.iterations = (uint32_t)denoise;
+            (void)pt.Denoise(dp, false);
+            pt.SetPostSource(VPT_POST_SOURCE_DENOISED);
+        }
         post.PostProcess();
         if (!radiance.empty()) write_file(radiance, img.data(), img.size() * 4);
         if (!camera.empty()) { float m[32]; memcpy(m, pt.GetCameraViewInverse().m, 64); memcpy(m + 16, pt.GetCameraProjectionInverse().m, 64); write_file(camera, m, sizeof(m)); }
