@@ -7,6 +7,7 @@
 #include "shade_core.hpp"
 #include "vote.hpp"
 #include "whole_refill.hpp"
+#include "whole_args.hpp"
 
 namespace vpt {
 
@@ -39,6 +40,18 @@ namespace vpt {
 #ifndef VPT_WHOLE_CAM_LDS
 #define VPT_WHOLE_CAM_LDS 1
 #endif
+// A/B switch (tests/tools/build_variant.py -DVPT_WHOLE_ARGS_AT_USE=0: the kernel before it): the loop reads the words of the scene, the parameters
+// and the path buffers again from the kernel's argument segment where it uses them (whole_args.hpp) and holds none of them in registers across the
+// trace loops.  Cornell 1080p, same box, alternating: 9250-9269 Msamples/s against 9100-9109 (profiles/r14_whole_uniforms_ab.md).  Builds on the
+// camera block: one-sample frames are a compile-time fact of WholeParams.
+#ifndef VPT_WHOLE_ARGS_AT_USE
+#define VPT_WHOLE_ARGS_AT_USE 1
+#endif
+#if VPT_WHOLE_ARGS_AT_USE && !VPT_WHOLE_CAM_LDS
+#error "VPT_WHOLE_ARGS_AT_USE needs VPT_WHOLE_CAM_LDS"
+#endif
+#define VPT_KERNARG __attribute__((address_space(4)))   // the constant address space: where a kernel's arguments lie
+template <> struct OneSampleFrames<VPT_KERNARG WholeParams> { static constexpr bool value = true; };
 constexpr int kWalkDone = 0x7fffffff;
 template <class Stack>
 __device__ __forceinline__ int walk_pop(Stack& stack) { return stack.sp ? (int)stack.pop() : kWalkDone; }
@@ -133,15 +146,15 @@ __device__ __forceinline__ bool lds_occluded_vote(const LdsSceneSrc& src, V3 o, 
     return occluded;
 }
 // sky_visible / light_visible of k_whole's non-validating instantiations (the interval and direction rules of traverse.hpp sky_visible)
-template <bool COUNT, class Stack>
-__device__ __forceinline__ bool sky_visible_vote(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const Stack& stack, TravStats& st, bool rq) {
+template <bool COUNT, class Sc, class Stack>
+__device__ __forceinline__ bool sky_visible_vote(const Sc& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const Stack& stack, TravStats& st, bool rq) {
     const float tmin = rq ? 0.0001f : 0.00001f, tmax = rq ? 1000000.0f : 1000.0f;
     if (!rq) d = normalize(d);
     LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * sc.scene_extent};
     return !lds_occluded_vote<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st);
 }
-template <bool COUNT, class Stack>
-__device__ __forceinline__ bool light_visible_vote(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const Stack& stack, TravStats& st) {
+template <bool COUNT, class Sc, class Stack>
+__device__ __forceinline__ bool light_visible_vote(const Sc& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const Stack& stack, TravStats& st) {
     const uint32_t slot = sc.tri_slot_of_gid[gid];
     if (slot == 0xffffffffu) return false;  // the sampled light triangle is a sliver: nothing can hit it
     LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * sc.scene_extent};
@@ -167,7 +180,8 @@ __device__ __forceinline__ bool light_visible_vote(const DeviceScene& sc, const 
 //           survivors keep their lanes for the next trace step.
 // Per path this is k_bounce's arithmetic in k_bounce's order (same shade_core, same connect code), and which lane or wave runs a
 // sample cannot matter: seeds come from (pixel, frame), results go to ACC[slot].  pathLight of a parked hit waits in ACC[slot].
-__device__ __forceinline__ V3 whole_finish(const RenderParams& P, const PathState& ps, uint32_t slot, V3 E, V3 thr_prev, V3 light_prev, const ShadeOut& o) {
+template <class Pm, class Ps>
+__device__ __forceinline__ V3 whole_finish(const Pm& P, const Ps& ps, uint32_t slot, V3 E, V3 thr_prev, V3 light_prev, const ShadeOut& o) {
     V3 contrib = E * thr_prev;
     if (o.cflags & kCF_Clamp) {
         float lum = dot(contrib, v3(0.212671f, 0.715160f, 0.072169f));
@@ -185,8 +199,18 @@ __device__ __forceinline__ V3 whole_finish(const RenderParams& P, const PathStat
 // (Measured and not kept: one-wave blocks, which leave the CU as soon as THEIR paths have ended and so let the next frame's launch in earlier —
 // a 1-frame launch at 1080p 542 us against 509 us, and slower with two or three frames in flight too: profiles/r04_whole_lanes.json.)
 template <bool COUNT, bool STRICT, bool PLAIN>
+#if VPT_WHOLE_ARGS_AT_USE
+__global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeArgs a) {   // (ONE parameter: the argument segment is a WholeArgs)
+    // what runs once, before the loop, reads the arguments as any kernel does
+    DeviceScene sc = a.sc;
+    RenderParams P = a.P;
+    const PathState ps = a.ps;
+    Counters* const ctr = a.ctr;
+    const uint32_t n_slots = a.n_slots, static_rounds = a.static_rounds, chunk_tiles = a.chunk_tiles;
+#else
 __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, RenderParams P, PathState ps, Counters* ctr, uint32_t n_slots, uint32_t dispatch_base,
                                                             uint32_t static_rounds, uint32_t chunk_tiles) {
+#endif
     sc.strict_hits = STRICT ? 1u : 0u;
     if (PLAIN) { sc.all_plain = 1u; sc.env_black = 1u; } else sc.all_plain = 0u;
 #if VPT_WHOLE_CAM_LDS
@@ -194,8 +218,10 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
     // pixel" branch — the other reader of the camera's matrices — drops out and nothing of the camera is live outside the refill step
     P.samples_per_frame = 1u;
 #endif
+#if !VPT_WHOLE_ARGS_AT_USE
     if (P.dispatch_base_dev) dispatch_base = *P.dispatch_base_dev;   // a replayed graph: the batch's first dispatch index lives in device memory
     const bool rq = (P.flags & VPT_FLAG_RAY_QUERIES) != 0u;
+#endif
     extern __shared__ __align__(16) unsigned char smem[];
     const TravStackT<kWholeStackRows> stack = make_stack<kWholeStackRows>(smem, sc.stack_overflow);
     float4* lds_nodes = reinterpret_cast<float4*>(smem + kWholeStackRows * kTraverseBlock * 4);
@@ -211,6 +237,14 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
     }
 #else
     const RenderParams& cam = P;
+#endif
+#if VPT_WHOLE_ARGS_AT_USE
+    // the loop's view of the arguments (whole_args.hpp): `a` again, where it lies in memory
+    const VPT_KERNARG WholeArgs* ka = (const VPT_KERNARG WholeArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    const DeviceScene& usc = sc;
+    const RenderParams& uP = P;
+    const PathState& ups = ps;
 #endif
     stage_scene<true>(sc, lds_nodes, lds_tris);
     constexpr uint32_t kWaves = kTraverseBlock / 64u;
@@ -230,6 +264,9 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
 #if VPT_DIAG_REFILL_LANES
     uint32_t d_passes = 0u, d_lanes = 0u;
 #endif
+#if VPT_DIAG_LIGHT_REFR
+    uint32_t d_steps = 0u, d_refr = 0u, d_refr_dead_only = 0u;
+#endif
     TravStats st, sst; st.nodes = 0; st.tris = 0; sst.nodes = 0; sst.tris = 0;
     uint32_t w_paths = 0u, w_rays = 0u, w_hits0 = 0u, w_alive0 = 0u, w_rays0 = 0u, w_parked = 0u;   // wave totals (uniform); *0: bounce 0 only; parked: hits of later bounces (their pathLight waits in ACC)
     // the lane's path between two steps
@@ -239,12 +276,23 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
     V3 porg = v3s(0.0f), pdir = v3s(0.0f), thr = v3s(1.0f), lightp = v3s(0.0f);
     float pdf = 1.0f;
     for (;;) {
+#if VPT_WHOLE_ARGS_AT_USE
+        // The compiler knows that argument memory does not change and would load every word once, ahead of the loop — the registers this is about.
+        // Behind this statement it no longer knows where `ka` points, so what a round of the loop reads through it is loaded in that round.
+        asm volatile("" : "+s"(ka));
+        const VPT_KERNARG WholeScene<STRICT, PLAIN>& usc = static_cast<const VPT_KERNARG WholeScene<STRICT, PLAIN>&>(ka->sc);
+        const VPT_KERNARG WholeParams& uP = static_cast<const VPT_KERNARG WholeParams&>(ka->P);
+        const VPT_KERNARG PathState& ups = ka->ps;
+#endif
         // ---- shade: a chunk of parked hits (a partial one only when nothing can be added to it any more: no lane holds a ray here)
         if (hit_count >= 64u || (refill::exhausted(cur, fresh) && hit_count > 0u)) {
             const uint32_t cnt = hit_count < 64u ? hit_count : 64u;
             const bool valid = lane_id() < cnt;
             uint32_t nrays = 0u;
             bool first = false, alive = false;
+#if VPT_DIAG_LIGHT_REFR
+            bool l_refr = false, l_dead = false;
+#endif
             if (valid) {
                 const uint32_t q = (hit_head + lane_id()) & 127u;
                 ShadeIn in_;
@@ -260,16 +308,22 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                 in_.inst = r_inst[wave][q];
                 first = in_.depth == 0u;   // (only a camera ray has depth 0: the in-medium walk that leaves the depth alone starts behind a refraction)
                 ShadeOut o;
-                shade_core<false, (int)kShadeTextured>(sc, P, ps, slot, in_, o);   // "all of these hit something"
+                shade_core<false, (int)kShadeTextured>(usc, uP, ups, slot, in_, o);   // "all of these hit something"
+#if VPT_DIAG_LIGHT_REFR
+                l_refr = o.diag_light_refr; l_dead = o.diag_light_refr_dead;
+#endif
                 // pathLight so far: fetched behind the shader (three registers less across its peak), in flight during the shadow queries
-                const V3 light_prev = first ? v3s(0.0f) : xyz(ps.ACC[slot]);
+                const V3 light_prev = first ? v3s(0.0f) : xyz(ups.ACC[slot]);
                 // connect, inline (RayGen.slang:92-102)
                 V3 E = o.emitted;
                 constexpr bool kVote = VPT_WHOLE_VOTE != 0 && !STRICT;   // vote-scheduled searches on the tree in LDS (above); the validating instantiations keep the per-lane loops
                 if (o.want_sky) {
                     bool vis;
-                    if constexpr (kVote) vis = sky_visible_vote<COUNT>(sc, lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq);
-                    else vis = sky_visible<true, COUNT>(sc, lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq);
+#if VPT_WHOLE_ARGS_AT_USE
+                    const bool rq = (uP.flags & VPT_FLAG_RAY_QUERIES) != 0u;
+#endif
+                    if constexpr (kVote) vis = sky_visible_vote<COUNT>(usc, lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq);
+                    else vis = sky_visible<true, COUNT>(usc, lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq);
                     if (vis) E = E + o.csky;
                     nrays++;
                 }
@@ -278,8 +332,8 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
 #if VPT_DIAG_NO_LIGHT_SEARCH   // measuring build only (tests/tools/build_variant.py): what the kernel costs WITHOUT its light-identity searches (wrong images)
                     vis = true;
 #else
-                    if constexpr (kVote) vis = light_visible_vote<COUNT>(sc, lds_nodes, lds_tris, o.light_o, o.light_d, o.light_gid, stack, sst);
-                    else vis = light_visible<true, COUNT>(sc, lds_nodes, lds_tris, o.light_o, o.light_d, o.light_gid, stack, sst);
+                    if constexpr (kVote) vis = light_visible_vote<COUNT>(usc, lds_nodes, lds_tris, o.light_o, o.light_d, o.light_gid, stack, sst);
+                    else vis = light_visible<true, COUNT>(usc, lds_nodes, lds_tris, o.light_o, o.light_d, o.light_gid, stack, sst);
 #endif
                     if (vis) E = E + o.clight;
                     nrays++;
@@ -289,7 +343,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                 // of 1703 SALU instructions (VALU 5491 / 5486), and Cornell 1080p runs at 8926-8945 against 8818-8831 Msamples/s, same box, alternating
                 // (profiles/r12_whole_walk_ab.md; a compiler update may take it back: tests/tools/spill_report.py shows the counts)
                 auto finish = [&]() {
-                    const V3 light = whole_finish(P, ps, slot, E, in_.thr_prev, light_prev, o);
+                    const V3 light = whole_finish(uP, ups, slot, E, in_.thr_prev, light_prev, o);
                     alive = o.alive;
                     if (alive) {
                         has_ray = true;
@@ -299,6 +353,10 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                 finish();
             }
             hit_head += cnt; hit_count -= cnt;
+#if VPT_DIAG_LIGHT_REFR   // steps in which the lobe ran on some lane | in which every lane that ran it has pg == 0 (the steps a sign-only evaluation would spare)
+            d_steps++;
+            if (__ballot(l_refr) != 0ull) { d_refr++; if (__ballot(l_refr && !l_dead) == 0ull) d_refr_dead_only++; }
+#endif
             w_rays += (uint32_t)__popcll(__ballot(nrays >= 1u)) + (uint32_t)__popcll(__ballot(nrays >= 2u));
             w_rays0 += (uint32_t)__popcll(__ballot(first && nrays >= 1u)) + (uint32_t)__popcll(__ballot(first && nrays >= 2u));
             w_alive0 += (uint32_t)__popcll(__ballot(first && alive));
@@ -324,9 +382,12 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
 #endif
                     if (lane_id() < g) {
                         uint32_t gslot, x, y, f;
-                        launch_pixel(P, cur.w_next + lane_id(), dispatch_base, gslot, x, y, f);
-                        const uint32_t seed = pcg_hash(P.base_seed + dispatch_base + f);  // PathTracer.cpp:139 with an explicit seed
-                        Rng r; r.s = y + P.width * x + seed;                              // RayGen.slang:28
+#if VPT_WHOLE_ARGS_AT_USE
+                        const uint32_t dispatch_base = uP.dispatch_base_dev ? *uP.dispatch_base_dev : ka->dispatch_base;   // (a replayed graph: as above)
+#endif
+                        launch_pixel(uP, cur.w_next + lane_id(), dispatch_base, gslot, x, y, f);
+                        const uint32_t seed = pcg_hash(uP.base_seed + dispatch_base + f);  // PathTracer.cpp:139 with an explicit seed
+                        Rng r; r.s = y + uP.width * x + seed;                              // RayGen.slang:28
                         V3 go, gd;
                         camera_ray(cam, r, x, y, go, gd);
                         const uint32_t j = lane_id();
@@ -359,8 +420,8 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
             HitRec hr;
             bool hit = false;
             if (has_ray) {
-                if constexpr (VPT_WHOLE_VOTE != 0 && !STRICT) { LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * sc.scene_extent}; hit = lds_closest_vote<COUNT>(src, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st); }
-                else hit = trace_any<true, COUNT>(sc, lds_nodes, lds_tris, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st);
+                if constexpr (VPT_WHOLE_VOTE != 0 && !STRICT) { LdsSceneSrc src{lds_nodes, lds_tris, false, kSlabFmaReach * usc.scene_extent}; hit = lds_closest_vote<COUNT>(src, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st); }
+                else hit = trace_any<true, COUNT>(usc, lds_nodes, lds_tris, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st);
             }
             const unsigned long long mh = __ballot(has_ray && hit);
             if (has_ray && hit) {
@@ -369,7 +430,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                 r_ra[wave][q] = f4u(porg, rng_s);
                 r_rb[wave][q] = f4u(pdir, depth | (in_medium ? 0x80000000u : 0u));
                 r_rt[wave][q] = f4(thr, pdf);
-                if (depth != 0u) ps.ACC[slot] = f4(lightp, 0.0f);   // pathLight so far (a camera ray's is 0)
+                if (depth != 0u) ups.ACC[slot] = f4(lightp, 0.0f);   // pathLight so far (a camera ray's is 0)
             }
             hit_count += (uint32_t)__popcll(mh);
             w_paths += (uint32_t)__popcll(__ballot(has_ray));
@@ -381,8 +442,8 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
                 in_.vdepth = 0u; in_.cchan = -1; in_.vol_index = -1; in_.vol_t = 0.0f; in_.atm_comp = -1;
                 in_.h = make_float4(-1.0f, 0.0f, 0.0f, 0.0f); in_.inst = 0u;
                 ShadeOut o;
-                shade_core<false, (int)kShadeMiss>(sc, P, ps, slot, in_, o);
-                (void)whole_finish(P, ps, slot, o.emitted, thr, lightp, o);
+                shade_core<false, (int)kShadeMiss>(usc, uP, ups, slot, in_, o);
+                (void)whole_finish(uP, ups, slot, o.emitted, thr, lightp, o);
             }
             has_ray = false;
             // nothing of the lane's path is live across the shade step (hits wait in the ring): say so, or its 17 registers stay allocated through shade_core
@@ -403,6 +464,13 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(DeviceScene sc, Ren
 #if VPT_DIAG_REFILL_LANES   // measuring build only: passes of camera_ray and the lanes that ran them, reported IN PLACE of a counting context's closest-hit visits
     if (lane_id() == 0) { atomicAdd(&ctr->stat_nodes, (unsigned long long)d_passes); atomicAdd(&ctr->stat_tris, (unsigned long long)d_lanes); }
     constexpr bool kReportVisits = false;
+#elif VPT_DIAG_LIGHT_REFR   // measuring build only, IN PLACE of a counting context's visits: shade steps | those whose light evaluation ran the refraction lobe |
+                            // of these, the steps in which only lanes with pg == 0 ran it
+    if (lane_id() == 0) {
+        atomicAdd(&ctr->stat_nodes, (unsigned long long)d_steps); atomicAdd(&ctr->stat_tris, (unsigned long long)d_refr);
+        atomicAdd(&ctr->stat_shadow_nodes, (unsigned long long)d_refr_dead_only);
+    }
+    constexpr bool kReportVisits = false;
 #else
     constexpr bool kReportVisits = COUNT;
 #endif
@@ -420,11 +488,19 @@ void launch_whole(hipStream_t s, uint32_t blocks, bool count, const DeviceScene&
     const size_t lds = traverse_lds_bytes(sc, true, kWholeStackRows);
     const dim3 g(blocks), b(kTraverseBlock);
     // one launch site for the five instantiations (the argument marshalling is host code the library's size bound pays for five times otherwise)
+#if VPT_WHOLE_ARGS_AT_USE
+    void (*k)(WholeArgs);
+#else
     void (*k)(DeviceScene, RenderParams, PathState, Counters*, uint32_t, uint32_t, uint32_t, uint32_t);
+#endif
     if (plain && !count && !sc.strict_hits && sc.env_black) k = k_whole<false, false, true>;
     else if (sc.strict_hits) k = count ? k_whole<true, true, false> : k_whole<false, true, false>;
     else k = count ? k_whole<true, false, false> : k_whole<false, false, false>;
+#if VPT_WHOLE_ARGS_AT_USE
+    hipLaunchKernelGGL(k, g, b, lds, s, WholeArgs{sc, P, ps, ctr, n_slots, dispatch_base, static_rounds, chunk_tiles});
+#else
     hipLaunchKernelGGL(k, g, b, lds, s, sc, P, ps, ctr, n_slots, dispatch_base, static_rounds, chunk_tiles);
+#endif
 }
 int whole_blocks_per_cu(const DeviceScene& sc, bool plain) {
     int nb = 0;

@@ -8,13 +8,21 @@
 #include "atmosphere.hpp"
 #include "wave.hpp"
 
+// measuring build (kernels_whole.hip, tests/tools/whole_light_refr.py): how often the light-sample evaluation of a shade step of the whole-path kernel runs
+// Bsdf::eval's refraction lobe.  2.2 % of the steps on the Cornell box, so skipping it where its result cannot count was not worth a branch
+// (profiles/REJECTED.md, round 14)
+#ifndef VPT_DIAG_LIGHT_REFR
+#define VPT_DIAG_LIGHT_REFR 0
+#endif
+
 namespace vpt {
 
 // ------------------------------------------------------------------ small helpers
 __device__ inline float4 f4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 __device__ inline float4 f4u(V3 v, uint32_t w) { return make_float4(v.x, v.y, v.z, __uint_as_float(w)); }
 __device__ inline V3 xyz(float4 v) { return v3(v.x, v.y, v.z); }
-__device__ inline void pixel_of_slot(const RenderParams& P, uint32_t slot, uint32_t& x, uint32_t& y, uint32_t& f) {
+template <class Pm>
+__device__ inline void pixel_of_slot(const Pm& P, uint32_t slot, uint32_t& x, uint32_t& y, uint32_t& f) {
     f = slot / P.shard_pixels;
     uint32_t sp = slot - f * P.shard_pixels;
     uint32_t ys = sp / P.width;
@@ -26,7 +34,8 @@ __device__ inline void pixel_of_slot(const RenderParams& P, uint32_t slot, uint3
 // and the launch index IS the slot.  With S > 1 dispatch k of the batch covers the pixels of chunk
 // c = (dispatch_base + k) % S^2 only: LaunchID * S + (c % S, c / S)  (RayGen.slang:16-25); its launch grid is
 // exactly the in-bounds part, and P.launch_off[k] is where it starts in the batch-wide launch index space.
-__device__ inline void launch_pixel(const RenderParams& P, uint32_t li, uint32_t dispatch_base, uint32_t& slot, uint32_t& x, uint32_t& y, uint32_t& f) {
+template <class Pm>
+__device__ inline void launch_pixel(const Pm& P, uint32_t li, uint32_t dispatch_base, uint32_t& slot, uint32_t& x, uint32_t& y, uint32_t& f) {
     if (P.split == 1u) { slot = li; pixel_of_slot(P, li, x, y, f); return; }
     uint32_t k = 0;
     while (P.launch_off[k + 1] <= li) k++;
@@ -73,6 +82,9 @@ struct ShadeOut {
     int sky_kind;       // 0 surface, 1 box scatter event, 2 atmosphere scatter event (the three expressions differ in association)
     bool sky_add;       // false: trace and track (the draws count) but add nothing (ozone collision)
     int cchan;          // payload.ColorChannel after this bounce
+#if VPT_DIAG_LIGHT_REFR
+    bool diag_light_refr, diag_light_refr_dead;   // the light-sample evaluation ran the refraction lobe | and the material's pg is 0
+#endif
 };
 
 // The miss / closest-hit shader and the visibility-independent tail of the bounce loop for ONE path, on
@@ -80,10 +92,23 @@ struct ShadeOut {
 // CLS: what the caller knows about every path it hands over (device_types.hpp kShade*): kShadeMiss — none hit anything;
 // kShadePlain — all hit a material whose textures are all 1x1 (the texture code drops out; results are those of the general
 // code, which would take the same branches); any other hit class — all hit something; kShadeAny — nothing.
-template <bool VOL, int CLS = kShadeAny>
-__device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderParams& P, const PathState& ps, uint32_t slot,
+// Sc, Pm, Ps: DeviceScene, RenderParams and PathState, or the whole-path kernel's views of them in its argument segment (whole_args.hpp: the same
+// fields, in another address space, with what that kernel knows at compile time as constant members).  The media code calls on into volume.hpp and
+// atmosphere.hpp, which take the structs themselves: it is handed them through media_arg (VOL kernels only).
+// OneSampleFrames: samples_per_frame is 1 at compile time and the branch to the pixel's next sample — which hands P to camera_ray, which the
+// whole-path kernel's view of its arguments cannot be — is not compiled
+template <class Pm> struct OneSampleFrames { static constexpr bool value = false; };
+template <bool VOL, class M, class T>
+__device__ __forceinline__ const M* media_arg(const T& t) { if constexpr (VOL) return &t; else return nullptr; }
+template <bool VOL, int CLS = kShadeAny, class Sc, class Pm, class Ps>
+__device__ __forceinline__ void shade_core(const Sc& sc, const Pm& P, const Ps& ps, uint32_t slot,
                                            const ShadeIn& in_, ShadeOut& out) {
+    const DeviceScene* const msc = media_arg<VOL, DeviceScene>(sc);   // (null and never read unless VOL)
+    const RenderParams* const mP = media_arg<VOL, RenderParams>(P);
     bool alive = false, want_sky = false, want_light = false, light_miss_ok = false;
+#if VPT_DIAG_LIGHT_REFR
+    out.diag_light_refr = false; out.diag_light_refr_dead = false;
+#endif
     // Without USE_RAY_QUERIES (RTCommon.slang:64-84) the light-identity compare of an emissive-mesh NEE sample reads a payload word nothing has
     // written: pinned as "never equal" (oracle.cpp does_ray_intersect), i.e. the sample is drawn (its random numbers count) and never visible.
     // Its shadow ray is therefore not even queued: no result of it could matter.
@@ -93,7 +118,7 @@ __device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderPa
         out.light_add = true; out.light_kind = 0; out.light_tdepth = 0.0f; out.light_w = 1.0f; out.light_mis = 1.0f; out.light_f = v3s(0.0f); out.light_rgb = v3s(0.0f);
     }
     // media whose transmittance is TRACKED (random draws) rather than evaluated: every unobscured NEE sample is tracked, used or not
-    const bool tracked = VOL && (sc.atm_on || sc.hetero);
+    const bool tracked = VOL && (msc->atm_on || msc->hetero);
     uint32_t vdepth = VOL ? in_.vdepth : 0u;
     const float4 h = in_.h;
     Rng rng; rng.s = in_.rng;
@@ -110,21 +135,21 @@ __device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderPa
     uint32_t new_depth = depth;
     if (VOL && in_.vol_index >= 0) {
         // ---- EvaluateVolumeScatteringEvent, RayGen.slang:265-380 (no atmosphere, no temperature grid)
-        const vpt_volume& v = sc.volumes[in_.vol_index];
+        const vpt_volume& v = msc->volumes[in_.vol_index];
         new_o = porg + pdir * in_.vol_t;
-        emitted = ld3(v.emissive_color) + temperature_emission(sc, v, rng, new_o);  // RayGen.slang:268
+        emitted = ld3(v.emissive_color) + temperature_emission(*msc, v, rng, new_o);  // RayGen.slang:268
         V3 to_sky = v3s(0.0f); V4 sky = v4(0.0f, 0.0f, 0.0f, 0.0f);
         if (P.flags & VPT_FLAG_SKY_MIS) {
-            sample_sky(sc, P, rng, to_sky, sky);
+            sample_sky(*msc, *mP, rng, to_sky, sky);
             sky.x *= P.sky_intensity; sky.y *= P.sky_intensity; sky.z *= P.sky_intensity;
         }
         V3 to_light = v3s(0.0f); V4 lc = v4(0.0f, 0.0f, 0.0f, 0.0f);
         if (P.flags & VPT_FLAG_MESH_MIS) sample_emissive(sc, rng, new_o, to_light, lc, light_gid);
-        const V3 nd = volume_scatter_direction(sc.phase, v, pdir, rng, vdepth);
-        const float ph = volume_phase(sc.phase, v, pdir, nd, vdepth);
+        const V3 nd = volume_scatter_direction(msc->phase, v, pdir, rng, vdepth);
+        const float ph = volume_phase(msc->phase, v, pdir, nd, vdepth);
         // NEE: the shadow rays start AT the scatter point (no offset); the sky term is assembled after the visibility test
         if ((P.flags & VPT_FLAG_SKY_MIS) && sky.w > 0.0f) {
-            float ps_ = volume_phase(sc.phase, v, pdir, to_sky, vdepth);
+            float ps_ = volume_phase(msc->phase, v, pdir, to_sky, vdepth);
             if (ps_ > 0.0f || tracked) {  // tracked transmittance draws whenever the sample is unobscured (:316-343)
                 out.sky_f = ld3(v.color) * ps_; out.sky_tdepth = (float)vdepth;
                 out.sky_rgb = v3(sky.x, sky.y, sky.z); out.sky_w = sky.w; out.sky_mis = power_heuristics(sky.w, ps_); out.sky_kind = 1;
@@ -133,7 +158,7 @@ __device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderPa
             }
         }
         if ((P.flags & VPT_FLAG_MESH_MIS) && lc.w > 0.0f && light_rays) {
-            float pl = volume_phase(sc.phase, v, pdir, to_light, vdepth);
+            float pl = volume_phase(msc->phase, v, pdir, to_light, vdepth);
             if (pl > 0.0f || tracked) {
                 out.light_f = ld3(v.color) * pl; out.light_tdepth = (float)(vdepth + 1u);  // :353 passes VolumeDepth + 1
                 out.light_rgb = v3(lc.x, lc.y, lc.z); out.light_w = lc.w; out.light_mis = power_heuristics(lc.w, pl); out.light_kind = 1;
@@ -156,7 +181,7 @@ __device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderPa
         else nd = pdir;
         if (P.flags & VPT_FLAG_SKY_MIS) {
             V3 to_sky; V4 cp;
-            sample_sky(sc, P, rng, to_sky, cp);
+            sample_sky(*msc, *mP, rng, to_sky, cp);
             cp.x *= P.sky_intensity; cp.y *= P.sky_intensity; cp.z *= P.sky_intensity;
             // the sun term needs the shadow ray first: its transmittance is tracked only when the ray is clear (:398-409)
             out.sky_rgb = v3(cp.x, cp.y, cp.z); out.sky_w = cp.w; out.sky_mis = 1.0f; out.sky_kind = 2;
@@ -183,7 +208,7 @@ __device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderPa
         }
         new_d = nd;
         new_depth = depth + 1u;
-    } else if (VOL && sc.atm_on && h.x < 0.0f) {
+    } else if (VOL && msc->atm_on && h.x < 0.0f) {
         new_depth = kMaxDepthMarker;  // Miss.slang:11-14: with an atmosphere the sky is in-scattered sunlight only
     } else if (CLS == kShadeMiss || (CLS == kShadeAny && h.x < 0.0f)) {
         // ---- Miss.slang:8-77
@@ -237,7 +262,7 @@ __device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderPa
             // sky NEE sample (:125-148) — 3 draws
             V3 to_sky = v3s(0.0f); V4 sky = v4(0.0f, 0.0f, 0.0f, 0.0f);
             if (P.flags & VPT_FLAG_SKY_MIS) {
-                if (VOL) sample_sky(sc, P, rng, to_sky, sky); else sample_env(sc, P, rng, to_sky, sky);
+                if (VOL) sample_sky(*msc, *mP, rng, to_sky, sky); else sample_env(sc, P, rng, to_sky, sky);
                 sky.x *= P.sky_intensity; sky.y *= P.sky_intensity; sky.z *= P.sky_intensity;  // applied twice upstream (quirk 1)
             }
             // emissive-mesh NEE sample (:155-184) — 4 draws unless this is an emitter
@@ -321,6 +346,18 @@ __device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderPa
                 }
             }
             if ((P.flags & VPT_FLAG_MESH_MIS) && !is_light && lc.w > 0.0f && light_rays) {
+#if VPT_DIAG_LIGHT_REFR   // measuring build only: did this lane's light-sample evaluation run the refraction lobe (Bsdf::eval's last block)?
+                {
+                    const V3 Ld = s.world_to_tangent(to_light);
+                    if (Ld.z < 0.0f) {
+                        V3 Hd = normalize(V * bs.eta + Ld);
+                        if (Hd.z < 0.0f) Hd = -Hd;
+                        const float vh = dot(V, Hd), lh = dot(Ld, Hd);
+                        out.diag_light_refr = (vh > 0.0f && lh < 0.0f) || (vh < 0.0f && lh > 0.0f);
+                        out.diag_light_refr_dead = out.diag_light_refr && bs.pg == 0.0f;
+                    }
+                }
+#endif
                 Eval e = bs.eval(V, s.world_to_tangent(to_light), ec_r, ec_g, gv);
                 if (e.pdf > 0.0f) {
                     if (VOL) {
@@ -355,7 +392,7 @@ __device__ __forceinline__ void shade_core(const DeviceScene& sc, const RenderPa
     uint32_t cflags = (want_sky ? kCF_Sky : 0u) | (want_light ? kCF_Light : 0u) | (new_depth != 1u ? kCF_Clamp : 0u);
     if (terminated) {
         cflags |= kCF_Finalize;
-        if (P.samples_per_frame > 1) {
+        if constexpr (!OneSampleFrames<Pm>::value) if (P.samples_per_frame > 1) {
             uint32_t sample = ps.sidx[slot] + 1u;
             if (sample < P.samples_per_frame) {  // next sample of the pixel continues the RNG stream (RayGen.slang:33)
                 uint32_t x, y, f;

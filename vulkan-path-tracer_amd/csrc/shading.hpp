@@ -71,7 +71,8 @@ __device__ inline V4 tex_finish(const TexTaps& k) {
     V4 b = lerp4(tex_decode(k.r01, k.c), tex_decode(k.r11, k.c), k.fx);
     return lerp4(a, b, k.fy);
 }
-__device__ inline V4 env_sample(const DeviceScene& sc, float u, float v) {
+template <class Sc>
+__device__ inline V4 env_sample(const Sc& sc, float u, float v) {
     int w = (int)sc.env_w, h = (int)sc.env_h;
     const float4* e = reinterpret_cast<const float4*>(sc.env);
     int x0, x1, y0, y1; float fx, fy;
@@ -130,7 +131,8 @@ __device__ inline V3 triangle_ng(const DeviceScene& sc, const InstanceDesc& in, 
 
 // SurfaceFrame in two halves around the texel fetches: surface_geom reads the triangle and interpolates (the uv is known after it),
 // surface_frame applies the normal map and the reference's two normal corrections.
-__device__ inline void surface_geom(const DeviceScene& sc, SurfaceFrame& s, const InstanceDesc& in, uint32_t gid, float hu, float hv, V3 raydir, bool geo_only) {
+template <class Sc>
+__device__ inline void surface_geom(const Sc& sc, SurfaceFrame& s, const InstanceDesc& in, uint32_t gid, float hu, float hv, V3 raydir, bool geo_only) {
     // the triangle's three vertices and its geometric normal from its de-indexed record (k_precompute_tri_shade): one 128-byte line
     // (the hit record carries the GLOBAL triangle id, so this fetch does not wait for the instance record)
     const float4* q = sc.tri_shade + (size_t)gid * 8;
@@ -356,7 +358,8 @@ __device__ inline void material_finish(const vpt_material& m, const MatTaps& k, 
         if (flags & VPT_FLAG_FURNACE) r.emissive[0] = r.emissive[1] = r.emissive[2] = 0.0f;
     }
 }
-__device__ inline void bsdf_init(Bsdf& b, const DeviceScene& sc, const vpt_material& m, const MatResolved& pre, const MatTaps& taps, bool inside,
+template <class Sc>
+__device__ inline void bsdf_init(Bsdf& b, const Sc& sc, const vpt_material& m, const MatResolved& pre, const MatTaps& taps, bool inside,
                                  uint32_t flags, V3& medium_color, float& medium_density, float& medium_aniso, float& aniso_rotation) {
     MatResolved r = pre;
     material_finish(m, taps, flags, r);
@@ -421,7 +424,8 @@ __device__ inline V3 sample_hg(Rng& r, V3 dir, float G) {  // :168-193
 // ImportanceSampleEnvMap, :286-346 (3 draws)
 // `need_direction`: the caller uses to_light even when the sample carries no light (media whose transmittance is tracked
 // along the shadow ray), so the all-black shortcut does not apply
-__device__ inline void sample_env(const DeviceScene& sc, const RenderParams& P, Rng& r, V3& to_light, V4& out, bool need_direction = false) {
+template <class Sc, class Pm>
+__device__ inline void sample_env(const Sc& sc, const Pm& P, Rng& r, V3& to_light, V4& out, bool need_direction = false) {
     if (sc.env_black && !need_direction) {
         // every texel and every pdf is exactly 0: the bilinear result is +0 for any direction, so only the
         // three draws (Sampler.slang:289) have an effect
@@ -475,7 +479,8 @@ __device__ inline void emissive_tri_compute(const DeviceScene& sc, const Emissiv
 // SampleEmissiveTriangle, :348-422 (1+1+2 draws; none if there is no emissive mesh)
 // (results are built in locals and assigned once at the end: with stores to the callers' cpdf on two paths the optimiser merges them into one store through a
 // selected ADDRESS, which keeps cpdf in scratch memory)
-__device__ inline void sample_emissive(const DeviceScene& sc, Rng& r, V3 pos, V3& to_light_out, V4& cpdf_out, uint32_t& gid) {
+template <class Sc>
+__device__ inline void sample_emissive(const Sc& sc, Rng& r, V3 pos, V3& to_light_out, V4& cpdf_out, uint32_t& gid) {
     gid = 0xffffffffu;
     uint32_t n = sc.emissive_count;
     V3 to_light = v3s(0.0f); V4 cpdf = v4(0.0f, 0.0f, 0.0f, 0.0f);

@@ -426,31 +426,28 @@ __device__ inline void stage_scene(const DeviceScene& sc, float4* lds_nodes, flo
         __syncthreads();
     }
 }
-template <bool LDS_SCENE, bool COUNT, class Stack>
-__device__ inline bool trace_any(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, float tmin,
+template <bool LDS_SCENE, bool COUNT, class Sc, class Stack>
+__device__ inline bool trace_any(const Sc& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, float tmin,
                                  float tmax, const Stack& stack, HitRec& h, TravStats& st) {
-    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
-    GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
-    return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st);
+    if constexpr (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
+    else { GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
 }
 
 // Sky visibility / light identity as exact any-hit queries (above).
 // rq: USE_RAY_QUERIES (RTCommon.slang:52-63: the direction as it is, TMin 1e-4, TMax 1e6); otherwise RTCommon.slang:64-84: normalised, TMin 1e-5, TMax 1000.
-template <bool LDS_SCENE, bool COUNT, class Stack>
-__device__ inline bool sky_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const Stack& stack, TravStats& st, bool rq) {
+template <bool LDS_SCENE, bool COUNT, class Sc, class Stack>
+__device__ inline bool sky_visible(const Sc& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const Stack& stack, TravStats& st, bool rq) {
     const float tmin = rq ? 0.0001f : 0.00001f, tmax = rq ? 1000000.0f : 1000.0f;
     if (!rq) d = normalize(d);
-    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
-    GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
-    return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st);
+    if constexpr (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
+    else { GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
 }
-template <bool LDS_SCENE, bool COUNT, class Stack>
-__device__ inline bool light_visible(const DeviceScene& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const Stack& stack, TravStats& st) {
+template <bool LDS_SCENE, bool COUNT, class Sc, class Stack>
+__device__ inline bool light_visible(const Sc& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const Stack& stack, TravStats& st) {
     uint32_t slot = sc.tri_slot_of_gid[gid];
     if (slot == 0xffffffffu) return false;  // the sampled light triangle is a sliver: nothing can hit it
-    if (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
-    GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u};
-    return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st);
+    if constexpr (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
+    else { GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
 }
 
 }  // namespace vpt

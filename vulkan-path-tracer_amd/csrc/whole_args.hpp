@@ -1,0 +1,41 @@
+// whole_args.hpp — the arguments of the whole-path kernel (kernels_whole.hip k_whole) as ONE struct, and the types through which its loop reads them.
+// The kernel takes a DeviceScene, a RenderParams and a PathState: several dozen pointers and scalars, most of them read at one place of the shade
+// step.  Held in registers they stay live across both trace loops, and what does not fit the 106 scalar registers lives in VGPR lanes (232
+// v_readlane / v_writelane in the PLAIN instantiation).  Instead the loop reads each word again where it is used, from the kernel's own argument
+// segment: a scalar load that hits the scalar cache, a result in scalar registers, no LDS.  WholeArgs is that segment — a kernel whose only
+// parameter is this struct has it at offset 0 — and the loop reads it through a pointer to the constant address space, from which the compiler
+// also knows that the pointers it loads point to global memory.
+// WholeScene / WholeParams are DeviceScene / RenderParams with what k_whole knows at compile time as constant members that hide the fields
+// (STRICT, PLAIN and its black environment, one-sample frames), so the shared shader code (shade_core.hpp, shading.hpp, traverse.hpp), which
+// reads `sc.all_plain`, `P.samples_per_frame`, ... through a template parameter as camera_ray<Cam> does, folds them as it did when the kernel
+// wrote them into its own copy.  They add no word: a DeviceScene in memory is read as a WholeScene.
+// Compiled for the device and — by tests/tools/whole_uniforms_driver.cpp — for the host (tests/test_whole_uniforms_cpu.py).
+#pragma once
+#include "device_types.hpp"
+
+namespace vpt {
+
+struct WholeArgs {
+    DeviceScene sc;
+    RenderParams P;
+    PathState ps;
+    Counters* ctr;
+    uint32_t n_slots, dispatch_base;
+    uint32_t static_rounds, chunk_tiles;
+};
+
+template <bool STRICT, bool PLAIN>
+struct WholeScene : DeviceScene {
+    static constexpr uint32_t strict_hits = STRICT ? 1u : 0u, all_plain = 0u;
+};
+template <bool STRICT>
+struct WholeScene<STRICT, true> : DeviceScene {   // the PLAIN instantiation runs on scenes with an all-zero env map only (launch_whole)
+    static constexpr uint32_t strict_hits = STRICT ? 1u : 0u, all_plain = 1u, env_black = 1u;
+};
+struct WholeParams : RenderParams {
+    static constexpr uint32_t samples_per_frame = 1u;   // the planner gives k_whole one-sample frames only (path_plan.hpp whole_possible)
+};
+static_assert(sizeof(WholeScene<false, false>) == sizeof(DeviceScene) && sizeof(WholeScene<true, true>) == sizeof(DeviceScene) && sizeof(WholeParams) == sizeof(RenderParams),
+              "the views add no word");
+
+}  // namespace vpt
