@@ -223,15 +223,10 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_bounce(DeviceScene sc, Re
                 }
                 const int fin_chan = VOL ? o.cchan : -1;  // the channel this sample is accumulated in (RayGen.slang:118-128)
                 if (VOL) shade_tail_media(P, ps, slot, in_.thr_prev, aborted, o);
-                V3 contrib = E * in_.thr_prev;
-                if (o.cflags & kCF_Clamp) {
-                    float lum = dot(contrib, v3(0.212671f, 0.715160f, 0.072169f));
-                    contrib = contrib * (P.max_luminance / max_(lum, P.max_luminance));
-                }
-                light = light_prev + contrib;
+                light = light_prev + path_contribution(E, in_.thr_prev, o.cflags, P.max_luminance);
                 if (VOL && aborted) light = light_prev;  // the loop was left before anything was added
                 if (o.terminated) {  // end of a sample: NaN/Inf guard, frame sum (RayGen.slang:116-128)
-                    bool ok = !isinf_(light.x) && !isinf_(light.y) && !isinf_(light.z) && !isnan_(light.x) && !isnan_(light.y) && !isnan_(light.z);
+                    const bool ok = finite3(light);
                     if (VOL && fin_chan != -1) light = v3(fin_chan == 0 ? light.x : 0.0f, fin_chan == 1 ? light.y : 0.0f, fin_chan == 2 ? light.z : 0.0f);
                     if (FIRST || P.samples_per_frame == 1) {  // first (or only) finalisation of the slot: 0 + pathLight
                         ps.ACC[slot] = ok ? f4(v3s(0.0f) + light, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);

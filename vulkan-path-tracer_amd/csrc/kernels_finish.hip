@@ -194,14 +194,10 @@ __global__ __launch_bounds__(kTraverseBlock, VPT_FINISH_MIN_BLOCKS) void k_finis
             V3 E = o.emitted;
             if (q_sky && vis_sky) E = E + o.csky;
             if (q_light && vis_light) E = E + o.clight;
-            V3 contrib = E * in_.thr_prev;
-            if (o.cflags & kCF_Clamp) {
-                float lum = dot(contrib, v3(0.212671f, 0.715160f, 0.072169f));
-                contrib = contrib * (P.max_luminance / max_(lum, P.max_luminance));
-            }
+            const V3 contrib = path_contribution(E, in_.thr_prev, o.cflags, P.max_luminance);
             V3 light = lightp + contrib;
             if (o.terminated) {  // end of a sample: NaN/Inf guard, frame sum (RayGen.slang:116-128)
-                const bool ok = !isinf_(light.x) && !isinf_(light.y) && !isinf_(light.z) && !isnan_(light.x) && !isnan_(light.y) && !isnan_(light.z);
+                const bool ok = finite3(light);
                 if (P.samples_per_frame == 1) ps.ACC[slot] = ok ? f4(v3s(0.0f) + light, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 else if (ok) { float4 acc = ps.ACC[slot]; ps.ACC[slot] = f4(xyz(acc) + light, 0.0f); }
                 light = v3s(0.0f);   // the pixel's next sample of the frame starts from pathLight = 0

@@ -277,14 +277,10 @@ __global__ __launch_bounds__(kTraverseBlock, 8) void k_connect(DeviceScene sc, R
                 V3 E = xyz(ps.CE[sl]);
                 if ((fl & kCF_Sky) && t_vis[2u * j]) E = E + xyz(ps.CS[sl]);
                 if ((fl & kCF_Light) && t_vis[2u * j + 1u]) E = E + xyz(ps.CL[sl]);
-                V3 contrib = E * xyz(Tprev[sl]);  // RayGen.slang:92
-                if (fl & kCF_Clamp) {
-                    float lum = dot(contrib, v3(0.212671f, 0.715160f, 0.072169f));
-                    contrib = contrib * (P.max_luminance / max_(lum, P.max_luminance));
-                }
+                const V3 contrib = path_contribution(E, xyz(Tprev[sl]), fl, P.max_luminance);
                 V3 light = xyz(ps.L[sl]) + contrib;
                 if (fl & kCF_Finalize) {
-                    bool ok = !isinf_(light.x) && !isinf_(light.y) && !isinf_(light.z) && !isnan_(light.x) && !isnan_(light.y) && !isnan_(light.z);
+                    const bool ok = finite3(light);
                     if (P.samples_per_frame == 1) {  // the only finalisation of this slot: 0 + pathLight
                         ps.ACC[sl] = ok ? f4(v3s(0.0f) + light, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                     } else if (ok) {

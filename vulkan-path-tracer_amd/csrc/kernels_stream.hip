@@ -292,14 +292,10 @@ __global__ __launch_bounds__(256) void k_join(RenderParams P, PathState ps, Stre
             V3 E = xyz(pe[k]);
             if (vs[k]) E = E + xyz(s4[k]);
             if (vl[k]) E = E + xyz(l4[k]);
-            V3 contrib = E * xyz(pt[k]);  // RayGen.slang:92
-            if (fl[k] & kCF_Clamp) {
-                float lum = dot(contrib, v3(0.212671f, 0.715160f, 0.072169f));
-                contrib = contrib * (P.max_luminance / max_(lum, P.max_luminance));
-            }
+            const V3 contrib = path_contribution(E, xyz(pt[k]), fl[k], P.max_luminance);
             V3 light = xyz(lp[k]) + contrib;
             if (fl[k] & kCF_Finalize) {  // end of a sample: NaN/Inf guard, frame sum (RayGen.slang:116-128)
-                bool ok = !isinf_(light.x) && !isinf_(light.y) && !isinf_(light.z) && !isnan_(light.x) && !isnan_(light.y) && !isnan_(light.z);
+                const bool ok = finite3(light);
                 if (P.samples_per_frame == 1) {  // the only finalisation of this slot: 0 + pathLight
                     ps.ACC[sl[k]] = ok ? f4(v3s(0.0f) + light, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 } else if (ok) {

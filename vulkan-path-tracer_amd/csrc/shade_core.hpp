@@ -8,19 +8,23 @@
 #include "atmosphere.hpp"
 #include "wave.hpp"
 
-// measuring build (kernels_whole.hip, tests/tools/whole_light_refr.py): how often the light-sample evaluation of a shade step of the whole-path kernel runs
-// Bsdf::eval's refraction lobe.  2.2 % of the steps on the Cornell box, so skipping it where its result cannot count was not worth a branch
-// (profiles/REJECTED.md, round 14)
-#ifndef VPT_DIAG_LIGHT_REFR
-#define VPT_DIAG_LIGHT_REFR 0
-#endif
-
 namespace vpt {
 
 // ------------------------------------------------------------------ small helpers
 __device__ inline float4 f4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 __device__ inline float4 f4u(V3 v, uint32_t w) { return make_float4(v.x, v.y, v.z, __uint_as_float(w)); }
 __device__ inline V3 xyz(float4 v) { return v3(v.x, v.y, v.z); }
+// The end of a bounce, part of the bit-exact parity contract and written once: what the bounce adds to pathLight — E * throughput, under kCF_Clamp
+// scaled down to max_luminance (RayGen.slang:92-102) — and the NaN/Inf guard in front of the frame sum (RayGen.slang:116-128).
+__device__ __forceinline__ V3 path_contribution(V3 E, V3 thr_prev, uint32_t cflags, float max_luminance) {
+    V3 contrib = E * thr_prev;
+    if (cflags & kCF_Clamp) {
+        float lum = dot(contrib, v3(0.212671f, 0.715160f, 0.072169f));
+        contrib = contrib * (max_luminance / max_(lum, max_luminance));
+    }
+    return contrib;
+}
+__device__ __forceinline__ bool finite3(V3 v) { return !isinf_(v.x) && !isinf_(v.y) && !isinf_(v.z) && !isnan_(v.x) && !isnan_(v.y) && !isnan_(v.z); }
 template <class Pm>
 __device__ inline void pixel_of_slot(const Pm& P, uint32_t slot, uint32_t& x, uint32_t& y, uint32_t& f) {
     f = slot / P.shard_pixels;
@@ -82,9 +86,6 @@ struct ShadeOut {
     int sky_kind;       // 0 surface, 1 box scatter event, 2 atmosphere scatter event (the three expressions differ in association)
     bool sky_add;       // false: trace and track (the draws count) but add nothing (ozone collision)
     int cchan;          // payload.ColorChannel after this bounce
-#if VPT_DIAG_LIGHT_REFR
-    bool diag_light_refr, diag_light_refr_dead;   // the light-sample evaluation ran the refraction lobe | and the material's pg is 0
-#endif
 };
 
 // The miss / closest-hit shader and the visibility-independent tail of the bounce loop for ONE path, on
@@ -106,9 +107,6 @@ __device__ __forceinline__ void shade_core(const Sc& sc, const Pm& P, const Ps& 
     const DeviceScene* const msc = media_arg<VOL, DeviceScene>(sc);   // (null and never read unless VOL)
     const RenderParams* const mP = media_arg<VOL, RenderParams>(P);
     bool alive = false, want_sky = false, want_light = false, light_miss_ok = false;
-#if VPT_DIAG_LIGHT_REFR
-    out.diag_light_refr = false; out.diag_light_refr_dead = false;
-#endif
     // Without USE_RAY_QUERIES (RTCommon.slang:64-84) the light-identity compare of an emissive-mesh NEE sample reads a payload word nothing has
     // written: pinned as "never equal" (oracle.cpp does_ray_intersect), i.e. the sample is drawn (its random numbers count) and never visible.
     // Its shadow ray is therefore not even queued: no result of it could matter.
@@ -346,18 +344,6 @@ __device__ __forceinline__ void shade_core(const Sc& sc, const Pm& P, const Ps& 
                 }
             }
             if ((P.flags & VPT_FLAG_MESH_MIS) && !is_light && lc.w > 0.0f && light_rays) {
-#if VPT_DIAG_LIGHT_REFR   // measuring build only: did this lane's light-sample evaluation run the refraction lobe (Bsdf::eval's last block)?
-                {
-                    const V3 Ld = s.world_to_tangent(to_light);
-                    if (Ld.z < 0.0f) {
-                        V3 Hd = normalize(V * bs.eta + Ld);
-                        if (Hd.z < 0.0f) Hd = -Hd;
-                        const float vh = dot(V, Hd), lh = dot(Ld, Hd);
-                        out.diag_light_refr = (vh > 0.0f && lh < 0.0f) || (vh < 0.0f && lh > 0.0f);
-                        out.diag_light_refr_dead = out.diag_light_refr && bs.pg == 0.0f;
-                    }
-                }
-#endif
                 Eval e = bs.eval(V, s.world_to_tangent(to_light), ec_r, ec_g, gv);
                 if (e.pdf > 0.0f) {
                     if (VOL) {

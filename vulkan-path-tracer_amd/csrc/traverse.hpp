@@ -81,14 +81,9 @@ __device__ inline void unpack_node(const uint4& w0, const uint4& w1, const uint4
     n.c0 = (int)w3.x; n.c1 = (int)w3.y; n.c2 = (int)w3.z; n.c3 = (int)w3.w;
 }
 
-// A/B switch of the LDS-tree node step (tests/tools/build_variant.py -DVPT_LDS_PLANES_BY_SIGN=0: the kernels before it, instruction for instruction):
-// load_node reads each axis' near and far plane vectors by the sign of the ray's direction and the box test sorts nothing (slab.hpp box_entry_dir).
-// Cornell 1080p, same box, alternating: 9110-9125 Msamples/s against 8932-8935 (profiles/r13_lds_node_step_ab.md).
-#ifndef VPT_LDS_PLANES_BY_SIGN
-#define VPT_LDS_PLANES_BY_SIGN 1
-#endif
-// near* / far*: the planes of the four children this ray meets first / last on each axis (load_node picks them by the sign of inv).
-// With -DVPT_LDS_PLANES_BY_SIGN=0 they are the min and the max planes as stored, and the box test sorts them per axis.
+// near* / far*: the planes of the four children this ray meets first / last on each axis.  load_node reads each axis' near and far plane vectors by
+// the sign of the ray's direction and the box test sorts nothing (slab.hpp box_entry_dir).  Cornell 1080p, same box, alternating: 9110-9125
+// Msamples/s against 8932-8935 with the planes read as stored and sorted per axis (profiles/r13_lds_node_step_ab.md).
 struct NodeDataWide {
     float4 nearx, neary, nearz, farx, fary, farz;
     int c0, c1, c2, c3;
@@ -115,12 +110,6 @@ struct LdsSceneSrc {
     const float4* tris;   // LDS
     bool strict;          // DeviceScene::strict_hits
     float reach;          // kSlabFmaReach * DeviceScene::scene_extent: origins within it may take the fma form of the box test (slab.hpp)
-    __device__ inline void node(int i, NodeDataWide& n) const {   // planes as stored: near* = min, far* = max
-        const float4* p = nodes + i * 8;
-        n.nearx = p[0]; n.neary = p[1]; n.nearz = p[2]; n.farx = p[3]; n.fary = p[4]; n.farz = p[5];
-        float4 c = p[6];
-        n.c0 = __float_as_int(c.x); n.c1 = __float_as_int(c.y); n.c2 = __float_as_int(c.z); n.c3 = __float_as_int(c.w);
-    }
     __device__ inline void tri(int i, float4& a, float4& b, float4& c) const {
         const float4* p = tris + i * 3;
         a = p[0]; b = p[1]; c = p[2];
@@ -163,14 +152,10 @@ template <bool STRICT> __device__ inline RaySlabWide make_slab(const LdsSceneSrc
 // the max vector by per-lane address (the node is 128-byte aligned data either way: six 16-byte reads and the child word, as before).
 __device__ inline void load_node(const GlobalSceneSrc& src, const RaySlab&, int i, NodeData& n) { src.node(i, n); }
 __device__ inline void load_node(const LdsSceneSrc& src, const RaySlabWide& r, int i, NodeDataWide& n) {
-#if VPT_LDS_PLANES_BY_SIGN
     const float4* p = src.nodes + i * 8;
     n.nearx = p[r.selx]; n.neary = p[r.sely]; n.nearz = p[r.selz]; n.farx = p[3 - r.selx]; n.fary = p[5 - r.sely]; n.farz = p[7 - r.selz];
     float4 c = p[6];
     n.c0 = __float_as_int(c.x); n.c1 = __float_as_int(c.y); n.c2 = __float_as_int(c.z); n.c3 = __float_as_int(c.w);
-#else
-    src.node(i, n);
-#endif
 }
 template <int K> __device__ inline float byte_f(uint32_t w) { return (float)((w >> (8 * K)) & 0xffu); }  // v_cvt_f32_ubyteK
 
@@ -231,11 +216,7 @@ __device__ inline void node_entries(const NodeDataWide& n, const RaySlabWide& r,
         ny.x -= r.o.y; ny.y -= r.o.y; ny.z -= r.o.y; ny.w -= r.o.y; fy.x -= r.o.y; fy.y -= r.o.y; fy.z -= r.o.y; fy.w -= r.o.y;
         nz.x -= r.o.z; nz.y -= r.o.z; nz.z -= r.o.z; nz.w -= r.o.z; fz.x -= r.o.z; fz.y -= r.o.z; fz.z -= r.o.z; fz.w -= r.o.z;
     }
-#if VPT_LDS_PLANES_BY_SIGN
 #define VPT_BOX(C) box_entry_dir(nx.C, ny.C, nz.C, fx.C, fy.C, fz.C, r.oi, r.inv, tmin, tlimit)
-#else
-#define VPT_BOX(C) box_entry_fma(nx.C, ny.C, nz.C, fx.C, fy.C, fz.C, r.oi, r.inv, tmin, tlimit)
-#endif
     t0 = VPT_BOX(x); t1 = VPT_BOX(y); t2 = VPT_BOX(z); t3 = VPT_BOX(w);
 #undef VPT_BOX
 }

@@ -7,8 +7,8 @@
 // also knows that the pointers it loads point to global memory.
 // WholeScene / WholeParams are DeviceScene / RenderParams with what k_whole knows at compile time as constant members that hide the fields
 // (STRICT, PLAIN and its black environment, one-sample frames), so the shared shader code (shade_core.hpp, shading.hpp, traverse.hpp), which
-// reads `sc.all_plain`, `P.samples_per_frame`, ... through a template parameter as camera_ray<Cam> does, folds them as it did when the kernel
-// wrote them into its own copy.  They add no word: a DeviceScene in memory is read as a WholeScene.
+// reads `sc.all_plain`, `P.samples_per_frame`, ... through a template parameter as camera_ray<Cam> does, folds them.  They add no word: a
+// DeviceScene in memory is read as a WholeScene.
 // Compiled for the device and — by tests/tools/whole_uniforms_driver.cpp — for the host (tests/test_whole_uniforms_cpu.py).
 #pragma once
 #include "device_types.hpp"
