@@ -51,12 +51,10 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeArgs a) {   //
     // only other reader, shade_core's "next sample of the pixel" branch, is not compiled: the planner gives this kernel one-sample frames only
     // (path_plan.hpp whole_possible), a compile-time fact of WholeParams.  Cornell 1080p, same box, alternating: 8827-8833 Msamples/s against
     // 8641-8658 with the camera in scalar registers (profiles/r11_whole_uniform_ab.md).
+    // The block (camera.hpp) also holds what camera_ray would compute alike for every sample of the launch: the camera's position, and whether the
+    // lens sample can move it — with depth of field off it cannot, and camera_ray only draws it: 9374-9398 against 9266-9295 (profiles/r16_whole_camera_ab.md).
     __shared__ CameraBlock cam;
-    if (threadIdx.x == 0u) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) { cam.view_inv[i] = P.view_inv[i]; cam.proj_inv[i] = P.proj_inv[i]; }
-        cam.width = P.width; cam.height = P.height; cam.focus_distance = P.focus_distance; cam.dof_strength = P.dof_strength;
-    }
+    if (threadIdx.x == 0u) fill_camera_block(cam, P.view_inv, P.proj_inv, P.width, P.height, P.focus_distance, P.dof_strength);
     // The loop's view of the arguments (whole_args.hpp): `a` again, where it lies in memory.  The loop reads the words of the scene, the parameters
     // and the path buffers from the kernel's argument segment where it uses them and holds none of them in registers across the trace loops.
     // Cornell 1080p, same box, alternating: 9250-9269 Msamples/s against 9100-9109 with the arguments held in registers and VGPR lanes

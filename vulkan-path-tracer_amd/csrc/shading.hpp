@@ -4,23 +4,14 @@
 // with -ffp-contract=off, so expression order here is part of the parity contract.
 #pragma once
 #include "device_types.hpp"
+#include "camera.hpp"   // Rng, the Defines.slang constants, random_circle, camera_ray
 
 namespace vpt {
 using namespace vptfp;
 
-// Defines.slang:1-7 (as fp32)
-#define VPT_PI 3.1415926535897F
-#define VPT_2PI 6.2831853071795F
-#define VPT_1_OVER_PI 0.3183098861837F
 constexpr uint32_t kMaxDepthMarker = 1000000u;  // Defines.slang:16 MAX_DEPTH
 
-struct Rng {  // Sampler.slang:21-43
-    uint32_t s;
-    __device__ inline float uf() { s = pcg_hash(s); return u32_to_unit(s); }
-};
-
 __device__ inline V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
-__device__ inline V4 v4(float x, float y, float z, float w) { V4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
 __device__ inline V4 lerp4(V4 a, V4 b, float t) { return v4(lerp(a.x, b.x, t), lerp(a.y, b.y, t), lerp(a.z, b.z, t), lerp(a.w, b.w, t)); }
 
 // ------------------------------------------------------------------ software samplers (LINEAR, mip 0)
@@ -381,12 +372,7 @@ __device__ inline void bsdf_init(Bsdf& b, const Sc& sc, const vpt_material& m, c
 }
 
 // ------------------------------------------------------------------ Sampler.slang
-__device__ inline V2 random_circle(Rng& r) {  // :102-112
-    float u1 = r.uf(), u2 = r.uf();
-    float s, c; sincos_(2.0f * VPT_PI * u1, &s, &c);
-    float rad = sqrt_(u2);
-    V2 o; o.x = rad * c; o.y = rad * s; return o;
-}
+// (random_circle, :102-112: camera.hpp)
 __device__ inline V3 random_sphere(Rng& r) {  // :114-133
     float u1 = r.uf(), u2 = r.uf();
     float s, c; sincos_(2.0f * VPT_PI * u1, &s, &c);
@@ -515,35 +501,6 @@ __device__ inline void sample_emissive(const Sc& sc, Rng& r, V3 pos, V3& to_ligh
         cpdf.x = ls.emissive_color[0] * te.x; cpdf.y = ls.emissive_color[1] * te.y; cpdf.z = ls.emissive_color[2] * te.z;
     }
     to_light_out = to_light; cpdf_out = cpdf;
-}
-
-// What camera_ray reads of RenderParams, field for field: the whole-path kernel keeps a copy per block in LDS (kernels_whole.hip), where it
-// costs no scalar registers between two refills.
-struct CameraBlock {
-    float view_inv[16], proj_inv[16];
-    uint32_t width, height;
-    float focus_distance, dof_strength;
-};
-// Camera ray + AA jitter + DOF, RayGen.slang:35-50 (4 draws, the DOF pair always drawn).  Cam: RenderParams or CameraBlock.
-template <class Cam>
-__device__ inline void camera_ray(const Cam& P, Rng& r, uint32_t x, uint32_t y, V3& origin, V3& direction) {
-    float j0 = r.uf(), j1 = r.uf();
-    float cx = ((float)x + 0.5f) + (j0 * (0.5f - -0.5f) + -0.5f);
-    float cy = ((float)y + 0.5f) + (j1 * (0.5f - -0.5f) + -0.5f);
-    float dx = (cx / (float)P.width) * 2.0f - 1.0f, dy = (cy / (float)P.height) * 2.0f - 1.0f;
-    V4 o4 = mat_v4(P.view_inv, v4(0.0f, 0.0f, 0.0f, 1.0f));
-    origin = v3(o4.x, o4.y, o4.z);
-    V4 tg = mat_v4(P.proj_inv, v4(dx, dy, 1.0f, 1.0f));
-    V3 tn = normalize(v3(tg.x, tg.y, tg.z));
-    V4 dd = mat_v4(P.view_inv, v4(tn.x, tn.y, tn.z, 0.0f));
-    direction = v3(dd.x, dd.y, dd.z);
-    V3 focus = origin + direction * max_(P.focus_distance, 0.001f);
-    V2 rc = random_circle(r);
-    float rox = rc.x * 0.5f * P.dof_strength, roy = rc.y * 0.5f * P.dof_strength;
-    V3 right = v3(P.view_inv[0], P.view_inv[1], P.view_inv[2]);
-    V3 upv = v3(P.view_inv[4], P.view_inv[5], P.view_inv[6]);
-    origin = origin + (rox * right + roy * upv);
-    direction = normalize(focus - origin);
 }
 
 }  // namespace vpt
