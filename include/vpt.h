@@ -626,6 +626,67 @@ int vpt_denoise_device(vpt_ctx* ctx, const vpt_denoise_params* params, void* rgb
 #define VPT_POST_SOURCE_DENOISED 1u   /* the image the latest vpt_denoise / vpt_denoise_device left in the context */
 int vpt_set_post_source(vpt_ctx* ctx, uint32_t source);
 
+/* ---- temporal accumulation -------------------------------------------------------------------------------------------------
+ * SVGF's other half: the previous result is reprojected through the first-hit geometry of the current frame, kept where the same surface
+ * is still seen, and the new samples are blended in — so a camera that moves does not start every frame from 1 spp.  The reference has no
+ * counterpart: its accumulation restarts with every camera change, as vpt_set_camera still does.  On the device, in the context's stream;
+ * the arithmetic is csrc/temporal.hpp's, and the device result equals a host compile of that header bit for bit.  The loop of a viewport:
+ *     vpt_set_camera -> vpt_render(k) -> vpt_temporal_accumulate -> vpt_denoise -> vpt_postprocess
+ *   a call            traces the VPT_FEATURES_CENTER guides anew (depth, normal, albedo, ids; camera, scene and flags as they stand, like
+ *                     vpt_denoise), blends the accumulation image of m frames (m = the context's frame count at the call; for the _device
+ *                     form at enqueue time) with the stored previous record, and makes the new record the previous one, with the camera it
+ *                     was made with.  Calling twice without a vpt_reset / vpt_set_camera in between counts those m frames twice.
+ *   hit pixels        X = the pixel's first hit; (fx, fy) = where the previous camera saw X; the four pixels around it are taps with their
+ *                     bilinear weights b.  A tap counts when it is inside the image, was a hit, |t_q - |X - o_prev|| <= depth_tolerance
+ *                     |X - o_prev|, n_p.n_q >= normal_threshold and (VPT_TEMPORAL_MATCH_INSTANCE) has the pixel's instance id.  With
+ *                     sum b > 0.01 there is a history: hist = sum b hist_q / sum b, n = sum b len_q / sum b, n' = min(n + m, max_history),
+ *                     out = hist + (cur - hist) min(m / n', 1), length n' — where that factor is 1 (m alone reaches max_history) out is cur
+ *                     itself, not the rounding of the expression, so max_history = 1 gives exactly the result without history.  Otherwise
+ *                     out = cur, length min(m, max_history).  A point behind the previous camera (clip w <= 0) or a singular previous
+ *                     camera has no history.
+ *   VPT_TEMPORAL_DEMODULATE  history and blend are of colour / max(albedo, 1e-3); the image handed out is multiplied by that of the current pixel.
+ *   miss pixels       keep their input bit for bit, have length 0 and are never a tap.
+ *   non-finite input  propagates into the result and the history; there is no guard.
+ *   result            an RGBA32F image kept in the context (alpha copied from the input) — a SNAPSHOT — and, if the pointer is not NULL, copied
+ *                     to the caller (width*height*16 bytes; a device pointer 16-byte aligned).  vpt_get_temporal_history: the history
+ *                     length of the latest result, width*height floats (a test hook and a debug view).
+ *   history           survives vpt_set_camera, vpt_reset, renders, vpt_denoise*, vpt_render_features, vpt_pick and the post calls.  It is
+ *                     dropped by everything else that resets the accumulation or changes what a pixel means — vpt_set_scene,
+ *                     vpt_set_material, vpt_set_instance_transforms (count > 0), vpt_set_environment, the volume, density-grid,
+ *                     phase-function and atmosphere calls, a vpt_set_params that resets, vpt_set_radiance, vpt_resize — and by
+ *                     vpt_temporal_reset; the next call then has no history anywhere.  Reprojecting through a moved instance's
+ *                     previous transform is out of scope: moving an instance drops the history.
+ *   memory            on first use, 124 bytes per pixel: the result (16), two records of history (r, g, b, length: 16), packed guide (n.xyz,
+ *                     t: 16) and instance id (4), and 36 of guides (albedo 16, ids 16, depth 4); re-made after vpt_resize.
+ *   side effects      like vpt_denoise: the accumulation, the frame counters and vpt_stats are untouched (stack_spills is recounted).
+ *   vpt_temporal_accumulate  blocking.  vpt_temporal_accumulate_device: enqueued behind the frames in flight like vpt_denoise_device, with a ticket.
+ *   errors            VPT_ERR_NO_SCENE before vpt_set_scene; VPT_ERR_INVALID_ARGUMENT for a NULL ctx or params, max_history == 0, a
+ *                     depth_tolerance that is not > 0, a normal_threshold outside [-1, 1] (or NaN), unknown flag bits, non-zero reserved
+ *                     words, an unaligned device pointer, a sharded context before vpt_assemble_shards, nothing rendered since the last
+ *                     reset (m == 0); for vpt_set_denoise_source a NULL ctx or an unknown source; for vpt_get_temporal_history a NULL
+ *                     argument or no result of the current size.  A failed call leaves the context usable and the previous history and
+ *                     result valid.
+ * vpt_set_denoise_source: which image vpt_denoise / vpt_denoise_device filter.  VPT_DENOISE_SOURCE_TEMPORAL: the latest temporal image
+ * (iterations == 0 copies it, so the post chain reaches it through VPT_POST_SOURCE_DENOISED); without one of the current size they return
+ * VPT_ERR_INVALID_ARGUMENT. */
+#define VPT_TEMPORAL_DEMODULATE     1u
+#define VPT_TEMPORAL_MATCH_INSTANCE 2u
+typedef struct vpt_temporal_params {
+    uint32_t max_history;     /* cap of the history length, in frames; >= 1 */
+    float depth_tolerance;    /* relative; > 0 */
+    float normal_threshold;   /* cosine; in [-1, 1] */
+    uint32_t flags;           /* VPT_TEMPORAL_* */
+    uint32_t reserved[2];
+} vpt_temporal_params;
+void vpt_default_temporal_params(vpt_temporal_params* out);   /* max_history 32, depth_tolerance 0.02, normal_threshold 0.9, both flags */
+int vpt_temporal_accumulate(vpt_ctx* ctx, const vpt_temporal_params* params, float* rgba_host);
+int vpt_temporal_accumulate_device(vpt_ctx* ctx, const vpt_temporal_params* params, void* rgba_device, uint64_t* ticket);
+int vpt_temporal_reset(vpt_ctx* ctx);                              /* drop the history; the next call starts afresh */
+int vpt_get_temporal_history(vpt_ctx* ctx, float* length_host);    /* VPT_ERR_INVALID_ARGUMENT without a result of the current size */
+#define VPT_DENOISE_SOURCE_RADIANCE 0u   /* the accumulation image (default) */
+#define VPT_DENOISE_SOURCE_TEMPORAL 1u   /* the image the latest vpt_temporal_accumulate / _device left in the context */
+int vpt_set_denoise_source(vpt_ctx* ctx, uint32_t source);
+
 /* ---- energy-compensation lookup tables -------------------------------------------
  * Replaces LookupTableCalculator::CalculateTable(tableSize, sampleCount) (LookupTableCalculator.cpp:44-157)
  * with its shaders LookupReflect.slang / LookupRefract.slang (+ ABOVE_SURFACE / BELOW_SURFACE): sampleCount/20

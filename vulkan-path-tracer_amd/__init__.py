@@ -14,6 +14,7 @@ from ._abi import default_params, default_post_params, volume, atmosphere  # noq
 from ._abi import PHASE_HENYEY_GREENSTEIN, PHASE_DRAINE, PHASE_HENYEY_GREENSTEIN_PLUS_DRAINE  # noqa: F401
 from ._abi import FEATURES_CENTER, FEATURES_SAMPLE  # noqa: F401
 from ._abi import default_denoise_params, DENOISE_DEMODULATE, DENOISE_MAX_ITERATIONS, POST_SOURCE_RADIANCE, POST_SOURCE_DENOISED  # noqa: F401
+from ._abi import default_temporal_params, TEMPORAL_DEMODULATE, TEMPORAL_MATCH_INSTANCE, DENOISE_SOURCE_RADIANCE, DENOISE_SOURCE_TEMPORAL  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -353,6 +354,37 @@ class PathTracer:
     def set_post_source(self, source):
         """vpt_set_post_source: POST_SOURCE_RADIANCE (default) or POST_SOURCE_DENOISED — the image postprocess / postprocess_device read."""
         _check(self.lib, self.ctx, self.lib.vpt_set_post_source(self.ctx, source), "vpt_set_post_source")
+
+    # ---- temporal accumulation (include/vpt.h vpt_temporal_accumulate / _device / vpt_temporal_reset / vpt_get_temporal_history / vpt_set_denoise_source)
+    def temporal_accumulate(self, params=None):
+        """vpt_temporal_accumulate: the accumulation image blended with the reprojected previous result -> float32 [h, w, 4].  The image also stays in
+        the context (a snapshot) for set_denoise_source(DENOISE_SOURCE_TEMPORAL), and becomes the history of the next call."""
+        tp = params or default_temporal_params()
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _check(self.lib, self.ctx, self.lib.vpt_temporal_accumulate(self.ctx, C.byref(tp), out.ctypes.data), "vpt_temporal_accumulate")
+        return out
+
+    def temporal_accumulate_device(self, params=None, ptr=None):
+        """vpt_temporal_accumulate_device: enqueued behind the frames in flight; the image is copied to device pointer `ptr` (16-byte aligned, or None)
+        on the context's device; returns the ticket."""
+        tp = params or default_temporal_params()
+        ticket = C.c_uint64(0)
+        _check(self.lib, self.ctx, self.lib.vpt_temporal_accumulate_device(self.ctx, C.byref(tp), ptr, C.byref(ticket)), "vpt_temporal_accumulate_device")
+        return int(ticket.value)
+
+    def temporal_reset(self):
+        """vpt_temporal_reset: drop the history; the next temporal_accumulate starts afresh."""
+        _check(self.lib, self.ctx, self.lib.vpt_temporal_reset(self.ctx), "vpt_temporal_reset")
+
+    def temporal_history(self):
+        """vpt_get_temporal_history: the history length, in frames, of the latest temporal result -> float32 [h, w] (0 on a miss)."""
+        out = np.empty((self.height, self.width), np.float32)
+        _check(self.lib, self.ctx, self.lib.vpt_get_temporal_history(self.ctx, out.ctypes.data), "vpt_get_temporal_history")
+        return out
+
+    def set_denoise_source(self, source):
+        """vpt_set_denoise_source: DENOISE_SOURCE_RADIANCE (default) or DENOISE_SOURCE_TEMPORAL — the image denoise / denoise_device filter."""
+        _check(self.lib, self.ctx, self.lib.vpt_set_denoise_source(self.ctx, source), "vpt_set_denoise_source")
 
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("primitive", "<u4"), ("instance", "<u4")])

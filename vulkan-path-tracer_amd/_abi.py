@@ -234,6 +234,24 @@ def default_denoise_params(**kw):
     return p
 
 
+TEMPORAL_DEMODULATE, TEMPORAL_MATCH_INSTANCE = 1, 2
+DENOISE_SOURCE_RADIANCE, DENOISE_SOURCE_TEMPORAL = 0, 1
+
+
+class TemporalParams(C.Structure):  # vpt_temporal_params
+    _fields_ = [("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def default_temporal_params(**kw):
+    """vpt_default_temporal_params: max_history 32, depth_tolerance 0.02, normal_threshold 0.9, albedo demodulation and instance matching."""
+    p = TemporalParams(32, 0.02, 0.9, TEMPORAL_DEMODULATE | TEMPORAL_MATCH_INSTANCE)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 # every symbol include/vpt.h declares, with (restype, argtypes)
 PROTOTYPES = {
     "vpt_create": (C.c_void_p, [C.POINTER(Config), C.POINTER(C.c_int)]),
@@ -289,6 +307,12 @@ PROTOTYPES = {
     "vpt_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]),
     "vpt_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(C.c_uint64)]),
     "vpt_set_post_source": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "vpt_default_temporal_params": (None, [C.POINTER(TemporalParams)]),
+    "vpt_temporal_accumulate": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), C.c_void_p]),
+    "vpt_temporal_accumulate_device": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vpt_temporal_reset": (C.c_int, [C.c_void_p]),
+    "vpt_get_temporal_history": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vpt_set_denoise_source": (C.c_int, [C.c_void_p, C.c_uint32]),
     "vpt_lab_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "vpt_lab_set_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "vpt_lab_trace": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),

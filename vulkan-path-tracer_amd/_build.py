@@ -16,7 +16,7 @@ LIB_LAB = os.path.join(HERE, "libvpt_hip_lab.so")
 SOURCES = ["kernels_whole.hip", "kernels_finish.hip", "kernels_bounce.hip", "kernels_aux.hip", "kernels_trace.hip", "kernels_stream.hip", "kernels_media.hip", "kernels_post.hip", "kernels_lut.hip",
            "api_context.hip", "api_scene.hip", "api_render.hip", "api_post.hip", "api_comm.hip", "bvh_build.cpp"]   # (the api_*.hip files hold no kernel: no fat binary, no per-file flag)
 LAB_SOURCES = ["kernels_lab_r1.hip", "api_lab.hip"]   # compiled and linked into the laboratory library only
-HEADERS = ["device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "grid_prep.hpp", "denoise.hpp", "kernels.hpp", "api_ctx.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "bvh_refit.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp", "whole_refill.hpp", "whole_args.hpp", "camera.hpp",
+HEADERS = ["device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "grid_prep.hpp", "denoise.hpp", "temporal.hpp", "kernels.hpp", "api_ctx.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "bvh_refit.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp", "whole_refill.hpp", "whole_args.hpp", "camera.hpp",
            os.path.join("..", "..", "include", "vpt.h"), os.path.join("..", "..", "include", "vpt_lab.h"), os.path.join("..", "..", "include", "vpt_fp32.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-result", "-Wno-pass-failed"]

@@ -45,6 +45,8 @@ void free_render_buffers(vpt_ctx* c) {
     c->post_out = nullptr; c->post_w = c->post_h = 0;
     if (c->dn_block) (void)hipFree(c->dn_block);   // the denoiser's images: re-made by the next vpt_denoise*, whose result is gone with them
     c->dn_block = nullptr; c->dn_w = c->dn_h = 0; c->dn_valid = false;
+    if (c->tp_block) (void)hipFree(c->tp_block);   // the temporal records and result: gone with the size they were made for
+    c->tp_block = nullptr; c->tp_w = c->tp_h = 0; c->tp_valid = c->tp_history = false;
 }
 
 // Size checks of a (width, height) before anything is freed or changed; *frames_out = the largest batch this context will render.
@@ -173,7 +175,7 @@ void sync_params(vpt_ctx* c) {
     P.emissive_pdf_bias = p.emissive_pdf_bias; P.flags = p.flags; P.base_seed = p.base_seed;
     P.split = p.screen_chunk_count; P.launch_off = c->d_launch_off;
     // the angles exactly as the shaders form them (Sampler.slang:333-334, Miss.slang:28-29); same header, same bits as on the device
-    const float VPT_PI = 3.1415926535897F;   // shading.hpp's M_PI
+    // (VPT_PI: camera.hpp's, the shaders' M_PI as fp32)
     vptfp::sincos_(P.sky_azimuth / 180.0f * VPT_PI, &P.sky_rot[0], &P.sky_rot[1]);
     vptfp::sincos_(P.sky_altitude / 180.0f * VPT_PI, &P.sky_rot[2], &P.sky_rot[3]);
     vptfp::sincos_(-(P.sky_altitude / 180.0f * VPT_PI), &P.sky_rot[4], &P.sky_rot[5]);
@@ -364,7 +366,7 @@ int ensure_legacy_buffers(vpt_ctx* c, Lane& L) {
     return VPT_OK;
 }
 
-void reset_accum(vpt_ctx* c) { c->frame_count = 0; c->dispatch_count = 0; c->samples_accum = 0; }  // PathTracer.h:183
+void reset_accum(vpt_ctx* c, bool keep_history) { c->frame_count = 0; c->dispatch_count = 0; c->samples_accum = 0; if (!keep_history) c->tp_history = false; }  // PathTracer.h:183
 
 void begin_timing(vpt_ctx* c, hipStream_t s, int kernel, hipEvent_t* a, hipEvent_t* b) {
     *a = *b = nullptr;
@@ -491,7 +493,7 @@ int vpt_set_camera(vpt_ctx* c, const float* vi, const float* pi) {
     if (!c || !vi || !pi) return VPT_ERR_INVALID_ARGUMENT;
     memcpy(c->P.view_inv, vi, 64); memcpy(c->P.proj_inv, pi, 64);   // host state only: batches already enqueued carry their own copy
     c->state_gen++;
-    reset_accum(c);
+    reset_accum(c, true);   // (the temporal history is reprojected through the new camera)
     return VPT_OK;
 }
 
@@ -534,7 +536,7 @@ int vpt_resize(vpt_ctx* c, uint32_t w, uint32_t h) {
     return alloc_render_buffers(c);
 }
 
-int vpt_reset(vpt_ctx* c) { if (!c) return VPT_ERR_INVALID_ARGUMENT; reset_accum(c); return VPT_OK; }
+int vpt_reset(vpt_ctx* c) { if (!c) return VPT_ERR_INVALID_ARGUMENT; reset_accum(c, true); return VPT_OK; }
 
 int vpt_device_identity(vpt_ctx* c, char* out, uint32_t out_bytes) {
     if (!c || !out || out_bytes < 32) return VPT_ERR_INVALID_ARGUMENT;

@@ -218,6 +218,16 @@ struct vpt_ctx {
     uint32_t dn_w = 0, dn_h = 0;     // size the block was made for
     bool dn_valid = false;           // dn_out holds a denoised image of dn_w x dn_h
     uint32_t post_source = VPT_POST_SOURCE_RADIANCE;
+    // temporal accumulation (api_post.hip): allocated on the first vpt_temporal_accumulate*, freed with the render buffers (vpt_resize, vpt_destroy)
+    float* tp_block = nullptr;       // one allocation: out | hist[0] | hist[1] | guide[0] | guide[1] | albedo | ids | depth | inst[0] | inst[1]
+    float *tp_out = nullptr, *tp_hist[2] = {nullptr, nullptr}, *tp_guide[2] = {nullptr, nullptr}, *tp_albedo = nullptr, *tp_depth = nullptr;
+    uint32_t *tp_ids = nullptr, *tp_inst[2] = {nullptr, nullptr};
+    uint32_t tp_w = 0, tp_h = 0;     // size the block was made for
+    uint32_t tp_latest = 0;          // which of the two records the latest call wrote
+    bool tp_valid = false;           // tp_out and record tp_latest hold a result of tp_w x tp_h
+    bool tp_history = false;         // ... and the next call may reproject it (dropped by everything that changes what a pixel means: reset_accum)
+    temporal::PrevCamera tp_camera{};   // the camera record tp_latest was made with
+    uint32_t denoise_source = VPT_DENOISE_SOURCE_RADIANCE;
 
     // profiling events
     std::vector<hipEvent_t> ev_pool;
@@ -256,7 +266,9 @@ int ensure_path_buffers(vpt_ctx* c, uint32_t want);
 int ensure_media_buffers(vpt_ctx* c, Lane& L);
 int ensure_sorted_buffers(vpt_ctx* c, Lane& L);
 int ensure_legacy_buffers(vpt_ctx* c, Lane& L);
-void reset_accum(vpt_ctx* c);
+// The accumulation starts afresh (PathTracer.h:183).  keep_history: the caller changed nothing a pixel's history depends on but the camera, which
+// vpt_temporal_accumulate reprojects through (vpt_set_camera, vpt_reset); every other caller drops the temporal history with the accumulation.
+void reset_accum(vpt_ctx* c, bool keep_history = false);
 int alloc_spill(vpt_ctx* c, Lane& L, int regions);
 Lane* get_lane(vpt_ctx* c, int k);
 int ensure_lane_buffers(vpt_ctx* c, Lane& L);

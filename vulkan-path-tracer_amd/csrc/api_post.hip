@@ -117,6 +117,8 @@ int check_denoise(vpt_ctx* c, const vpt_denoise_params* dp, const void* device_o
     if (dp->flags & ~VPT_DENOISE_DEMODULATE) return fail(c, VPT_ERR_INVALID_ARGUMENT, "unknown denoise flag bits");
     if (((uintptr_t)device_out & 15u) != 0u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "the device image must be 16-byte aligned");
     if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
+    if (c->denoise_source == VPT_DENOISE_SOURCE_TEMPORAL && !(c->tp_valid && c->tp_w == c->P.width && c->tp_h == c->P.height))
+        return fail(c, VPT_ERR_INVALID_ARGUMENT, "denoise source is the temporal image and there is none of this size: call vpt_temporal_accumulate first");
     return post_preconditions(c);
 }
 int ensure_denoise_buffers(vpt_ctx* c) {
@@ -137,7 +139,7 @@ int enqueue_denoise(vpt_ctx* c, const vpt_denoise_params* dp) {
     if (rc) return rc;
     hipStream_t s = c->main.stream;
     const uint32_t W = c->P.width, H = c->P.height;
-    const float* src = whole_image(c);
+    const float* src = c->denoise_source == VPT_DENOISE_SOURCE_TEMPORAL ? c->tp_out : whole_image(c);   // (check_denoise has asked for it)
     if (dp->iterations == 0) {
         HIPCHK(c, hipMemcpyAsync(c->dn_out, src, (size_t)W * H * 16, hipMemcpyDeviceToDevice, s));
     } else {
@@ -160,9 +162,117 @@ int enqueue_denoise(vpt_ctx* c, const vpt_denoise_params* dp) {
     return VPT_OK;
 }
 
+// ---- vpt_temporal_accumulate
+int check_temporal(vpt_ctx* c, const vpt_temporal_params* tp, const void* device_out) {
+    if (!c || !tp) return VPT_ERR_INVALID_ARGUMENT;
+    if (tp->max_history == 0u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "max_history must be >= 1");
+    if (!(tp->depth_tolerance > 0.0f)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "depth_tolerance must be > 0");
+    if (!(tp->normal_threshold >= -1.0f && tp->normal_threshold <= 1.0f)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "normal_threshold must be in [-1, 1]");
+    if (tp->flags & ~(VPT_TEMPORAL_DEMODULATE | VPT_TEMPORAL_MATCH_INSTANCE)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "unknown temporal flag bits");
+    if (tp->reserved[0] | tp->reserved[1]) return fail(c, VPT_ERR_INVALID_ARGUMENT, "reserved words must be 0");
+    if (((uintptr_t)device_out & 15u) != 0u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "the device image must be 16-byte aligned");
+    if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
+    int rc = post_preconditions(c);
+    if (rc) return rc;
+    if (c->frame_count == 0u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "nothing rendered since the last reset: there are no new samples to blend in");
+    return VPT_OK;
+}
+int ensure_temporal_buffers(vpt_ctx* c) {
+    const uint32_t w = c->P.width, h = c->P.height;
+    if (c->tp_block && c->tp_w == w && c->tp_h == h) return VPT_OK;
+    if (c->tp_block) (void)hipFree(c->tp_block);
+    c->tp_block = nullptr; c->tp_valid = c->tp_history = false; c->tp_w = c->tp_h = 0;
+    const size_t npx = (size_t)w * h;
+    HIPCHK(c, hipMalloc((void**)&c->tp_block, npx * (7 * 16 + 3 * 4)));   // seven 16-byte images first (every one 16-byte aligned), then the three of one word
+    float* p = c->tp_block;
+    c->tp_out = p; c->tp_hist[0] = p + npx * 4; c->tp_hist[1] = p + npx * 8; c->tp_guide[0] = p + npx * 12; c->tp_guide[1] = p + npx * 16;
+    c->tp_albedo = p + npx * 20; c->tp_ids = (uint32_t*)(p + npx * 24);
+    c->tp_depth = p + npx * 28; c->tp_inst[0] = (uint32_t*)(p + npx * 29); c->tp_inst[1] = (uint32_t*)(p + npx * 30);
+    c->tp_w = w; c->tp_h = h;
+    return VPT_OK;
+}
+// Guides into the new record, k_temporal against the previous one: the launches on the main lane's stream, nothing waited for.  The image is
+// whole_image(c) as the stream finds it; m is the frame count as the host has it now.  Nothing of the context changes before the last launch is queued.
+int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
+    int rc = ensure_temporal_buffers(c);
+    if (rc) return rc;
+    const uint32_t W = c->P.width, H = c->P.height;
+    const uint32_t prev = c->tp_latest, next = prev ^ 1u;
+    FirstHitArgs a{};
+    a.n = ((W + 7u) / 8u) * ((H + 7u) / 8u) * 64u;
+    a.mode = VPT_FEATURES_CENTER;
+    a.depth = c->tp_depth; a.normal = (float4*)c->tp_guide[next]; a.albedo = (float4*)c->tp_albedo; a.ids = (uint4*)c->tp_ids;
+    enqueue_first_hit(c, a);
+    temporal::Frame f{};
+    memcpy(f.view_inv, c->P.view_inv, 64); memcpy(f.proj_inv, c->P.proj_inv, 64);
+    f.width = W; f.height = H; f.focus_distance = c->P.focus_distance; f.dof_strength = c->P.dof_strength;
+    f.prev = c->tp_camera;
+    f.have_prev = (c->tp_valid && c->tp_history && c->tp_camera.ok) ? 1u : 0u;
+    f.m = (float)c->frame_count; f.max_history = (float)tp->max_history;
+    f.depth_tolerance = tp->depth_tolerance; f.normal_threshold = tp->normal_threshold; f.flags = tp->flags;
+    launch_temporal(c->main.stream, whole_image(c), c->tp_depth, c->tp_albedo, c->tp_ids, c->tp_hist[prev], c->tp_guide[prev], c->tp_inst[prev],
+                    c->tp_hist[next], c->tp_guide[next], c->tp_inst[next], c->tp_out, f);
+    c->tp_camera = temporal::prev_camera_of(c->P.view_inv, c->P.proj_inv);
+    c->tp_latest = next; c->tp_valid = true; c->tp_history = true;
+    return VPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void vpt_default_temporal_params(vpt_temporal_params* p) {
+    if (p) *p = vpt_temporal_params{32u, 0.02f, 0.9f, VPT_TEMPORAL_DEMODULATE | VPT_TEMPORAL_MATCH_INSTANCE, {0u, 0u}};
+}
+int vpt_temporal_accumulate(vpt_ctx* c, const vpt_temporal_params* tp, float* rgba_host) {
+    int rc = check_temporal(c, tp, nullptr);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if ((rc = drain(c))) return rc;
+    if ((rc = enqueue_temporal(c, tp))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    HIPCHK(c, hipGetLastError());
+    if (rgba_host) HIPCHK(c, hipMemcpy(rgba_host, c->tp_out, (size_t)c->tp_w * c->tp_h * 16, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+// Behind the frames in flight on the context's stream, like vpt_denoise_device: the next frame's resolve waits for it (it reads the image).
+int vpt_temporal_accumulate_device(vpt_ctx* c, const vpt_temporal_params* tp, void* rgba_device, uint64_t* ticket) {
+    int rc = check_temporal(c, tp, rgba_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if ((rc = finish_outstanding(c))) return rc;
+    if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));
+    if ((rc = enqueue_temporal(c, tp))) return rc;
+    if (rgba_device) HIPCHK(c, hipMemcpyAsync(rgba_device, c->tp_out, (size_t)c->tp_w * c->tp_h * 16, hipMemcpyDeviceToDevice, c->main.stream));
+    HIPCHK(c, hipEventRecord(c->ev_post, c->main.stream));
+    c->post_pending = true;
+    const uint64_t t = issue_ticket(c, c->main.stream);
+    if (ticket) *ticket = t;
+    return VPT_OK;
+}
+int vpt_temporal_reset(vpt_ctx* c) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    c->tp_history = false;   // (the latest result stays readable)
+    return VPT_OK;
+}
+int vpt_get_temporal_history(vpt_ctx* c, float* length_host) {
+    if (!c || !length_host) return VPT_ERR_INVALID_ARGUMENT;
+    if (!(c->tp_valid && c->tp_w == c->P.width && c->tp_h == c->P.height)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "no temporal result of this size: call vpt_temporal_accumulate first");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    { int rd = quiesce(c); if (rd) return rd; }
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    const size_t npx = (size_t)c->tp_w * c->tp_h;
+    std::vector<float> rec(npx * 4);   // (r, g, b, length) per pixel
+    HIPCHK(c, hipMemcpy(rec.data(), c->tp_hist[c->tp_latest], npx * 16, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npx; i++) length_host[i] = rec[i * 4 + 3];
+    return VPT_OK;
+}
+int vpt_set_denoise_source(vpt_ctx* c, uint32_t source) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    if (source > VPT_DENOISE_SOURCE_TEMPORAL) return fail(c, VPT_ERR_INVALID_ARGUMENT, "unknown denoise source");
+    c->denoise_source = source;
+    return VPT_OK;
+}
 
 void vpt_default_denoise_params(vpt_denoise_params* p) {
     if (p) *p = vpt_denoise_params{5u, 1.0f, 0.1f, 0.05f, VPT_DENOISE_DEMODULATE, 0u};

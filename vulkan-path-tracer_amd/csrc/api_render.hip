@@ -564,6 +564,7 @@ int vpt_set_radiance(vpt_ctx* c, const float* src, uint32_t frame_count) {
     c->frame_count = frame_count;
     c->dispatch_count = (uint64_t)frame_count * c->params.screen_chunk_count * c->params.screen_chunk_count;
     c->samples_accum = frame_count * c->params.samples_per_frame;
+    c->tp_history = false;   // the image is the caller's now: no temporal history describes it
     return VPT_OK;
 }
 

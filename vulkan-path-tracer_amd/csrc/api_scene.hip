@@ -197,6 +197,7 @@ int install_grid(vpt_ctx* c, DensityGrid g, const float* values, size_t n_values
     c->grids.swap(list);
     if (c->d_grids) (void)hipFree(c->d_grids);
     c->d_grids = dl; c->dsc.grids = dl;
+    c->tp_history = false;   // (a density-grid call: the temporal history goes, as with every other edit of the media)
     return (int)c->grids.size() - 1;
 }
 
@@ -472,6 +473,7 @@ int vpt_clear_density_grids(vpt_ctx* c) {
     c->grids.clear();
     if (c->d_grids) { (void)hipFree(c->d_grids); c->d_grids = nullptr; }
     c->dsc.grids = nullptr;
+    c->tp_history = false;
     return VPT_OK;
 }
 void vpt_default_atmosphere(vpt_atmosphere* a) {  // PathTracer.h:222-232

@@ -57,6 +57,28 @@ VPT_HD void camera_ray(const Cam& P, Rng& r, uint32_t x, uint32_t y, V3& origin,
     direction = normalize(focus - origin);
 }
 
+// camera_ray with its four draws handed in — the jitter pair and random_circle's point — instead of drawn: the same expressions in the same
+// order, so with the integrator's draws it is the integrator's ray bit for bit, and with (0.5, 0.5) and (0, 0) it is the ray through the pixel centre
+// with no lens offset.  k_first_hit (kernels_aux.hip) calls it, and temporal.hpp to find the world point of a pixel again: the integrators keep camera_ray.
+template <class Cam>
+VPT_HD void camera_ray_with(const Cam& P, float j0, float j1, V2 rc, uint32_t x, uint32_t y, V3& origin, V3& direction) {
+    float cx = ((float)x + 0.5f) + (j0 * (0.5f - -0.5f) + -0.5f);
+    float cy = ((float)y + 0.5f) + (j1 * (0.5f - -0.5f) + -0.5f);
+    float dx = (cx / (float)P.width) * 2.0f - 1.0f, dy = (cy / (float)P.height) * 2.0f - 1.0f;
+    V4 o4 = mat_v4(P.view_inv, v4(0.0f, 0.0f, 0.0f, 1.0f));
+    origin = v3(o4.x, o4.y, o4.z);
+    V4 tg = mat_v4(P.proj_inv, v4(dx, dy, 1.0f, 1.0f));
+    V3 tn = normalize(v3(tg.x, tg.y, tg.z));
+    V4 dd = mat_v4(P.view_inv, v4(tn.x, tn.y, tn.z, 0.0f));
+    direction = v3(dd.x, dd.y, dd.z);
+    V3 focus = origin + direction * max_(P.focus_distance, 0.001f);
+    float rox = rc.x * 0.5f * P.dof_strength, roy = rc.y * 0.5f * P.dof_strength;
+    V3 right = v3(P.view_inv[0], P.view_inv[1], P.view_inv[2]);
+    V3 upv = v3(P.view_inv[4], P.view_inv[5], P.view_inv[6]);
+    origin = origin + (rox * right + roy * upv);
+    direction = normalize(focus - origin);
+}
+
 // ---- the whole-path kernel's camera
 // What camera_ray reads of RenderParams — of the two matrices only rows 0-2: their rows 3 feed the .w that camera_ray drops — and, in that
 // room, what is the same for every sample of a launch: the camera's position and whether the lens sample can move it.  No larger than the

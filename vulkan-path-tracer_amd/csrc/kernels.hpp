@@ -2,6 +2,7 @@
 #pragma once
 #include "device_types.hpp"
 #include "denoise.hpp"
+#include "temporal.hpp"
 #include "../../include/vpt_lab.h"   // VPT_TRACE_* / VPT_LAB_* constants (the functions exist in the laboratory build only)
 #ifndef VPT_LAB
 #define VPT_LAB 0
@@ -148,5 +149,10 @@ void launch_tonemap(hipStream_t s, const float* hdr, const float* bloom0, uint8_
 // of a demodulated run, which reads `albedo`.  All images RGBA32F of w x h but depth (one float per pixel).
 void launch_denoise_prepare(hipStream_t s, const float* c, const float* depth, const float* albedo, float* guide, float* e, uint32_t w, uint32_t h, bool demodulate);
 void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, const float* albedo, float* out, uint32_t w, uint32_t h, const denoise::Pass& ps, bool remodulate);
+// vpt_temporal_accumulate (temporal.hpp holds the arithmetic): one launch over f.width x f.height.  cur, albedo, out: RGBA32F; depth: one float, ids: k_first_hit's
+// uint4, per pixel.  The previous record (prev_*: never read when f.have_prev is 0) and the new one are (hist F4, guide F4, inst uint32) per pixel; `guide`
+// holds the first-hit normal image on entry and the packed (n.xyz, t) on exit.
+void launch_temporal(hipStream_t s, const float* cur, const float* depth, const float* albedo, const uint32_t* ids, const float* prev_hist, const float* prev_guide, const uint32_t* prev_inst,
+                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f);
 
 }  // namespace vpt

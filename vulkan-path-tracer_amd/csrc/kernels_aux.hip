@@ -218,26 +218,7 @@ void launch_refit_level(hipStream_t s, const DeviceScene& sc, const uint32_t* or
     if (end > begin) hipLaunchKernelGGL(k_refit_level, dim3(cdiv(end - begin, 256)), dim3(256), 0, s, sc, order, begin, end, tris, pad, boxes, nodes_out, wide_out);
 }
 
-// camera_ray (shading.hpp) with its four draws handed in — the jitter pair and random_circle's point — instead of drawn: the same expressions in the same
-// order, so with the integrator's draws it is the integrator's ray bit for bit, and with (0.5, 0.5) and (0, 0) it is the ray through the pixel centre
-// with no lens offset.  Only k_first_hit calls it: the integrators keep camera_ray.
-__device__ inline void camera_ray_with(const RenderParams& P, float j0, float j1, V2 rc, uint32_t x, uint32_t y, V3& origin, V3& direction) {
-    float cx = ((float)x + 0.5f) + (j0 * (0.5f - -0.5f) + -0.5f);
-    float cy = ((float)y + 0.5f) + (j1 * (0.5f - -0.5f) + -0.5f);
-    float dx = (cx / (float)P.width) * 2.0f - 1.0f, dy = (cy / (float)P.height) * 2.0f - 1.0f;
-    V4 o4 = mat_v4(P.view_inv, v4(0.0f, 0.0f, 0.0f, 1.0f));
-    origin = v3(o4.x, o4.y, o4.z);
-    V4 tg = mat_v4(P.proj_inv, v4(dx, dy, 1.0f, 1.0f));
-    V3 tn = normalize(v3(tg.x, tg.y, tg.z));
-    V4 dd = mat_v4(P.view_inv, v4(tn.x, tn.y, tn.z, 0.0f));
-    direction = v3(dd.x, dd.y, dd.z);
-    V3 focus = origin + direction * max_(P.focus_distance, 0.001f);
-    float rox = rc.x * 0.5f * P.dof_strength, roy = rc.y * 0.5f * P.dof_strength;
-    V3 right = v3(P.view_inv[0], P.view_inv[1], P.view_inv[2]);
-    V3 upv = v3(P.view_inv[4], P.view_inv[5], P.view_inv[6]);
-    origin = origin + (rox * right + roy * upv);
-    direction = normalize(focus - origin);
-}
+// (camera_ray_with, the camera ray with its four draws handed in: camera.hpp)
 // The closest hit of a ray and, for a camera ray, what lies there (kernels.hpp FirstHitArgs): vpt_trace_rays' test hook on caller-supplied rays, and the
 // guide buffers of vpt_render_features / vpt_pick — the integrator's camera-ray query (RayGen.slang:70: direction normalised, tmin 0.01, tmax 100000)
 // followed by the head of ClosestHit.slang (SurfaceFrame, :45-71; Material.Initialize's base colour, Material.slang:44) and nothing after it.  In camera

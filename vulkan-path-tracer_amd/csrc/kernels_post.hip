@@ -609,6 +609,42 @@ void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, c
 #undef VPT_DN
 }
 
+// ---- vpt_temporal_accumulate (api_post.hip enqueue_temporal): temporal.hpp's temporal_pixel does all the arithmetic; the kernel only decides where a
+// value is read from, so the device gives the bits of the host compile (tests/test_gpu_temporal.py).  One thread per pixel on the 64 x 4 tile, a wave per
+// row.  The four taps of neighbouring lanes land on neighbouring pixels of the previous record (a reprojection is smooth where it is valid), so a wave's
+// tap is a handful of cache lines it shares with the next tap: no LDS staging.
+struct TpRecords {
+    // the previous record: read at the taps
+    const dn::F4* prev_hist; const dn::F4* prev_guide; const uint32_t* prev_inst;
+    // the new one: `guide` holds k_first_hit's normal on entry and the packed (n.xyz, t) on exit (every thread reads and writes its own pixel only)
+    dn::F4* hist; dn::F4* guide; uint32_t* inst;
+};
+struct TpPrevSrc {
+    const dn::F4* h; const dn::F4* g; const uint32_t* i; int w;
+    __device__ __forceinline__ dn::F4 hist(int x, int y) const { return h[(size_t)y * w + x]; }
+    __device__ __forceinline__ dn::F4 guide(int x, int y) const { return g[(size_t)y * w + x]; }
+    __device__ __forceinline__ uint32_t inst(int x, int y) const { return i[(size_t)y * w + x]; }
+};
+__global__ __launch_bounds__(256) void k_temporal(const dn::F4* cur, const float* depth, const dn::F4* albedo, const uint4* ids, TpRecords rec, dn::F4* out, temporal::Frame f) {
+    const int x = blockIdx.x * kTileW + (int)(threadIdx.x & 63u), y = blockIdx.y * kTileH + (int)(threadIdx.x >> 6);
+    if (x >= (int)f.width || y >= (int)f.height) return;
+    const size_t p = (size_t)y * f.width + x;
+    const dn::F4 g = dn::pack_guide(rec.guide[p], depth[p]);
+    const uint32_t inst = ids[p].x;
+    const TpPrevSrc prev{rec.prev_hist, rec.prev_guide, rec.prev_inst, (int)f.width};
+    const temporal::Result r = temporal::temporal_pixel(prev, f, x, y, cur[p], g, albedo[p], inst);
+    out[p] = r.image;
+    rec.hist[p] = r.record;
+    rec.guide[p] = g;
+    rec.inst[p] = inst;
+}
+void launch_temporal(hipStream_t s, const float* cur, const float* depth, const float* albedo, const uint32_t* ids, const float* prev_hist, const float* prev_guide, const uint32_t* prev_inst,
+                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f) {
+    const TpRecords rec{reinterpret_cast<const dn::F4*>(prev_hist), reinterpret_cast<const dn::F4*>(prev_guide), prev_inst, reinterpret_cast<dn::F4*>(hist), reinterpret_cast<dn::F4*>(guide), inst};
+    hipLaunchKernelGGL(k_temporal, dim3(cdiv_(f.width, kTileW), cdiv_(f.height, kTileH)), dim3(256), 0, s, reinterpret_cast<const dn::F4*>(cur), depth, reinterpret_cast<const dn::F4*>(albedo),
+                       reinterpret_cast<const uint4*>(ids), rec, reinterpret_cast<dn::F4*>(out), f);
+}
+
 void launch_bloom_threshold(hipStream_t s, const float* in, float* out, uint32_t w, uint32_t h, float threshold, float falloff) {
     uint32_t n = w * h;
     hipLaunchKernelGGL(k_bloom_threshold, dim3(cdiv_(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(in), reinterpret_cast<float4*>(out), n, threshold, falloff);
