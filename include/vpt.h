@@ -687,6 +687,50 @@ int vpt_get_temporal_history(vpt_ctx* ctx, float* length_host);    /* VPT_ERR_IN
 #define VPT_DENOISE_SOURCE_TEMPORAL 1u   /* the image the latest vpt_temporal_accumulate / _device left in the context */
 int vpt_set_denoise_source(vpt_ctx* ctx, uint32_t source);
 
+/* ---- SVGF: reseeding, luminance variance, variance-guided a-trous ------------------------------------------------------------------
+ * What turns the two calls above into SVGF (Schied et al. 2017).  The loop of a viewport:
+ *     vpt_set_camera -> vpt_set_base_seed(frame_index) -> vpt_render(k) -> vpt_temporal_accumulate -> vpt_denoise -> vpt_postprocess
+ * vpt_set_base_seed: vpt_params.base_seed and nothing else.  Every vpt_set_camera restarts the accumulation at dispatch 0, so without a new
+ *                     seed every frame of a moving viewport draws the same random numbers per pixel and the history averages the same noise.
+ *                     The accumulation restarts as after vpt_set_camera: the temporal history SURVIVES (vpt_set_params would drop it).  Waits
+ *                     for work in flight; a captured batch is not replayed with the old seed.  Afterwards the context renders, bit for bit,
+ *                     what a context given that seed through vpt_set_params renders (vpt_render_features in VPT_FEATURES_SAMPLE mode included).
+ *                     Setting the seed it already has still restarts the accumulation.  VPT_ERR_INVALID_ARGUMENT for a NULL ctx.
+ * vpt_set_svgf_options: context state, like vpt_set_denoise_source.  With variance == 0 (default) every call returns the bits it returned
+ *                     without these options, and nothing more is allocated or launched.  With variance == 1:
+ *   vpt_temporal_accumulate*  keeps, beside the colour record, the first and second moment (mu1, mu2) of the luminance l = (0.2126 r + 0.7152 g)
+ *                     + 0.0722 b of the colour the blend takes in (demodulated under VPT_TEMPORAL_DEMODULATE): reprojected over the same counted
+ *                     taps with the same weights, blended with the colour's own factor — mu' = h + (new - h) a, the new value (l, l l) itself
+ *                     where a is 1 or there is no history — and writes a variance image: max(0, mu2 - mu1 mu1) where the pixel's new
+ *                     history length is >= min_history * m, -1 ("unknown") where it is shorter, 0 on a miss (whose moments are (0, 0)).  Image
+ *                     and history length keep their bits.  The moments share every fate of the history.
+ *   vpt_denoise*      with VPT_DENOISE_SOURCE_TEMPORAL (with VPT_DENOISE_SOURCE_RADIANCE the option is ignored): the variance v rides through
+ *                     the passes beside the colour.  A pixel with v_p < 0 is filtered by the fixed-sigma_color rule above, tap for tap, and
+ *                     stays at -1.  Otherwise g = the 3 x 3 Gaussian (1/4, 1/8, 1/16) of v over the pixels at distance 1 (whatever the
+ *                     step) that are inside the image, hits and have v >= 0, normalised by the weights that counted; taps with v_q < 0 are
+ *                     skipped; w = exp(-(dn + dz + dl)) with dl = |lum(e_p) - lum(e_q)| / (sigma_luminance sqrt(g) + 1e-6), w = 1 at the
+ *                     centre; e' = sum k w e / sum k w and v' = sum (k w)^2 v / (sum k w)^2.  The last pass re-modulates and returns the
+ *                     source's alpha; iterations == 0 stays a copy.  The arithmetic is csrc/denoise.hpp's atrous_pixel_variance; the taps
+ *                     of every step are read from memory.
+ *   memory            20 bytes per pixel more on the first temporal call with the option on (two moment records, the variance image).
+ *   changing `variance`  drops the temporal history, like vpt_temporal_reset.
+ *   errors            VPT_ERR_INVALID_ARGUMENT for a NULL argument, a variance other than 0 or 1, a sigma_luminance that is not > 0,
+ *                     min_history == 0, a non-zero reserved word; for vpt_denoise* when the option is on, the source is the temporal image and
+ *                     the latest temporal result was made with the option off; for the two read-backs (test hooks and debug views) a NULL
+ *                     argument or no temporal result of the current size made with variance == 1. */
+typedef struct vpt_svgf_options {
+    uint32_t variance;        /* 0 (default): off, everything as without these options.  1: on */
+    float    sigma_luminance; /* SVGF's sigma_l; default 4; > 0 */
+    uint32_t min_history;     /* images a pixel's moments must hold before its variance is trusted; default 4; >= 1 */
+    uint32_t reserved;        /* 0 */
+} vpt_svgf_options;
+int vpt_set_base_seed(vpt_ctx* ctx, uint32_t base_seed);
+void vpt_default_svgf_options(vpt_svgf_options* out);   /* variance 0, sigma_luminance 4, min_history 4 */
+int vpt_set_svgf_options(vpt_ctx* ctx, const vpt_svgf_options* options);
+int vpt_get_svgf_options(const vpt_ctx* ctx, vpt_svgf_options* out);
+int vpt_get_temporal_variance(vpt_ctx* ctx, float* var_host);   /* width*height floats */
+int vpt_get_temporal_moments(vpt_ctx* ctx, float* mu_host);     /* width*height*2 floats: mu1, mu2 per pixel */
+
 /* ---- energy-compensation lookup tables -------------------------------------------
  * Replaces LookupTableCalculator::CalculateTable(tableSize, sampleCount) (LookupTableCalculator.cpp:44-157)
  * with its shaders LookupReflect.slang / LookupRefract.slang (+ ABOVE_SURFACE / BELOW_SURFACE): sampleCount/20

@@ -15,6 +15,7 @@ from ._abi import PHASE_HENYEY_GREENSTEIN, PHASE_DRAINE, PHASE_HENYEY_GREENSTEIN
 from ._abi import FEATURES_CENTER, FEATURES_SAMPLE  # noqa: F401
 from ._abi import default_denoise_params, DENOISE_DEMODULATE, DENOISE_MAX_ITERATIONS, POST_SOURCE_RADIANCE, POST_SOURCE_DENOISED  # noqa: F401
 from ._abi import default_temporal_params, TEMPORAL_DEMODULATE, TEMPORAL_MATCH_INSTANCE, DENOISE_SOURCE_RADIANCE, DENOISE_SOURCE_TEMPORAL  # noqa: F401
+from ._abi import SvgfOptions, default_svgf_options  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -385,6 +386,40 @@ class PathTracer:
     def set_denoise_source(self, source):
         """vpt_set_denoise_source: DENOISE_SOURCE_RADIANCE (default) or DENOISE_SOURCE_TEMPORAL — the image denoise / denoise_device filter."""
         _check(self.lib, self.ctx, self.lib.vpt_set_denoise_source(self.ctx, source), "vpt_set_denoise_source")
+
+    # ---- SVGF (include/vpt.h vpt_set_base_seed / vpt_set_svgf_options / vpt_get_svgf_options / vpt_get_temporal_variance / vpt_get_temporal_moments)
+    def set_base_seed(self, base_seed):
+        """vpt_set_base_seed: other random numbers from the next frame on.  The accumulation restarts as after set_camera: the temporal history survives."""
+        _check(self.lib, self.ctx, self.lib.vpt_set_base_seed(self.ctx, base_seed), "vpt_set_base_seed")
+
+    def set_svgf_options(self, **kw):
+        """vpt_set_svgf_options: the context's options with the fields given replaced (variance, sigma_luminance, min_history).  Changing `variance`
+        drops the temporal history."""
+        o = self.svgf_options()
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        _check(self.lib, self.ctx, self.lib.vpt_set_svgf_options(self.ctx, C.byref(o)), "vpt_set_svgf_options")
+
+    def svgf_options(self):
+        """vpt_get_svgf_options -> SvgfOptions."""
+        o = _abi.SvgfOptions()
+        _check(self.lib, self.ctx, self.lib.vpt_get_svgf_options(self.ctx, C.byref(o)), "vpt_get_svgf_options")
+        return o
+
+    def temporal_variance(self):
+        """vpt_get_temporal_variance: the luminance variance of the latest temporal result made with variance = 1 -> float32 [h, w]
+        (-1: history shorter than min_history images; 0 on a miss)."""
+        out = np.empty((self.height, self.width), np.float32)
+        _check(self.lib, self.ctx, self.lib.vpt_get_temporal_variance(self.ctx, out.ctypes.data), "vpt_get_temporal_variance")
+        return out
+
+    def temporal_moments(self):
+        """vpt_get_temporal_moments: first and second luminance moment of the latest temporal result made with variance = 1 -> float32 [h, w, 2]."""
+        out = np.empty((self.height, self.width, 2), np.float32)
+        _check(self.lib, self.ctx, self.lib.vpt_get_temporal_moments(self.ctx, out.ctypes.data), "vpt_get_temporal_moments")
+        return out
 
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("primitive", "<u4"), ("instance", "<u4")])

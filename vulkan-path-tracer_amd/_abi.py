@@ -252,6 +252,20 @@ def default_temporal_params(**kw):
     return p
 
 
+class SvgfOptions(C.Structure):  # vpt_svgf_options
+    _fields_ = [("variance", C.c_uint32), ("sigma_luminance", C.c_float), ("min_history", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def default_svgf_options(**kw):
+    """vpt_default_svgf_options: variance off, sigma_luminance 4, min_history 4."""
+    p = SvgfOptions(0, 4.0, 4, 0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 # every symbol include/vpt.h declares, with (restype, argtypes)
 PROTOTYPES = {
     "vpt_create": (C.c_void_p, [C.POINTER(Config), C.POINTER(C.c_int)]),
@@ -313,6 +327,12 @@ PROTOTYPES = {
     "vpt_temporal_reset": (C.c_int, [C.c_void_p]),
     "vpt_get_temporal_history": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_set_denoise_source": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "vpt_set_base_seed": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "vpt_default_svgf_options": (None, [C.POINTER(SvgfOptions)]),
+    "vpt_set_svgf_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfOptions)]),
+    "vpt_get_svgf_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfOptions)]),
+    "vpt_get_temporal_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vpt_get_temporal_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_lab_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "vpt_lab_set_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "vpt_lab_trace": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),

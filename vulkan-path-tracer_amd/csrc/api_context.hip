@@ -47,6 +47,8 @@ void free_render_buffers(vpt_ctx* c) {
     c->dn_block = nullptr; c->dn_w = c->dn_h = 0; c->dn_valid = false;
     if (c->tp_block) (void)hipFree(c->tp_block);   // the temporal records and result: gone with the size they were made for
     c->tp_block = nullptr; c->tp_w = c->tp_h = 0; c->tp_valid = c->tp_history = false;
+    if (c->sv_block) (void)hipFree(c->sv_block);   // ... and the luminance moments that went with them
+    c->sv_block = nullptr; c->sv_valid = false;
 }
 
 // Size checks of a (width, height) before anything is freed or changed; *frames_out = the largest batch this context will render.
@@ -519,6 +521,18 @@ int vpt_set_params(vpt_ctx* c, const vpt_params* p) {
         HIPCHK(c, hipSetDevice(c->cfg.device));
         int rc2 = refresh_material_tables(c); if (rc2) return rc2;
     }
+    return VPT_OK;
+}
+
+// The seed alone, for a viewport that wants other random numbers every frame: what vpt_set_params does for it (nothing in flight, no captured batch
+// replayed with the old seed), but the accumulation restarts the way vpt_set_camera restarts it — the temporal history stays.
+int vpt_set_base_seed(vpt_ctx* c, uint32_t base_seed) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    { int rd = drain(c); if (rd) return rd; }
+    c->state_gen++;
+    c->params.base_seed = base_seed;
+    sync_params(c);
+    reset_accum(c, true);
     return VPT_OK;
 }
 

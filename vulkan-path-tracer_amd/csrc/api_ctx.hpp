@@ -228,6 +228,11 @@ struct vpt_ctx {
     bool tp_history = false;         // ... and the next call may reproject it (dropped by everything that changes what a pixel means: reset_accum)
     temporal::PrevCamera tp_camera{};   // the camera record tp_latest was made with
     uint32_t denoise_source = VPT_DENOISE_SOURCE_RADIANCE;
+    // SVGF's variance (vpt_set_svgf_options): allocated on the first temporal call with the option on, for the size of tp_block, and freed wherever tp_block is
+    vpt_svgf_options svgf{0u, 4.0f, 4u, 0u};
+    float* sv_block = nullptr;       // one allocation: moments[0] | moments[1] (mu1, mu2 per pixel, swapped with the records) | variance
+    float *sv_moments[2] = {nullptr, nullptr}, *sv_variance = nullptr;
+    bool sv_valid = false;           // the latest temporal result was made with the option on: moments tp_latest and the variance image go with it
 
     // profiling events
     std::vector<hipEvent_t> ev_pool;

@@ -119,6 +119,8 @@ int check_denoise(vpt_ctx* c, const vpt_denoise_params* dp, const void* device_o
     if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
     if (c->denoise_source == VPT_DENOISE_SOURCE_TEMPORAL && !(c->tp_valid && c->tp_w == c->P.width && c->tp_h == c->P.height))
         return fail(c, VPT_ERR_INVALID_ARGUMENT, "denoise source is the temporal image and there is none of this size: call vpt_temporal_accumulate first");
+    if (c->denoise_source == VPT_DENOISE_SOURCE_TEMPORAL && c->svgf.variance && !c->sv_valid)
+        return fail(c, VPT_ERR_INVALID_ARGUMENT, "the variance-guided filter needs a temporal result made with vpt_svgf_options.variance == 1");
     return post_preconditions(c);
 }
 int ensure_denoise_buffers(vpt_ctx* c) {
@@ -144,17 +146,19 @@ int enqueue_denoise(vpt_ctx* c, const vpt_denoise_params* dp) {
         HIPCHK(c, hipMemcpyAsync(c->dn_out, src, (size_t)W * H * 16, hipMemcpyDeviceToDevice, s));
     } else {
         const bool demodulate = (dp->flags & VPT_DENOISE_DEMODULATE) != 0;
+        const bool variance = c->denoise_source == VPT_DENOISE_SOURCE_TEMPORAL && c->svgf.variance != 0u;   // (check_denoise: the variance image is there)
         FirstHitArgs a{};
         a.n = ((W + 7u) / 8u) * ((H + 7u) / 8u) * 64u;
         a.mode = VPT_FEATURES_CENTER;
         a.depth = c->dn_depth; a.normal = (float4*)c->dn_guide; a.albedo = (float4*)c->dn_albedo;
         enqueue_first_hit(c, a);
-        launch_denoise_prepare(s, src, c->dn_depth, c->dn_albedo, c->dn_guide, c->dn_ping, W, H, demodulate);
+        launch_denoise_prepare(s, src, c->dn_depth, c->dn_albedo, c->dn_guide, c->dn_ping, W, H, demodulate, variance ? c->sv_variance : nullptr);
         const float* in = c->dn_ping;
         for (uint32_t i = 0; i < dp->iterations; i++) {
             const bool last = i + 1 == dp->iterations;
             float* out = last ? c->dn_out : (in == c->dn_ping ? c->dn_pong : c->dn_ping);
-            launch_denoise_atrous(s, in, c->dn_guide, c->dn_albedo, out, W, H, denoise::pass_of(i, dp->sigma_color, dp->sigma_normal, dp->sigma_depth), last && demodulate);
+            launch_denoise_atrous(s, in, c->dn_guide, c->dn_albedo, out, W, H, denoise::pass_of(i, dp->sigma_color, dp->sigma_normal, dp->sigma_depth), last && demodulate,
+                                  variance, c->svgf.sigma_luminance, last);
             in = out;
         }
     }
@@ -182,6 +186,8 @@ int ensure_temporal_buffers(vpt_ctx* c) {
     if (c->tp_block && c->tp_w == w && c->tp_h == h) return VPT_OK;
     if (c->tp_block) (void)hipFree(c->tp_block);
     c->tp_block = nullptr; c->tp_valid = c->tp_history = false; c->tp_w = c->tp_h = 0;
+    if (c->sv_block) (void)hipFree(c->sv_block);   // (made for the old size)
+    c->sv_block = nullptr; c->sv_valid = false;
     const size_t npx = (size_t)w * h;
     HIPCHK(c, hipMalloc((void**)&c->tp_block, npx * (7 * 16 + 3 * 4)));   // seven 16-byte images first (every one 16-byte aligned), then the three of one word
     float* p = c->tp_block;
@@ -191,11 +197,21 @@ int ensure_temporal_buffers(vpt_ctx* c) {
     c->tp_w = w; c->tp_h = h;
     return VPT_OK;
 }
+// The luminance moments and the variance image, 20 B per pixel, for the size tp_block was made for: only ever with vpt_svgf_options.variance == 1.
+int ensure_variance_buffers(vpt_ctx* c) {
+    if (c->sv_block) return VPT_OK;
+    const size_t npx = (size_t)c->tp_w * c->tp_h;
+    HIPCHK(c, hipMalloc((void**)&c->sv_block, npx * (2 * 8 + 4)));
+    c->sv_moments[0] = c->sv_block; c->sv_moments[1] = c->sv_block + npx * 2; c->sv_variance = c->sv_block + npx * 4;
+    return VPT_OK;
+}
 // Guides into the new record, k_temporal against the previous one: the launches on the main lane's stream, nothing waited for.  The image is
 // whole_image(c) as the stream finds it; m is the frame count as the host has it now.  Nothing of the context changes before the last launch is queued.
 int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
     int rc = ensure_temporal_buffers(c);
     if (rc) return rc;
+    const bool variance = c->svgf.variance != 0u;
+    if (variance && (rc = ensure_variance_buffers(c))) return rc;
     const uint32_t W = c->P.width, H = c->P.height;
     const uint32_t prev = c->tp_latest, next = prev ^ 1u;
     FirstHitArgs a{};
@@ -211,9 +227,10 @@ int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
     f.m = (float)c->frame_count; f.max_history = (float)tp->max_history;
     f.depth_tolerance = tp->depth_tolerance; f.normal_threshold = tp->normal_threshold; f.flags = tp->flags;
     launch_temporal(c->main.stream, whole_image(c), c->tp_depth, c->tp_albedo, c->tp_ids, c->tp_hist[prev], c->tp_guide[prev], c->tp_inst[prev],
-                    c->tp_hist[next], c->tp_guide[next], c->tp_inst[next], c->tp_out, f);
+                    c->tp_hist[next], c->tp_guide[next], c->tp_inst[next], c->tp_out, f, variance ? c->sv_moments[prev] : nullptr, variance ? c->sv_moments[next] : nullptr,
+                    variance ? c->sv_variance : nullptr, (float)c->svgf.min_history * f.m);
     c->tp_camera = temporal::prev_camera_of(c->P.view_inv, c->P.proj_inv);
-    c->tp_latest = next; c->tp_valid = true; c->tp_history = true;
+    c->tp_latest = next; c->tp_valid = true; c->tp_history = true; c->sv_valid = variance;
     return VPT_OK;
 }
 
@@ -267,6 +284,42 @@ int vpt_get_temporal_history(vpt_ctx* c, float* length_host) {
     for (size_t i = 0; i < npx; i++) length_host[i] = rec[i * 4 + 3];
     return VPT_OK;
 }
+// ---- SVGF's variance: options, and the two read-backs of the latest temporal result made with them
+void vpt_default_svgf_options(vpt_svgf_options* o) {
+    if (o) *o = vpt_svgf_options{0u, 4.0f, 4u, 0u};
+}
+int vpt_set_svgf_options(vpt_ctx* c, const vpt_svgf_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    if (o->variance > 1u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "variance must be 0 or 1");
+    if (!(o->sigma_luminance > 0.0f)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "sigma_luminance must be > 0");
+    if (o->min_history == 0u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "min_history must be >= 1");
+    if (o->reserved) return fail(c, VPT_ERR_INVALID_ARGUMENT, "reserved words must be 0");
+    if (o->variance != c->svgf.variance) c->tp_history = false;   // a record without moments is never read as one with them
+    c->svgf = *o;
+    return VPT_OK;
+}
+int vpt_get_svgf_options(const vpt_ctx* c, vpt_svgf_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    *o = c->svgf;
+    return VPT_OK;
+}
+namespace {
+// The moment record (two floats per pixel) or the variance image (one) of the latest temporal result, which must have been made with the option on.
+int read_variance_result(vpt_ctx* c, float* host, bool moments) {
+    if (!c || !host) return VPT_ERR_INVALID_ARGUMENT;
+    if (!(c->tp_valid && c->sv_valid && c->tp_w == c->P.width && c->tp_h == c->P.height))
+        return fail(c, VPT_ERR_INVALID_ARGUMENT, "no temporal result of this size made with vpt_svgf_options.variance == 1");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    { int rd = quiesce(c); if (rd) return rd; }
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    const size_t npx = (size_t)c->tp_w * c->tp_h;
+    HIPCHK(c, hipMemcpy(host, moments ? c->sv_moments[c->tp_latest] : c->sv_variance, npx * (moments ? 8 : 4), hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+}  // namespace
+int vpt_get_temporal_variance(vpt_ctx* c, float* var_host) { return read_variance_result(c, var_host, false); }
+int vpt_get_temporal_moments(vpt_ctx* c, float* mu_host) { return read_variance_result(c, mu_host, true); }
+
 int vpt_set_denoise_source(vpt_ctx* c, uint32_t source) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
     if (source > VPT_DENOISE_SOURCE_TEMPORAL) return fail(c, VPT_ERR_INVALID_ARGUMENT, "unknown denoise source");

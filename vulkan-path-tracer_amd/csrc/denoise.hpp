@@ -110,5 +110,101 @@ VPT_HD F4 atrous_pixel(const Src& src, int x, int y, int w, int h, const Pass& p
     return r;
 }
 
+// ---- the variance-guided passes (vpt_svgf_options.variance == 1, denoise source TEMPORAL): SVGF's a-trous, Schied et al. 2017
+// The variance v of the temporal luminance moments rides in e.w through the passes (>= 0 known, -1 unknown); the source's alpha waits in the .w of the
+// denoiser's albedo copy, which no pass reads before the last one puts it back.  A miss keeps its input — alpha included — through every pass, as above.
+//   prepare     e.rgb as above; hit: e.w = v, albedo.w = alpha.
+//   pass, v_p < 0    the rule above for this pixel, tap for tap (fixed sigma_color, every hit tap: the same sums in the same order); v' = -1.
+//   pass, else  g = the 3 x 3 Gaussian (centre 1/4, edges 1/8, corners 1/16; row-major) of v over the pixels at distance 1 — whatever the step — that
+//               are inside the image, hits and have v >= 0, divided by the kernel weights that counted (>= 1/4: the centre counts unless v_p is NaN).
+//               Taps with v_q < 0 are skipped; for the others w = exp_(-((dn + dz) + dl)), dn and dz as above,
+//                   dl = |lum(e_p) - lum(e_q)| / (sigma_luminance sqrt_(g) + 1e-6)      lum = temporal's (0.2126 r + 0.7152 g) + 0.0722 b
+//               (the divisor's reciprocal formed once per pixel), w = 1 at the centre.
+//                   e' = sum k w e_q / sum k w          v' = sum (k w)^2 v_q / (sum k w)^2
+//               With g = 0 (a converged neighbourhood) the reciprocal is 1e6: a tap whose luminance differs by more than 1.04e-4 has weight exactly 0.
+//   last pass   multiplies by max_(albedo, 1e-3) again (DEMODULATE) and returns alpha to .w.
+constexpr float kLumFloor = 1.0e-6f;
+VPT_HD float luminance(const F4& e) { return (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z; }
+VPT_HD float prefilter_kernel(int d) { return d == 0 ? 0.5f : 0.25f; }   // outer product: centre 1/4, edges 1/8, corners 1/16
+// The prepare pass of one pixel: e (v in .w of a hit) and the albedo copy (alpha in .w of a hit).
+VPT_HD F4 prepare_pixel_variance(const F4& c, F4& albedo, float depth, bool demodulate, float v) {
+    F4 e = prepare_pixel(c, albedo, depth, demodulate);
+    if (depth < 0.0f) return e;
+    albedo.w = c.w;
+    e.w = v;
+    return e;
+}
+template <class Src>
+VPT_HD F4 atrous_pixel_variance(const Src& src, int x, int y, int w, int h, const Pass& ps, float sigma_luminance, const F4& ep, const F4& gp, bool last, bool remodulate, const F4& albedo) {
+    if (!is_hit(gp)) return ep;
+    const bool fixed = ep.w < 0.0f;   // unknown variance: today's rule
+    float rcp_lum = 0.0f;
+    const float lp = luminance(ep);
+    if (!fixed) {
+        float gs = 0.0f, gw = 0.0f;
+        VPT_DN_ROLLED
+        for (int dy = -1; dy <= 1; dy++) {
+            const int qy = y + dy;
+            if (qy < 0 || qy >= h) continue;
+            VPT_DN_ROLLED
+            for (int dx = -1; dx <= 1; dx++) {
+                const int qx = x + dx;
+                if (qx < 0 || qx >= w) continue;
+                const F4 gq = src.guide(qx, qy);
+                const F4 eq = src.color(qx, qy);
+                if (!is_hit(gq) || !(eq.w >= 0.0f)) continue;
+                const float k = prefilter_kernel(dy) * prefilter_kernel(dx);
+                gs = gs + k * eq.w;
+                gw = gw + k;
+            }
+        }
+        rcp_lum = 1.0f / (sigma_luminance * vptfp::sqrt_(gs / gw) + kLumFloor);
+    }
+    const float rcp_depth = 1.0f / (ps.depth_scale * vptfp::max_(gp.w, kDepthFloor));
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, sv = 0.0f;
+    VPT_DN_ROLLED
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * ps.step;
+        if (qy < 0 || qy >= h) continue;
+        const float ky = tap_kernel(dy);
+        VPT_DN_ROLLED
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * ps.step;
+            if (qx < 0 || qx >= w) continue;
+            const F4 gq = src.guide(qx, qy);
+            const F4 eq = src.color(qx, qy);
+            if (!is_hit(gq)) continue;
+            if (!fixed && eq.w < 0.0f) continue;
+            float wt = 1.0f;
+            if (dx != 0 || dy != 0) {
+                const float nd = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
+                const float dn = vptfp::max_(0.0f, 1.0f - nd) * ps.rcp_normal;
+                const float dz = vptfp::fabs_(gp.w - gq.w) * rcp_depth;
+                float dc;
+                if (fixed) {
+                    const float cx = ep.x - eq.x, cy = ep.y - eq.y, cz = ep.z - eq.z;
+                    dc = ((cx * cx + cy * cy) + cz * cz) * ps.rcp_color;
+                } else {
+                    dc = vptfp::fabs_(lp - luminance(eq)) * rcp_lum;
+                }
+                wt = vptfp::exp_(-((dn + dz) + dc));
+            }
+            const float kw = (ky * tap_kernel(dx)) * wt;
+            sr = sr + kw * eq.x;
+            sg = sg + kw * eq.y;
+            sb = sb + kw * eq.z;
+            sw = sw + kw;
+            sv = sv + (kw * kw) * eq.w;
+        }
+    }
+    F4 r = f4(sr / sw, sg / sw, sb / sw, fixed ? -1.0f : sv / (sw * sw));
+    if (remodulate) {
+        const F4 a = albedo_scale(albedo);
+        r.x = r.x * a.x; r.y = r.y * a.y; r.z = r.z * a.z;
+    }
+    if (last) r.w = albedo.w;
+    return r;
+}
+
 }  // namespace denoise
 }  // namespace vpt

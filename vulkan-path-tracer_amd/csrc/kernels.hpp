@@ -147,12 +147,16 @@ void launch_tonemap(hipStream_t s, const float* hdr, const float* bloom0, uint8_
 // vpt_denoise (denoise.hpp holds the arithmetic).  prepare: e = the (demodulated) colour of c; `guide` holds the first-hit normal image on entry and the
 // packed (n.xyz, t) on exit.  atrous: one pass in -> out at ps.step (steps 1 and 2 through an LDS tile, larger ones from memory); remodulate: the last pass
 // of a demodulated run, which reads `albedo`.  All images RGBA32F of w x h but depth (one float per pixel).
-void launch_denoise_prepare(hipStream_t s, const float* c, const float* depth, const float* albedo, float* guide, float* e, uint32_t w, uint32_t h, bool demodulate);
-void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, const float* albedo, float* out, uint32_t w, uint32_t h, const denoise::Pass& ps, bool remodulate);
+// variance (the variance-guided passes; nullptr / false: off): prepare puts a hit's variance into e.w and its alpha into albedo.w; a pass then runs
+// atrous_pixel_variance on taps from memory with sigma_luminance, and the `last` one returns the alpha.
+void launch_denoise_prepare(hipStream_t s, const float* c, const float* depth, float* albedo, float* guide, float* e, uint32_t w, uint32_t h, bool demodulate, const float* variance);
+void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, const float* albedo, float* out, uint32_t w, uint32_t h, const denoise::Pass& ps, bool remodulate,
+                           bool variance, float sigma_luminance, bool last);
 // vpt_temporal_accumulate (temporal.hpp holds the arithmetic): one launch over f.width x f.height.  cur, albedo, out: RGBA32F; depth: one float, ids: k_first_hit's
 // uint4, per pixel.  The previous record (prev_*: never read when f.have_prev is 0) and the new one are (hist F4, guide F4, inst uint32) per pixel; `guide`
-// holds the first-hit normal image on entry and the packed (n.xyz, t) on exit.
+// holds the first-hit normal image on entry and the packed (n.xyz, t) on exit.  variance != nullptr: the luminance moments (two floats per pixel, previous
+// and new) are carried too and the variance image (one float per pixel) is written; min_len = min_history * m.
 void launch_temporal(hipStream_t s, const float* cur, const float* depth, const float* albedo, const uint32_t* ids, const float* prev_hist, const float* prev_guide, const uint32_t* prev_inst,
-                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f);
+                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f, const float* prev_moments, float* moments, float* variance, float min_len);
 
 }  // namespace vpt

@@ -538,11 +538,18 @@ namespace dn = denoise;
 
 // One thread per pixel: e = the (demodulated) colour, and the guide packed in place — `guide` holds k_first_hit's normal on entry and (n.xyz, t) on exit
 // (every thread reads and writes its own pixel only).
-__global__ __launch_bounds__(256) void k_denoise_prepare(const dn::F4* c, const float* depth, const dn::F4* albedo, dn::F4* guide, dn::F4* e, uint32_t n, int demodulate) {
+// variance != nullptr (the variance-guided passes): a hit's e.w is its variance and its alpha waits in the albedo copy's .w.
+__global__ __launch_bounds__(256) void k_denoise_prepare(const dn::F4* c, const float* depth, dn::F4* albedo, dn::F4* guide, dn::F4* e, uint32_t n, int demodulate, const float* variance) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float t = depth[i];
-    e[i] = dn::prepare_pixel(c[i], albedo[i], t, demodulate != 0);
+    if (variance) {
+        dn::F4 a = albedo[i];
+        e[i] = dn::prepare_pixel_variance(c[i], a, t, demodulate != 0, variance[i]);
+        albedo[i] = a;
+    } else {
+        e[i] = dn::prepare_pixel(c[i], albedo[i], t, demodulate != 0);
+    }
     guide[i] = dn::pack_guide(guide[i], t);
 }
 
@@ -564,8 +571,10 @@ struct DnTileSrc {
     __device__ __forceinline__ dn::F4 color(int x, int y) const { return e[(y - oy) * kDnTW + (x - ox)]; }
     __device__ __forceinline__ dn::F4 guide(int x, int y) const { return g[(y - oy) * kDnTW + (x - ox)]; }
 };
-template <bool TILED>
-__global__ __launch_bounds__(256) void k_denoise_atrous(const dn::F4* in, const dn::F4* guide, const dn::F4* albedo, dn::F4* out, int w, int h, dn::Pass ps, int remodulate) {
+// VARIANCE: denoise.hpp's atrous_pixel_variance (e.w carries the variance; `last` returns alpha from the albedo copy); shipped in the memory-tap form, which
+// covers every step.
+template <bool TILED, bool VARIANCE>
+__global__ __launch_bounds__(256) void k_denoise_atrous(const dn::F4* in, const dn::F4* guide, const dn::F4* albedo, dn::F4* out, int w, int h, dn::Pass ps, int remodulate, float sigma_luminance, int last) {
     constexpr int N = TILED ? kDnTW * kDnTH : 1;
     __shared__ dn::F4 s_e[N];
     __shared__ dn::F4 s_g[N];
@@ -586,8 +595,11 @@ __global__ __launch_bounds__(256) void k_denoise_atrous(const dn::F4* in, const 
     if (x >= w || y >= h) return;
     const size_t p = (size_t)y * w + x;
     dn::F4 alb = dn::f4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (remodulate) alb = albedo[p];
-    if (TILED) {
+    if (remodulate || (VARIANCE && last)) alb = albedo[p];
+    if (VARIANCE) {
+        const DnMemorySrc src{in, guide, w};
+        out[p] = dn::atrous_pixel_variance(src, x, y, w, h, ps, sigma_luminance, in[p], guide[p], last != 0, remodulate != 0, alb);
+    } else if (TILED) {
         const DnTileSrc<N> src{s_e, s_g, x0 - halo, y0 - halo};
         out[p] = dn::atrous_pixel(src, x, y, w, h, ps, src.color(x, y), src.guide(x, y), remodulate != 0, alb);
     } else {
@@ -596,16 +608,18 @@ __global__ __launch_bounds__(256) void k_denoise_atrous(const dn::F4* in, const 
     }
 }
 
-void launch_denoise_prepare(hipStream_t s, const float* c, const float* depth, const float* albedo, float* guide, float* e, uint32_t w, uint32_t h, bool demodulate) {
+void launch_denoise_prepare(hipStream_t s, const float* c, const float* depth, float* albedo, float* guide, float* e, uint32_t w, uint32_t h, bool demodulate, const float* variance) {
     const uint32_t n = w * h;
-    hipLaunchKernelGGL(k_denoise_prepare, dim3(cdiv_(n, 256)), dim3(256), 0, s, reinterpret_cast<const dn::F4*>(c), depth, reinterpret_cast<const dn::F4*>(albedo),
-                       reinterpret_cast<dn::F4*>(guide), reinterpret_cast<dn::F4*>(e), n, demodulate ? 1 : 0);
+    hipLaunchKernelGGL(k_denoise_prepare, dim3(cdiv_(n, 256)), dim3(256), 0, s, reinterpret_cast<const dn::F4*>(c), depth, reinterpret_cast<dn::F4*>(albedo),
+                       reinterpret_cast<dn::F4*>(guide), reinterpret_cast<dn::F4*>(e), n, demodulate ? 1 : 0, variance);
 }
-void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, const float* albedo, float* out, uint32_t w, uint32_t h, const denoise::Pass& ps, bool remodulate) {
+// variance: the variance-guided pass (sigma_luminance; `last` returns alpha), always on taps from memory.
+void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, const float* albedo, float* out, uint32_t w, uint32_t h, const denoise::Pass& ps, bool remodulate,
+                           bool variance, float sigma_luminance, bool last) {
     const dim3 g(cdiv_(w, kTileW), cdiv_(h, kTileH)), b(256);
-#define VPT_DN(T) hipLaunchKernelGGL(k_denoise_atrous<T>, g, b, 0, s, reinterpret_cast<const dn::F4*>(in), reinterpret_cast<const dn::F4*>(guide), reinterpret_cast<const dn::F4*>(albedo), \
-                                     reinterpret_cast<dn::F4*>(out), (int)w, (int)h, ps, remodulate ? 1 : 0)
-    if (2 * ps.step <= kDnMaxHalo) VPT_DN(true); else VPT_DN(false);
+#define VPT_DN(T, V) hipLaunchKernelGGL((k_denoise_atrous<T, V>), g, b, 0, s, reinterpret_cast<const dn::F4*>(in), reinterpret_cast<const dn::F4*>(guide), reinterpret_cast<const dn::F4*>(albedo), \
+                                        reinterpret_cast<dn::F4*>(out), (int)w, (int)h, ps, remodulate ? 1 : 0, sigma_luminance, last ? 1 : 0)
+    if (variance) VPT_DN(false, true); else if (2 * ps.step <= kDnMaxHalo) VPT_DN(true, false); else VPT_DN(false, false);
 #undef VPT_DN
 }
 
@@ -618,31 +632,43 @@ struct TpRecords {
     const dn::F4* prev_hist; const dn::F4* prev_guide; const uint32_t* prev_inst;
     // the new one: `guide` holds k_first_hit's normal on entry and the packed (n.xyz, t) on exit (every thread reads and writes its own pixel only)
     dn::F4* hist; dn::F4* guide; uint32_t* inst;
+    // vpt_svgf_options.variance only, otherwise nullptr: the luminance moments of both records and the variance image
+    const temporal::M2* prev_moments; temporal::M2* moments; float* variance;
 };
 struct TpPrevSrc {
-    const dn::F4* h; const dn::F4* g; const uint32_t* i; int w;
+    const dn::F4* h; const dn::F4* g; const uint32_t* i; int w; const temporal::M2* m;
     __device__ __forceinline__ dn::F4 hist(int x, int y) const { return h[(size_t)y * w + x]; }
+    __device__ __forceinline__ temporal::M2 moments(int x, int y) const { return m ? m[(size_t)y * w + x] : temporal::M2{0.0f, 0.0f}; }
     __device__ __forceinline__ dn::F4 guide(int x, int y) const { return g[(size_t)y * w + x]; }
     __device__ __forceinline__ uint32_t inst(int x, int y) const { return i[(size_t)y * w + x]; }
 };
-__global__ __launch_bounds__(256) void k_temporal(const dn::F4* cur, const float* depth, const dn::F4* albedo, const uint4* ids, TpRecords rec, dn::F4* out, temporal::Frame f) {
+// ONE kernel for both settings of vpt_svgf_options.variance, by a run-time branch on rec.variance (a second instantiation was 4.5 KB the library's size
+// bound has no page for, DESIGN.md "Library size"): temporal_pixel_variance has temporal_pixel's statements for image and record, so with the option off the
+// bits are temporal_pixel's (tests/test_gpu_temporal.py holds them to its host compile); the tap's moment record is read beside its two other reads only
+// when there is one, and nothing more is written.
+__global__ __launch_bounds__(256) void k_temporal(const dn::F4* cur, const float* depth, const dn::F4* albedo, const uint4* ids, TpRecords rec, dn::F4* out, temporal::Frame f, float min_len) {
     const int x = blockIdx.x * kTileW + (int)(threadIdx.x & 63u), y = blockIdx.y * kTileH + (int)(threadIdx.x >> 6);
     if (x >= (int)f.width || y >= (int)f.height) return;
     const size_t p = (size_t)y * f.width + x;
     const dn::F4 g = dn::pack_guide(rec.guide[p], depth[p]);
     const uint32_t inst = ids[p].x;
-    const TpPrevSrc prev{rec.prev_hist, rec.prev_guide, rec.prev_inst, (int)f.width};
-    const temporal::Result r = temporal::temporal_pixel(prev, f, x, y, cur[p], g, albedo[p], inst);
-    out[p] = r.image;
-    rec.hist[p] = r.record;
+    const TpPrevSrc prev{rec.prev_hist, rec.prev_guide, rec.prev_inst, (int)f.width, rec.prev_moments};
+    const temporal::ResultV rv = temporal::temporal_pixel_variance(prev, f, min_len, x, y, cur[p], g, albedo[p], inst);
+    if (rec.variance) {
+        rec.moments[p] = rv.moments;
+        rec.variance[p] = rv.variance;
+    }
+    out[p] = rv.r.image;
+    rec.hist[p] = rv.r.record;
     rec.guide[p] = g;
     rec.inst[p] = inst;
 }
 void launch_temporal(hipStream_t s, const float* cur, const float* depth, const float* albedo, const uint32_t* ids, const float* prev_hist, const float* prev_guide, const uint32_t* prev_inst,
-                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f) {
-    const TpRecords rec{reinterpret_cast<const dn::F4*>(prev_hist), reinterpret_cast<const dn::F4*>(prev_guide), prev_inst, reinterpret_cast<dn::F4*>(hist), reinterpret_cast<dn::F4*>(guide), inst};
+                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f, const float* prev_moments, float* moments, float* variance, float min_len) {
+    const TpRecords rec{reinterpret_cast<const dn::F4*>(prev_hist), reinterpret_cast<const dn::F4*>(prev_guide), prev_inst, reinterpret_cast<dn::F4*>(hist), reinterpret_cast<dn::F4*>(guide), inst,
+                        reinterpret_cast<const temporal::M2*>(prev_moments), reinterpret_cast<temporal::M2*>(moments), variance};
     hipLaunchKernelGGL(k_temporal, dim3(cdiv_(f.width, kTileW), cdiv_(f.height, kTileH)), dim3(256), 0, s, reinterpret_cast<const dn::F4*>(cur), depth, reinterpret_cast<const dn::F4*>(albedo),
-                       reinterpret_cast<const uint4*>(ids), rec, reinterpret_cast<dn::F4*>(out), f);
+                       reinterpret_cast<const uint4*>(ids), rec, reinterpret_cast<dn::F4*>(out), f, min_len);
 }
 
 void launch_bloom_threshold(hipStream_t s, const float* in, float* out, uint32_t w, uint32_t h, float threshold, float falloff) {

@@ -173,5 +173,104 @@ VPT_HD Result temporal_pixel(const Prev& prev, const Frame& f, int x, int y, con
     return r;
 }
 
+// ---- per pixel, with the luminance moments (vpt_svgf_options.variance == 1): SVGF's variance estimate
+// temporal_pixel above, statement for statement — image and record have its bits — and beside it a second record per pixel, the first and second moment
+// of the luminance l = luminance(e_cur) of the SAME e_cur the colour blend uses (demodulated under DEMODULATE):
+//   taps        a counted tap adds b mu1_q and b mu2_q to two more sums, after the length's: the same taps, the same weights.
+//   history     sw > kMinWeight: h1 = s1 / sw, h2 = s2 / sw, mu1 = h1 + (l - h1) a, mu2 = h2 + (l l - h2) a with the colour's own a; where a is 1 the new
+//               values (l, l l) themselves.  No history: (l, l l).
+//   variance    max_(0, mu2 - mu1 mu1) where len' >= min_len (= min_history m, formed by the caller), -1 ("unknown": too few images for the moments to
+//               mean anything) otherwise, 0 on a miss.  A miss has moments (0, 0) and is never a tap.
+// prev.moments(x, y): the previous moment record, read beside prev.hist.  Non-finite input propagates; there is no guard.
+// k_temporal calls THIS function for both settings of the option (one kernel: the library's size bound) and drops the moments when it is off — image and
+// record are temporal_pixel's bits either way, which tests/test_svgf_cpu.py holds on the host and tests/test_gpu_temporal.py on the device.
+struct alignas(8) M2 { float mu1, mu2; };
+struct ResultV {
+    Result r;
+    M2 moments;
+    float variance;
+};
+constexpr float kUnknownVariance = -1.0f;
+// The order of the sum is fixed here: (r + g) + b.
+VPT_HD float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
+template <class Prev>
+VPT_HD ResultV temporal_pixel_variance(const Prev& prev, const Frame& f, float min_len, int x, int y, const F4& cur, const F4& guide, const F4& albedo, uint32_t inst) {
+    ResultV rv;
+    Result& r = rv.r;
+    if (!denoise::is_hit(guide)) {
+        r.image = cur;
+        r.record = denoise::f4(cur.x, cur.y, cur.z, 0.0f);
+        rv.moments.mu1 = 0.0f; rv.moments.mu2 = 0.0f;
+        rv.variance = 0.0f;
+        return rv;
+    }
+    const bool demodulate = (f.flags & kDemodulate) != 0u;
+    const F4 scale = denoise::albedo_scale(albedo);
+    float er = cur.x, eg = cur.y, eb = cur.z;
+    if (demodulate) { er = er / scale.x; eg = eg / scale.y; eb = eb / scale.z; }
+    const float l = luminance(er, eg, eb);
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    if (f.have_prev) {
+        V3 o, d;
+        V2 rc; rc.x = 0.0f; rc.y = 0.0f;
+        camera_ray_with(f, 0.5f, 0.5f, rc, (uint32_t)x, (uint32_t)y, o, d);
+        d = normalize(d);
+        const V3 X = o + guide.w * d;
+        const V4 clip = mat_v4(f.prev.clip, v4(X.x, X.y, X.z, 1.0f));
+        if (clip.w > 0.0f) {
+            const float fx = ((clip.x / clip.w + 1.0f) * 0.5f) * (float)f.width - 0.5f;
+            const float fy = ((clip.y / clip.w + 1.0f) * 0.5f) * (float)f.height - 0.5f;
+            const float x0 = floor_(fx), y0 = floor_(fy);
+            const float ax = fx - x0, ay = fy - y0;
+            const float te = length(X - v3(f.prev.origin[0], f.prev.origin[1], f.prev.origin[2]));
+            const float tol = f.depth_tolerance * te;
+            const V3 np = v3(guide.x, guide.y, guide.z);
+            for (int k = 0; k < 4; k++) {
+                const int i = k & 1, j = k >> 1;
+                const float qxf = x0 + (float)i, qyf = y0 + (float)j;
+                if (!(qxf >= 0.0f && qxf < (float)f.width && qyf >= 0.0f && qyf < (float)f.height)) continue;   // (a NaN is outside)
+                const int qx = (int)qxf, qy = (int)qyf;
+                const F4 gq = prev.guide(qx, qy);
+                const F4 hq = prev.hist(qx, qy);
+                const M2 mq = prev.moments(qx, qy);
+                const uint32_t iq = prev.inst(qx, qy);
+                if (!denoise::is_hit(gq)) continue;
+                if (!(fabs_(gq.w - te) <= tol)) continue;
+                if (!(dot(np, v3(gq.x, gq.y, gq.z)) >= f.normal_threshold)) continue;
+                if ((f.flags & kMatchInstance) != 0u && iq != inst) continue;
+                const float b = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+                sw = sw + b;
+                sr = sr + b * hq.x;
+                sg = sg + b * hq.y;
+                sb = sb + b * hq.z;
+                sl = sl + b * hq.w;
+                s1 = s1 + b * mq.mu1;
+                s2 = s2 + b * mq.mu2;
+            }
+        }
+    }
+    float len = min_(f.m, f.max_history);
+    float mu1 = l, mu2 = l * l;
+    if (sw > kMinWeight) {
+        const float hr = sr / sw, hg = sg / sw, hb = sb / sw, n = sl / sw;
+        len = min_(n + f.m, f.max_history);
+        const float a = min_(f.m / len, 1.0f);
+        if (a < 1.0f) {
+            const float h1 = s1 / sw, h2 = s2 / sw;
+            er = hr + (er - hr) * a;
+            eg = hg + (eg - hg) * a;
+            eb = hb + (eb - hb) * a;
+            mu1 = h1 + (mu1 - h1) * a;
+            mu2 = h2 + (mu2 - h2) * a;
+        }
+    }
+    r.record = denoise::f4(er, eg, eb, len);
+    r.image = demodulate ? denoise::f4(er * scale.x, eg * scale.y, eb * scale.z, cur.w) : denoise::f4(er, eg, eb, cur.w);
+    rv.moments.mu1 = mu1; rv.moments.mu2 = mu2;
+    rv.variance = len >= min_len ? max_(0.0f, mu2 - mu1 * mu1) : kUnknownVariance;
+    return rv;
+}
+
 }  // namespace temporal
 }  // namespace vpt

@@ -299,5 +299,24 @@ void PathTracer::SetPostSource(uint32_t source) {
     if (!m_Ctx) throw std::runtime_error("SetPostSource before SetScene");
     Check(vpt_set_post_source(m_Ctx, source), "vpt_set_post_source");
 }
+std::vector<float> PathTracer::TemporalAccumulate(const vpt_temporal_params& params, bool download) {
+    if (!m_Ctx) throw std::runtime_error("TemporalAccumulate before SetScene");
+    std::vector<float> out(download ? (size_t)m_Width * m_Height * 4 : 0);
+    Check(vpt_temporal_accumulate(m_Ctx, &params, download ? out.data() : nullptr), "vpt_temporal_accumulate");
+    return out;
+}
+void PathTracer::SetDenoiseSource(uint32_t source) {
+    if (!m_Ctx) throw std::runtime_error("SetDenoiseSource before SetScene");
+    Check(vpt_set_denoise_source(m_Ctx, source), "vpt_set_denoise_source");
+}
+void PathTracer::SetBaseSeed(uint32_t seed) {
+    m_Params.base_seed = seed;   // (before SetScene it goes with the parameters SetScene installs)
+    if (m_Ctx) Check(vpt_set_base_seed(m_Ctx, seed), "vpt_set_base_seed");
+    m_SamplesAccumulated = 0; m_DispatchCount = 0;
+}
+void PathTracer::SetSvgfOptions(const vpt_svgf_options& options) {
+    if (!m_Ctx) throw std::runtime_error("SetSvgfOptions before SetScene");
+    Check(vpt_set_svgf_options(m_Ctx, &options), "vpt_set_svgf_options");
+}
 
 }  // namespace vpthost

@@ -200,6 +200,19 @@ public:
     std::vector<float> Denoise(const vpt_denoise_params& params = DefaultDenoiseParams(), bool download = true);
     void SetPostSource(uint32_t source);   // VPT_POST_SOURCE_RADIANCE (default) / VPT_POST_SOURCE_DENOISED
 
+    // EXTENSION, no upstream member (the reference's accumulation restarts with every camera change): the accumulated image blended with the previous
+    // result reprojected through the first-hit guides (vpt_temporal_accumulate; blocking).  The result stays in the context as a snapshot —
+    // SetDenoiseSource(VPT_DENOISE_SOURCE_TEMPORAL) makes Denoise filter it — and is returned (width*height*4 floats) unless download is false.  The loop
+    // of a viewport: SetCameraViewInverse -> SetBaseSeed(frame index) -> PathTrace -> TemporalAccumulate -> Denoise -> PostProcess.
+    static vpt_temporal_params DefaultTemporalParams() { vpt_temporal_params p; vpt_default_temporal_params(&p); return p; }
+    std::vector<float> TemporalAccumulate(const vpt_temporal_params& params = DefaultTemporalParams(), bool download = true);
+    void SetDenoiseSource(uint32_t source);   // VPT_DENOISE_SOURCE_RADIANCE (default) / VPT_DENOISE_SOURCE_TEMPORAL
+    // EXTENSION: SetSeed's value without SetSeed's loss of the temporal history (vpt_set_base_seed): the accumulation restarts as after a camera change.
+    void SetBaseSeed(uint32_t seed);
+    // EXTENSION: SVGF's luminance variance and the variance-guided a-trous passes (vpt_set_svgf_options); context state, so after SetScene like SetPostSource.
+    static vpt_svgf_options DefaultSvgfOptions() { vpt_svgf_options o; vpt_default_svgf_options(&o); return o; }
+    void SetSvgfOptions(const vpt_svgf_options& options);
+
     [[nodiscard]] vpt_ctx* Context() const { return m_Ctx; }  // for PostProcessor
 
 private:
