@@ -230,7 +230,7 @@ typedef struct vpt_config {
 #define VPT_PIPELINE_STAGED_SORTED 4u /* STAGED with the shade queue sorted by material class (miss | plain | textured | glass | emissive),
                                        * one shade launch per class, the miss and plain ones specialised.  Bit-identical; measured
                                        * 10-14 % SLOWER than STAGED on the BASELINE scenes (profiles/REJECTED.md), so AUTO never picks it */
-#define VPT_PIPELINE_WHOLE 5u  /* ONE launch per batch: persistent waves run every path from its camera ray to its end, a lane whose path has ended takes
+#define VPT_PIPELINE_WHOLE 5u  /* one launch per batch (a batch of the headline's order of size: one per PART of it, a few — see vpt_stats.kernel_launches): persistent waves run every path from its camera ray to its end, a lane whose path has ended takes
                                * the batch's next sample (kernels_whole.hip k_whole; the reference's own shape: one RayGen thread = one whole path).
                                * For scenes whose BVH rides in LDS, no media, samples_per_frame == 1, every sample resident — VPT_ERR_UNSUPPORTED
                                * otherwise.  Bit-identical.  AUTO takes it wherever it applies: measured faster than FUSED at every batch size
@@ -240,7 +240,7 @@ typedef struct vpt_config {
 
 #define VPT_KERNEL_COUNT 10
 enum vpt_kernel_id {
-    VPT_K_PRIMARY = 0,  /* whole-path pipeline: the batch's one launch (k_whole); fused pipeline: bounce 0 (camera ray + extend + shade + connect);
+    VPT_K_PRIMARY = 0,  /* whole-path pipeline: the batch's launches of k_whole, one per part (below); fused pipeline: bounce 0 (camera ray + extend + shade + connect);
                          * staged pipeline: raygen */
     VPT_K_EXTEND = 1,
     VPT_K_SHADE = 2,
@@ -268,8 +268,10 @@ typedef struct vpt_stats {
     uint64_t tris_tested;      /* extend kernel, only when count_traversal */
     uint64_t shadow_nodes_visited; /* connect kernel, only when count_traversal */
     uint64_t shadow_tris_tested;   /* connect kernel, only when count_traversal */
-    uint64_t kernel_launches[VPT_KERNEL_COUNT];
-    double kernel_ms[VPT_KERNEL_COUNT]; /* only when profile */
+    uint64_t kernel_launches[VPT_KERNEL_COUNT];   /* whole-path batches count PARTS under VPT_K_PRIMARY and VPT_K_RESOLVE: a batch of at least ~450 M samples on a scene
+                                * with 1x1 textures and a black environment runs as 3 parts of consecutive frames, each part's resolve on a second stream
+                                * beside the next part's launch; every other batch is one part (csrc/path_plan.hpp decide) */
+    double kernel_ms[VPT_KERNEL_COUNT]; /* only when profile (a part's resolve is timed on its own stream: it overlaps the next part's launch) */
     uint64_t total_vertex_count; /* GetTotalVertexCount */
     uint64_t total_index_count;  /* GetTotalIndexCount */
     uint32_t bvh_nodes;

@@ -39,12 +39,17 @@ int vpt_lab_set_rays(vpt_ctx* ctx, const vpt_ray* rays_host, uint32_t n);
  *                         (0: never — the per-bounce kernels; 0xffff: no bound, the default)
  *   VPT_LAB_WHOLE_SCHED   how a whole-path launch deals its tiles of 64 samples: low 4 bits = tiles per atomic (1-15), bits 4-5 = rounds dealt without
  *                         an atomic (0: the first, 1: all but the last, 2: half, 3: the first, and the chunks shrink towards the end of the batch).  Default 4 (first
- *                         round static, then four tiles per atomic) */
+ *                         round static, then four tiles per atomic)
+ *   VPT_LAB_WHOLE_PARTS   a whole-path batch runs as this many equal parts of consecutive frames (1-8; frames / n each, the remainder goes to the first
+ *                         ones; no more parts than frames), each part's resolve on the second stream beside the next part's launch.  0, the default: the
+ *                         library's rule (path_plan.hpp decide: only batches of the headline's order of size are split).  Captured batches, batches on
+ *                         an extra lane and split-screen dispatches always run as one part */
 #define VPT_LAB_LANES 1u
 #define VPT_LAB_LANE_GRID 2u
 #define VPT_LAB_TAIL_GRID 3u
 #define VPT_LAB_WHOLE_FRAMES 4u
 #define VPT_LAB_WHOLE_SCHED 5u
+#define VPT_LAB_WHOLE_PARTS 6u
 int vpt_lab_set(vpt_ctx* ctx, uint32_t key, uint32_t value);
 int vpt_lab_trace(vpt_ctx* ctx, uint32_t variant, uint32_t any_hit, const uint32_t* order_host, uint32_t param, uint32_t reps,
                   vpt_hit* hits_host, float* best_ms, uint64_t* visits);

@@ -238,7 +238,8 @@ plan::Facts facts_of(const vpt_ctx* c) {
     f.pipeline = c->cfg.pipeline; f.build_flags = c->cfg.build_flags; f.lab_build = VPT_LAB != 0;
     f.has_scene = c->has_scene; f.lds_scene = c->lds_scene; f.whole_grid = c->whole_blocks > 0; f.media = media_on(c);
     f.samples_per_frame = c->P.samples_per_frame; f.split = c->P.split; f.max_depth = c->P.max_depth; f.depth_bounded = c->depth_bounded;
-    f.whole_frames_bound = c->lab_whole_frames;
+    f.whole_frames_bound = c->lab_whole_frames; f.whole_parts = c->lab_whole_parts;
+    f.whole_plain = c->scene_plain && !c->dsc.strict_hits && c->dsc.env_black;   // (launch_whole's choice, counting aside)
     f.profile = c->cfg.profile != 0; f.count_traversal = c->cfg.count_traversal != 0;
     f.shard_pixels = c->P.shard_pixels;
     f.cfg_frames = c->cfg.frames_in_flight; f.cfg_resident = c->cfg.resident_frames;

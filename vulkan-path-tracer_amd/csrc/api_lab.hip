@@ -8,13 +8,14 @@ using namespace vpt::api;
 extern "C" {
 
 int vpt_lab_set(vpt_ctx* c, uint32_t key, uint32_t value) {
-    if (!c || (value > 3u && key != VPT_LAB_WHOLE_FRAMES && key != VPT_LAB_WHOLE_SCHED)) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c || (value > 3u && key != VPT_LAB_WHOLE_FRAMES && key != VPT_LAB_WHOLE_SCHED && key != VPT_LAB_WHOLE_PARTS)) return VPT_ERR_INVALID_ARGUMENT;
     { int rd = quiesce(c); if (rd) return rd; }
     if (key == VPT_LAB_LANES && value >= 1u) c->lab_lanes = value;
     else if (key == VPT_LAB_LANE_GRID && value >= 1u) c->lab_lane_grid = value;
     else if (key == VPT_LAB_TAIL_GRID && value >= 1u) c->lab_tail_grid = value;
     else if (key == VPT_LAB_WHOLE_SCHED && (value & 15u) >= 1u && (value >> 4) <= 3u) c->lab_whole_sched = value;
     else if (key == VPT_LAB_WHOLE_FRAMES) c->lab_whole_frames = value == 0xffffu ? 0xffffffffu : value;   // (0xffff: no bound, the default)
+    else if (key == VPT_LAB_WHOLE_PARTS && value <= plan::kMaxParts) c->lab_whole_parts = value;
     else return VPT_ERR_INVALID_ARGUMENT;
     c->state_gen++;   // captured batches hold the old grids
     return VPT_OK;

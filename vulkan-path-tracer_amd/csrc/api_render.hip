@@ -33,6 +33,20 @@ int decide_batch(vpt_ctx* c, const Lane& L, const plan::Facts& f, uint32_t frame
     sd = plan::decide(f, frames, L.frames_alloc, L.resident_alloc, batch_slots(c->P, frames, dispatch_base), &L != &c->main, capturing);
     return sd.err != VPT_OK ? fail(c, sd.err, sd.msg) : VPT_OK;
 }
+// The path buffers as part of a whole-path batch sees them: its first sample is the part's slot 0 (seeds come from pixel and dispatch index, results
+// go to ACC[slot]: a sample computes the same in whichever part it runs).
+PathState part_state(const vpt_ctx* c, const Lane& L, uint32_t first_frame) {
+    PathState ps = L.ps;
+    const size_t at = (size_t)first_frame * c->P.shard_pixels;
+    ps.ACC += at; ps.M += at; ps.maniso += at;
+    return ps;
+}
+// The guarded resolve of part `i` of batch b (a batch that is not split is its own part 0) on stream `on`.  Frames resolve in order.
+void resolve_part(vpt_ctx* c, Lane& L, const BatchState& b, uint32_t i, hipStream_t on) {
+    const uint32_t first = b.sd.parts.first[i];
+    const uint32_t* guard = plan::runs_fused(b.sd.kind) ? &L.ctr->alive3[b.k3] : plan::runs_streams(b.sd.kind) ? &L.sctr->alive[b.parity].v : &L.ctr->ray_count[b.parity];
+    TIMED(c, on, VPT_K_RESOLVE, launch_resolve(on, c->P, part_state(c, L, first), c->image, b.sd.parts.first[i + 1] - first, b.dispatch_base + first, guard));
+}
 // Turns the decided schedule into buffers and launches.
 int batch_begin(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, uint32_t dispatch_base, Grids grids, BatchState& b) {
     hipStream_t s = L.stream;
@@ -61,14 +75,23 @@ int batch_begin(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, 
     if (n_slots == 0) return VPT_OK;
     HIPCHK(c, hipMemsetAsync(L.ctr, 0, offsetof(Counters, stat_closest), s));  // queue words only, stat_* keep running
     const DeviceScene dsc = lane_scene(c, L);
-    if (sd.kind == Kind::Whole) {  // the batch's paths from camera ray to their end in one launch; no queue is written, alive3[] stays 0 for the resolve's guard
-        const uint32_t grid = std::max(1u, std::min<uint32_t>((uint32_t)std::min(c->whole_blocks, b.primary_grid), (n_slots + 255u) / 256u));   // (blocks of 256 lanes)
-        // tiles of 64 samples: `rounds` per wave; mode 0: the first round static, mode 1: all but the last, mode 2: half of them; the rest through the counter
-        const uint32_t n_waves = grid * 4u, rounds = ((n_slots + 63u) / 64u) / n_waves, mode = c->lab_whole_sched >> 4;
-        const uint32_t static_rounds = (mode == 0u || mode == 3u) ? std::min(rounds, 1u) : mode == 1u ? (rounds >= 2u ? rounds - 1u : 0u) : rounds / 2u;
-        // (mode 3: mode 0 with guided chunks — at most the given tiles per atomic, fewer towards the end of the batch)
-        TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, L.ps, L.ctr, n_slots, dispatch_base, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u)));
+    if (sd.kind == Kind::Whole) {  // the batch's paths from camera ray to their end, one launch per part; no queue is written, alive3[] stays 0 for the resolve's guard
         b.parity = 1; b.k3 = 1; b.iter = 1;
+        for (uint32_t i = 0; i < sd.parts.n; i++) {
+            const uint32_t first = sd.parts.first[i], n_part = sd.parts.n > 1u ? (sd.parts.first[i + 1] - first) * c->P.shard_pixels : n_slots;
+            const uint32_t grid = std::max(1u, std::min<uint32_t>((uint32_t)std::min(c->whole_blocks, b.primary_grid), (n_part + 255u) / 256u));   // (blocks of 256 lanes)
+            // tiles of 64 samples: `rounds` per wave; mode 0: the first round static, mode 1: all but the last, mode 2: half of them; the rest through the counter
+            const uint32_t n_waves = grid * 4u, rounds = ((n_part + 63u) / 64u) / n_waves, mode = c->lab_whole_sched >> 4;
+            const uint32_t static_rounds = (mode == 0u || mode == 3u) ? std::min(rounds, 1u) : mode == 1u ? (rounds >= 2u ? rounds - 1u : 0u) : rounds / 2u;
+            // (mode 3: mode 0 with guided chunks — at most the given tiles per atomic, fewer towards the end of the batch)
+            if (i) HIPCHK(c, hipMemsetAsync(&L.ctr->extend_head, 0, 4, s));   // the tile cursor starts at 0 in every part
+            TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, part_state(c, L, first), L.ctr, n_part, dispatch_base + first, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u)));
+            if (i + 1u < sd.parts.n) {   // this part's resolve on the second stream, beside the next part's launch (the last part's: batch_resolve)
+                HIPCHK(c, hipEventRecord(L.ev_shade, s));
+                HIPCHK(c, hipStreamWaitEvent(L.stream2, L.ev_shade, 0));
+                resolve_part(c, L, b, i, L.stream2);
+            }
+        }
     } else if (sd.kind == Kind::Fused) {  // bounce 0 of every slot needs no input records; survivors land in queue[1]
         TIMED(c, s, VPT_K_PRIMARY, launch_bounce(s, (uint32_t)b.primary_grid, c->lds_scene, b.count, true, dsc, c->P, L.ps, L.ss, nullptr, L.queue[1], L.ctr, 0u, b.n_first, dispatch_base, 0u, c->scene_plain));
         b.parity = 1; b.k3 = 1; b.iter = 1;
@@ -191,8 +214,11 @@ int batch_resolve(vpt_ctx* c, Lane& L, BatchState& b) {
 #endif
     if (b.sd.overlap && b.join_pending) { HIPCHK(c, hipStreamWaitEvent(s, L.ev_join, 0)); b.join_pending = false; }   // the resolve reads the frame sums the join writes
     const bool stream = plan::runs_streams(b.sd.kind);
-    const uint32_t* guard = plan::runs_fused(b.sd.kind) ? &L.ctr->alive3[b.k3] : stream ? &L.sctr->alive[b.parity].v : &L.ctr->ray_count[b.parity];
-    TIMED(c, s, VPT_K_RESOLVE, launch_resolve(s, c->P, L.ps, c->image, b.frames, b.dispatch_base, guard));
+    if (b.sd.parts.n > 1u) {   // the last part's resolve follows the others', which went to the second stream (batch_begin)
+        HIPCHK(c, hipEventRecord(L.ev_join, L.stream2));
+        HIPCHK(c, hipStreamWaitEvent(s, L.ev_join, 0));
+    }
+    resolve_part(c, L, b, b.sd.parts.n - 1u, s);
     HIPCHK(c, hipMemcpyAsync(&L.h_ctr->ctr, L.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
     if (stream) {  // the exact number of live paths, and the queue length (holes included), which must fit the queue allocation
         HIPCHK(c, hipMemcpyAsync(&L.h_ctr->alive[0], &L.sctr->alive[b.parity].v, 4, hipMemcpyDeviceToHost, s));

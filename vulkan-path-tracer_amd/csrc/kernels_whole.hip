@@ -1,4 +1,6 @@
 // kernels_whole.hip — k_whole: whole paths in one launch, for scenes whose BVH rides in LDS (VPT_PIPELINE_WHOLE; the headline kernel).
+// A launch runs a batch, or one PART of a large one — consecutive frames, its slot 0 the part's first sample (api_render.hip part_state) — while the
+// resolve of the part before runs beside it on the lane's second stream (path_plan.hpp Schedule::parts); the kernel does not know the difference.
 // With it: launch_whole and whole_blocks_per_cu.  A wave is 64 lanes.  (Variants of this kernel that were measured and not taken: profiles/REJECTED.md.)
 #include "kernels.hpp"
 #include "traverse.hpp"
@@ -17,7 +19,7 @@ template <> struct OneSampleFrames<VPT_KERNARG WholeParams> { static constexpr b
 // (RayGen.slang:66-114).  k_whole is that loop on persistent waves, for scenes whose BVH rides in LDS and which have no media:
 // a lane keeps its path in registers from bounce to bounce, and a lane whose path has ended takes the next unstarted sample of the
 // batch, so a launch runs until the batch's samples are used up and no path record, queue or counter crosses HBM in between —
-// only the per-sample frame sums (ACC) do.  One launch per batch instead of max_depth: what a 1-frame batch at 1080p needs (its
+// only the per-sample frame sums (ACC) do.  One launch per batch (or part of one) instead of max_depth: what a 1-frame batch at 1080p needs (its
 // later bounces are launches of 10^5 paths that do not fill the chip, vpt_render_async).
 // A wave alternates two steps, each on full lanes:
 //   trace   every lane holds a ray — a survivor of the shade step or a fresh camera ray — and finds its closest hit; misses run the

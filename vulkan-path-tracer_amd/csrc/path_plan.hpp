@@ -33,6 +33,52 @@ constexpr uint64_t kSampleBytes = 36, kResidentBytes = 8 + 17 * 16 + 6;
 #endif
 constexpr uint32_t kFinishSmallBatchPaths = 6u << 20, kFinishAfterBounces = VPT_FINISH_AFTER, kFinishBelowPaths = VPT_FINISH_BELOW;
 
+// A large whole-path batch runs as a few PARTS of consecutive frames, one launch of k_whole each, and the resolve of part i runs on the lane's
+// second stream beside the launch of part i + 1: k_whole is bound by VALU issue and leaves the memory idle, the resolve is a pass over the
+// part's frame sums at the memory roof and leaves the VALU idle, so only the last part's resolve stays exposed.  One more launch costs about
+// 0.3 ms (ramp, drain of the rings, launch gap), the resolve about 2.7 ms per G samples:
+//  * batches of at least kPartsMinSamples samples are split (the smallest size measured to gain: 226 frames of 1080p; 56 frames lose 2.4 %),
+//  * on scenes that run k_whole's PLAIN instantiation only: three waves of the general one (168 registers) leave no room for a resolve wave (24) among a
+//    SIMD's 512 registers, and the compact material scene ran 0.3-0.6 % slower split,
+//  * into kPartsCount parts, each 1 / kPartsRatio as long as the one before (1: equal parts), so the exposed last resolve is short.
+// Measured: profiles/r17_whole_resolve_overlap_ab.md.
+#ifndef VPT_PARTS_MIN_SAMPLES   // (-D overrides, as above)
+#define VPT_PARTS_MIN_SAMPLES (27ull << 24)
+#endif
+#ifndef VPT_PARTS_COUNT
+#define VPT_PARTS_COUNT 3
+#endif
+#ifndef VPT_PARTS_RATIO
+#define VPT_PARTS_RATIO 4
+#endif
+constexpr uint32_t kMaxParts = 8;
+constexpr uint64_t kPartsMinSamples = VPT_PARTS_MIN_SAMPLES;
+constexpr uint32_t kPartsCount = VPT_PARTS_COUNT, kPartsRatio = VPT_PARTS_RATIO;
+static_assert(kPartsCount >= 1 && kPartsCount <= kMaxParts && kPartsRatio >= 1 && kPartsRatio <= 16, "parts of a whole-path batch");
+
+// The parts of a batch: part i is frames [first[i], first[i + 1]) of it; ascending, none empty, first[0] == 0 and first[n] == frames.
+struct Parts {
+    uint32_t n = 1;
+    uint32_t first[kMaxParts + 1] = {};
+};
+inline Parts one_part(uint32_t frames) { Parts p; p.first[1] = frames; return p; }
+// `n` parts of `frames` frames, each 1 / ratio as long as the one before as far as whole frames allow (ratio 1: equal parts, the remainder goes
+// to the first ones); min(n, frames) parts when the batch has fewer frames than that.
+inline Parts split_parts(uint32_t frames, uint32_t n, uint32_t ratio) {
+    n = std::max(1u, std::min(std::min(n, kMaxParts), frames));
+    Parts p; p.n = n;
+    uint64_t total = 0, w = 1, cum = 0;
+    for (uint32_t i = 0; i < n; i++) { total += w; w *= ratio; }   // weights ratio^(n-1), ..., ratio, 1
+    for (uint32_t i = 0; i < n; i++) {
+        w /= ratio; cum += w;
+        p.first[i + 1] = ratio == 1u ? (i + 1u) * (frames / n) + std::min(i + 1u, frames % n) : (uint32_t)((uint64_t)frames * cum / total);
+    }
+    for (uint32_t i = n - 1; i >= 1; i--) p.first[i] = std::min(p.first[i], frames - (n - i));   // none empty: room for the parts behind ...
+    for (uint32_t i = 1; i < n; i++) p.first[i] = std::max(p.first[i], p.first[i - 1] + 1u);      // ... and a frame for each
+    p.first[n] = frames;
+    return p;
+}
+
 // What scene, parameters and configuration say, as plain values (api_context.hip facts_of).
 struct Facts {
     uint32_t pipeline = VPT_PIPELINE_AUTO, build_flags = 0;   // vpt_config
@@ -44,6 +90,8 @@ struct Facts {
     uint32_t samples_per_frame = 1, split = 1, max_depth = 0;
     bool depth_bounded = true;       // every path ends within max_depth * samples_per_frame bounces (api_scene.hip update_depth_bounded)
     uint32_t whole_frames_bound = 0xffffffffu;   // VPT_PIPELINE_AUTO runs batches of at most this many frames as ONE whole-path launch (VPT_LAB_WHOLE_FRAMES)
+    bool whole_plain = false;        // ... which runs its PLAIN instantiation on this scene (counting aside): 158 registers, so that a resolve wave fits beside three of its waves per SIMD
+    uint32_t whole_parts = 0;        // != 0: a whole-path batch runs as this many equal parts wherever it may be split at all (VPT_LAB_WHOLE_PARTS); 0: the rule of decide()
     bool profile = false, count_traversal = false;   // vpt_config: kernels are timed / visits counted, one kernel at a time
     uint32_t shard_pixels = 1;
     uint32_t cfg_frames = 0, cfg_resident = 0;   // vpt_config.frames_in_flight / .resident_frames
@@ -198,7 +246,7 @@ inline Policy policy_of(const Facts& f) {
 }
 
 enum class Kind : uint32_t {
-    Whole,           // ONE launch of k_whole runs every path from its camera ray to its end
+    Whole,           // a launch of k_whole runs every path from its camera ray to its end (one per part of the batch: Schedule::parts)
     Fused,           // one kernel per bounce, bounce 0 included (k_bounce); media ride in it too
     Streams,         // extend -> shade (streams out) -> sky rays, light rays -> join on the vote-scheduled traversal kernels
     StreamsSorted,   // ... with the shade queue sorted by material class
@@ -215,6 +263,7 @@ struct Schedule {
     bool finisher = false;    // ONE launch of k_finish may run what is left of the batch to its end ...
     uint32_t finish_at = 0;   // ... and does once this many bounces have run (0: when the host sees few paths alive, if at all)
     bool overlap = false;     // the shadow-ray kernels and the join of bounce k run on the second stream, beside the extend of bounce k + 1
+    Parts parts;              // Kind::Whole: one launch and one resolve per part, the resolve of part i on the second stream beside the launch of part i + 1
     int err = VPT_OK;         // != VPT_OK: the batch is refused with `msg`, and nothing else of the schedule means anything
     const char* msg = nullptr;
 };
@@ -230,6 +279,7 @@ inline Schedule decide(const Facts& f, uint32_t frames, uint32_t frames_alloc, u
     // refilled with the batch's next unstarted samples behind every shade stage, until they are used up
     const bool whole = whole_policy(p, frames) && frames <= frames_alloc;   // (keeps its paths in registers: no records, nothing to regenerate)
     s.resident = whole ? frames : std::min(frames, resident_alloc);
+    s.parts = one_part(frames);
     s.regen = s.resident < frames;
     if (s.regen && !p.regen) return refuse(VPT_ERR_DEVICE, "internal: this batch needs all of its samples resident");
     // AUTO: fused for LDS-resident scenes, the stream pipeline otherwise (atrium 1150 vs 575, glass bust 2410 vs 1290, Cornell box with
@@ -250,6 +300,12 @@ inline Schedule decide(const Facts& f, uint32_t frames, uint32_t frames_alloc, u
     s.overlap = s.kind == Kind::Streams && !f.profile && !f.count_traversal && !capturing && !on_lane;   // (a lane's batch stays on its one stream: the lanes overlap each other)
     s.finisher = !(f.build_flags & VPT_BUILD_STREAMS_ONLY) && (s.kind == Kind::Streams || s.kind == Kind::StreamsSorted);
     if (s.finisher && !s.regen && n_slots <= kFinishSmallBatchPaths) s.finish_at = kFinishAfterBounces;
+    // Parts need the second stream and launch indices that are frames of shard_pixels samples: not a captured batch, not a lane's, no split-screen
+    // dispatch.  Timed and counted batches split like the others: bench.py divides the counters of an unprofiled run by the times of a profiled one.
+    if (s.kind == Kind::Whole && f.split == 1u && !capturing && !on_lane) {
+        if (f.whole_parts != 0u) s.parts = split_parts(frames, f.whole_parts, 1u);
+        else if (f.whole_plain && n_slots >= kPartsMinSamples) s.parts = split_parts(frames, kPartsCount, kPartsRatio);   // (the general instantiation's 168 registers leave the resolve no room: nothing to gain, two launches to pay)
+    }
     return s;
 }
 
