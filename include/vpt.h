@@ -656,8 +656,8 @@ int vpt_set_post_source(vpt_ctx* ctx, uint32_t source);
  *                     dropped by everything else that resets the accumulation or changes what a pixel means — vpt_set_scene,
  *                     vpt_set_material, vpt_set_instance_transforms (count > 0), vpt_set_environment, the volume, density-grid,
  *                     phase-function and atmosphere calls, a vpt_set_params that resets, vpt_set_radiance, vpt_resize — and by
- *                     vpt_temporal_reset; the next call then has no history anywhere.  Reprojecting through a moved instance's
- *                     previous transform is out of scope: moving an instance drops the history.
+ *                     vpt_temporal_reset; the next call then has no history anywhere.  Moving an instance drops the history unless
+ *                     vpt_temporal_options.instance_motion is 1 (below): then it is reprojected through the instance's previous transform.
  *   memory            on first use, 124 bytes per pixel: the result (16), two records of history (r, g, b, length: 16), packed guide (n.xyz,
  *                     t: 16) and instance id (4), and 36 of guides (albedo 16, ids 16, depth 4); re-made after vpt_resize.
  *   side effects      like vpt_denoise: the accumulation, the frame counters and vpt_stats are untouched (stack_spills is recounted).
@@ -732,6 +732,43 @@ int vpt_set_svgf_options(vpt_ctx* ctx, const vpt_svgf_options* options);
 int vpt_get_svgf_options(const vpt_ctx* ctx, vpt_svgf_options* out);
 int vpt_get_temporal_variance(vpt_ctx* ctx, float* var_host);   /* width*height floats */
 int vpt_get_temporal_moments(vpt_ctx* ctx, float* mu_host);     /* width*height*2 floats: mu1, mu2 per pixel */
+
+/* ---- the temporal history across instance moves -------------------------------------------------------------------------------------
+ * The loop of an animated viewport:
+ *     vpt_set_instance_transforms -> vpt_set_base_seed(frame_index) -> vpt_render(k) -> vpt_temporal_accumulate -> vpt_denoise -> vpt_postprocess
+ * vpt_set_temporal_options: context state, like vpt_set_svgf_options.  With instance_motion == 0 (default) every call returns the bits it
+ *                     returned without these options, nothing more is allocated, uploaded or launched, a move drops the history, and
+ *                     vpt_get_temporal_motion answers VPT_ERR_INVALID_ARGUMENT.  With instance_motion == 1:
+ *   vpt_set_instance_transforms  a call with count > 0 that succeeds restarts the accumulation the way vpt_set_camera does: the history, the
+ *                     moments and the stored previous camera survive.  A rejected or failed call changes nothing.
+ *   previous transform  of an instance: the matrix it had when the latest temporal record was made, however many moves lie between —
+ *                     two moves compose, a move there and back is no move.  Only the moved instances' matrices are kept.
+ *   vpt_temporal_accumulate*  compares previous and current matrix byte for byte, per instance.  Where none differs the call is the one above.
+ *                     Otherwise, per instance on the host in double, rounded to float once: D = M_prev M_cur^-1 and nt = the inverse transpose
+ *                     of D's upper 3 x 3.  A hit pixel of a moved instance uses Xp = D (X, 1) — where its surface WAS — for X in the clip
+ *                     transform and in the depth |Xp - o_prev|, and normalize(nt n_p) for n_p in the normal test; the instance test, the
+ *                     weights, the blend, the moments and the variance are untouched.  An instance whose M_cur or D is singular or not
+ *                     finite has no history; nothing else is affected.  The arithmetic is csrc/temporal.hpp's temporal_pixel_motion.
+ *   vpt_get_temporal_motion  width*height*2 floats: (fx - x, fy - y) per pixel — where the previous image saw the pixel's surface, minus the
+ *                     pixel's own coordinates — on hit pixels for which (fx, fy) was computed (a previous record, clip w > 0, an instance
+ *                     with a history), (0, 0) elsewhere.  A debug view and test hook, and what a host's own TAA or upscaler wants.  Valid
+ *                     for a result of the current size made with the option on.
+ *   the limit         a reprojection follows the surface, not the light: the history of a pixel NEAR a moved object still carries the old
+ *                     lighting — its shadow and its reflection lag by up to max_history frames.  This is SVGF's behaviour too.
+ *   memory            8 bytes per pixel (the motion image) on the first temporal call with the option on, and two tables of 112 bytes per
+ *                     instance on the first call after a move; freed with the temporal records.
+ *   changing `instance_motion`  drops the temporal history, like vpt_temporal_reset.  Everything that drops the history without the option
+ *                     still drops it, and forgets the previous transforms.
+ *   errors            VPT_ERR_INVALID_ARGUMENT for a NULL argument, instance_motion > 1, a non-zero reserved word; a refused call changes
+ *                     nothing. */
+typedef struct vpt_temporal_options {
+    uint32_t instance_motion;   /* 0 (default): a move drops the history.  1: the history is reprojected through the move */
+    uint32_t reserved[3];       /* 0 */
+} vpt_temporal_options;
+void vpt_default_temporal_options(vpt_temporal_options* out);   /* instance_motion 0 */
+int vpt_set_temporal_options(vpt_ctx* ctx, const vpt_temporal_options* options);
+int vpt_get_temporal_options(const vpt_ctx* ctx, vpt_temporal_options* out);
+int vpt_get_temporal_motion(vpt_ctx* ctx, float* motion_host);   /* width*height*2 floats */
 
 /* ---- energy-compensation lookup tables -------------------------------------------
  * Replaces LookupTableCalculator::CalculateTable(tableSize, sampleCount) (LookupTableCalculator.cpp:44-157)

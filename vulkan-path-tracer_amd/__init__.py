@@ -16,6 +16,7 @@ from ._abi import FEATURES_CENTER, FEATURES_SAMPLE  # noqa: F401
 from ._abi import default_denoise_params, DENOISE_DEMODULATE, DENOISE_MAX_ITERATIONS, POST_SOURCE_RADIANCE, POST_SOURCE_DENOISED  # noqa: F401
 from ._abi import default_temporal_params, TEMPORAL_DEMODULATE, TEMPORAL_MATCH_INSTANCE, DENOISE_SOURCE_RADIANCE, DENOISE_SOURCE_TEMPORAL  # noqa: F401
 from ._abi import SvgfOptions, default_svgf_options  # noqa: F401
+from ._abi import TemporalOptions, default_temporal_options  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -419,6 +420,30 @@ class PathTracer:
         """vpt_get_temporal_moments: first and second luminance moment of the latest temporal result made with variance = 1 -> float32 [h, w, 2]."""
         out = np.empty((self.height, self.width, 2), np.float32)
         _check(self.lib, self.ctx, self.lib.vpt_get_temporal_moments(self.ctx, out.ctypes.data), "vpt_get_temporal_moments")
+        return out
+
+    # ---- the temporal history across instance moves (include/vpt.h vpt_set_temporal_options / vpt_get_temporal_options / vpt_get_temporal_motion)
+    def set_temporal_options(self, **kw):
+        """vpt_set_temporal_options: the context's options with the fields given replaced (instance_motion).  With instance_motion = 1
+        set_instance_transforms keeps the temporal history and temporal_accumulate reprojects it through the move.  Changing it drops the history."""
+        o = self.temporal_options()
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        _check(self.lib, self.ctx, self.lib.vpt_set_temporal_options(self.ctx, C.byref(o)), "vpt_set_temporal_options")
+
+    def temporal_options(self):
+        """vpt_get_temporal_options -> TemporalOptions."""
+        o = _abi.TemporalOptions()
+        _check(self.lib, self.ctx, self.lib.vpt_get_temporal_options(self.ctx, C.byref(o)), "vpt_get_temporal_options")
+        return o
+
+    def temporal_motion(self):
+        """vpt_get_temporal_motion: where the previous image saw each pixel's surface, minus the pixel's own coordinates, of the latest temporal result
+        made with instance_motion = 1 -> float32 [h, w, 2] ((0, 0) on a miss and wherever nothing was reprojected)."""
+        out = np.empty((self.height, self.width, 2), np.float32)
+        _check(self.lib, self.ctx, self.lib.vpt_get_temporal_motion(self.ctx, out.ctypes.data), "vpt_get_temporal_motion")
         return out
 
 

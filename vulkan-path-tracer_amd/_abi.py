@@ -266,6 +266,20 @@ def default_svgf_options(**kw):
     return p
 
 
+class TemporalOptions(C.Structure):  # vpt_temporal_options
+    _fields_ = [("instance_motion", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+def default_temporal_options(**kw):
+    """vpt_default_temporal_options: instance_motion off (a move drops the temporal history)."""
+    p = TemporalOptions(0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 # every symbol include/vpt.h declares, with (restype, argtypes)
 PROTOTYPES = {
     "vpt_create": (C.c_void_p, [C.POINTER(Config), C.POINTER(C.c_int)]),
@@ -333,6 +347,10 @@ PROTOTYPES = {
     "vpt_get_svgf_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfOptions)]),
     "vpt_get_temporal_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_get_temporal_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vpt_default_temporal_options": (None, [C.POINTER(TemporalOptions)]),
+    "vpt_set_temporal_options": (C.c_int, [C.c_void_p, C.POINTER(TemporalOptions)]),
+    "vpt_get_temporal_options": (C.c_int, [C.c_void_p, C.POINTER(TemporalOptions)]),
+    "vpt_get_temporal_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_lab_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "vpt_lab_set_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "vpt_lab_trace": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),

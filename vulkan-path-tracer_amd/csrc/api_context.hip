@@ -49,6 +49,7 @@ void free_render_buffers(vpt_ctx* c) {
     c->tp_block = nullptr; c->tp_w = c->tp_h = 0; c->tp_valid = c->tp_history = false;
     if (c->sv_block) (void)hipFree(c->sv_block);   // ... and the luminance moments that went with them
     c->sv_block = nullptr; c->sv_valid = false;
+    free_motion_buffers(c);
 }
 
 // Size checks of a (width, height) before anything is freed or changed; *frames_out = the largest batch this context will render.
@@ -369,7 +370,12 @@ int ensure_legacy_buffers(vpt_ctx* c, Lane& L) {
     return VPT_OK;
 }
 
-void reset_accum(vpt_ctx* c, bool keep_history) { c->frame_count = 0; c->dispatch_count = 0; c->samples_accum = 0; if (!keep_history) c->tp_history = false; }  // PathTracer.h:183
+void reset_accum(vpt_ctx* c, bool keep_history) { c->frame_count = 0; c->dispatch_count = 0; c->samples_accum = 0; if (!keep_history) { c->tp_history = false; c->tp_snapshot.clear(); } }  // PathTracer.h:183
+void free_motion_buffers(vpt_ctx* c) {
+    if (c->tp_motion) (void)hipFree(c->tp_motion);
+    for (int k = 0; k < 2; k++) { if (c->tp_motion_table[k]) (void)hipFree(c->tp_motion_table[k]); c->tp_motion_table[k] = nullptr; }
+    c->tp_motion = nullptr; c->tp_motion_cap = 0; c->tp_motion_valid = false;
+}
 
 void begin_timing(vpt_ctx* c, hipStream_t s, int kernel, hipEvent_t* a, hipEvent_t* b) {
     *a = *b = nullptr;

@@ -234,6 +234,15 @@ struct vpt_ctx {
     float* sv_block = nullptr;       // one allocation: moments[0] | moments[1] (mu1, mu2 per pixel, swapped with the records) | variance
     float *sv_moments[2] = {nullptr, nullptr}, *sv_variance = nullptr;
     bool sv_valid = false;           // the latest temporal result was made with the option on: moments tp_latest and the variance image go with it
+    // moved instances (vpt_set_temporal_options): nothing of this is allocated, kept or uploaded while instance_motion is 0
+    vpt_temporal_options tp_options{0u, {0u, 0u, 0u}};
+    temporal::MotionSnapshot tp_snapshot;   // the matrices, at the latest record, of the instances moved since: only while a history is there to carry
+    float* tp_motion = nullptr;      // the motion image, 8 B per pixel of tp_w x tp_h: allocated on the first temporal call with the option on, freed wherever tp_block is
+    temporal::InstanceMotion* tp_motion_table[2] = {nullptr, nullptr};   // the per-instance records, swapped like the records of the image: the table a queued k_temporal reads is never written
+    std::vector<temporal::InstanceMotion> tp_motion_host[2];             // ... and what each was uploaded from
+    size_t tp_motion_cap = 0;        // records each table holds
+    uint32_t tp_motion_latest = 0;
+    bool tp_motion_valid = false;    // the latest temporal result was made with the option on: tp_motion goes with it
 
     // profiling events
     std::vector<hipEvent_t> ev_pool;
@@ -275,6 +284,7 @@ int ensure_legacy_buffers(vpt_ctx* c, Lane& L);
 // The accumulation starts afresh (PathTracer.h:183).  keep_history: the caller changed nothing a pixel's history depends on but the camera, which
 // vpt_temporal_accumulate reprojects through (vpt_set_camera, vpt_reset); every other caller drops the temporal history with the accumulation.
 void reset_accum(vpt_ctx* c, bool keep_history = false);
+void free_motion_buffers(vpt_ctx* c);   // the motion image and tables of vpt_temporal_options.instance_motion: wherever tp_block goes
 int alloc_spill(vpt_ctx* c, Lane& L, int regions);
 Lane* get_lane(vpt_ctx* c, int k);
 int ensure_lane_buffers(vpt_ctx* c, Lane& L);

@@ -188,6 +188,7 @@ int ensure_temporal_buffers(vpt_ctx* c) {
     c->tp_block = nullptr; c->tp_valid = c->tp_history = false; c->tp_w = c->tp_h = 0;
     if (c->sv_block) (void)hipFree(c->sv_block);   // (made for the old size)
     c->sv_block = nullptr; c->sv_valid = false;
+    free_motion_buffers(c);
     const size_t npx = (size_t)w * h;
     HIPCHK(c, hipMalloc((void**)&c->tp_block, npx * (7 * 16 + 3 * 4)));   // seven 16-byte images first (every one 16-byte aligned), then the three of one word
     float* p = c->tp_block;
@@ -205,6 +206,35 @@ int ensure_variance_buffers(vpt_ctx* c) {
     c->sv_moments[0] = c->sv_block; c->sv_moments[1] = c->sv_block + npx * 2; c->sv_variance = c->sv_block + npx * 4;
     return VPT_OK;
 }
+// vpt_temporal_options.instance_motion == 1: the motion image, 8 B per pixel of the size tp_block was made for ...
+int ensure_motion_image(vpt_ctx* c) {
+    if (c->tp_motion) return VPT_OK;
+    HIPCHK(c, hipMalloc((void**)&c->tp_motion, (size_t)c->tp_w * c->tp_h * 8));
+    return VPT_OK;
+}
+// ... and, when an instance's matrix differs from the one it had at the previous record, the per-instance records: built on the host, into the table the
+// previous call did not read (that call's k_temporal may still be queued), by a copy in the main stream's order.  *table stays nullptr when nothing moved.
+int upload_motion_table(vpt_ctx* c, bool have_prev, const temporal::InstanceMotion** table) {
+    *table = nullptr;
+    const uint32_t n = (uint32_t)c->instances.size();
+    const uint32_t k = c->tp_motion_latest ^ 1u;
+    if (!have_prev || n == 0u || !c->tp_snapshot.table(n, c->instances[0].xform, sizeof(InstanceDesc), c->tp_motion_host[k])) return VPT_OK;
+    if (c->tp_motion_cap < n) {
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));   // (a queued k_temporal may read the tables freed here: they go only behind it)
+        for (int j = 0; j < 2; j++) {
+            if (c->tp_motion_table[j]) (void)hipFree(c->tp_motion_table[j]);
+            c->tp_motion_table[j] = nullptr;
+        }
+        c->tp_motion_cap = 0;
+        HIPCHK(c, hipMalloc((void**)&c->tp_motion_table[0], (size_t)n * sizeof(temporal::InstanceMotion)));
+        HIPCHK(c, hipMalloc((void**)&c->tp_motion_table[1], (size_t)n * sizeof(temporal::InstanceMotion)));
+        c->tp_motion_cap = n;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->tp_motion_table[k], c->tp_motion_host[k].data(), (size_t)n * sizeof(temporal::InstanceMotion), hipMemcpyHostToDevice, c->main.stream));
+    c->tp_motion_latest = k;
+    *table = c->tp_motion_table[k];
+    return VPT_OK;
+}
 // Guides into the new record, k_temporal against the previous one: the launches on the main lane's stream, nothing waited for.  The image is
 // whole_image(c) as the stream finds it; m is the frame count as the host has it now.  Nothing of the context changes before the last launch is queued.
 int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
@@ -212,6 +242,11 @@ int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
     if (rc) return rc;
     const bool variance = c->svgf.variance != 0u;
     if (variance && (rc = ensure_variance_buffers(c))) return rc;
+    const bool motion = c->tp_options.instance_motion != 0u;
+    const bool history = c->tp_valid && c->tp_history;
+    const temporal::InstanceMotion* motion_table = nullptr;
+    if (motion && (rc = ensure_motion_image(c))) return rc;
+    if (motion && (rc = upload_motion_table(c, history && c->tp_camera.ok, &motion_table))) return rc;
     const uint32_t W = c->P.width, H = c->P.height;
     const uint32_t prev = c->tp_latest, next = prev ^ 1u;
     FirstHitArgs a{};
@@ -223,14 +258,15 @@ int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
     memcpy(f.view_inv, c->P.view_inv, 64); memcpy(f.proj_inv, c->P.proj_inv, 64);
     f.width = W; f.height = H; f.focus_distance = c->P.focus_distance; f.dof_strength = c->P.dof_strength;
     f.prev = c->tp_camera;
-    f.have_prev = (c->tp_valid && c->tp_history && c->tp_camera.ok) ? 1u : 0u;
+    f.have_prev = (history && c->tp_camera.ok) ? 1u : 0u;
     f.m = (float)c->frame_count; f.max_history = (float)tp->max_history;
     f.depth_tolerance = tp->depth_tolerance; f.normal_threshold = tp->normal_threshold; f.flags = tp->flags;
     launch_temporal(c->main.stream, whole_image(c), c->tp_depth, c->tp_albedo, c->tp_ids, c->tp_hist[prev], c->tp_guide[prev], c->tp_inst[prev],
                     c->tp_hist[next], c->tp_guide[next], c->tp_inst[next], c->tp_out, f, variance ? c->sv_moments[prev] : nullptr, variance ? c->sv_moments[next] : nullptr,
-                    variance ? c->sv_variance : nullptr, (float)c->svgf.min_history * f.m);
+                    variance ? c->sv_variance : nullptr, (float)c->svgf.min_history * f.m, motion_table, (uint32_t)c->instances.size(), motion ? c->tp_motion : nullptr);
     c->tp_camera = temporal::prev_camera_of(c->P.view_inv, c->P.proj_inv);
-    c->tp_latest = next; c->tp_valid = true; c->tp_history = true; c->sv_valid = variance;
+    c->tp_snapshot.clear();   // the new record was made with the matrices the instances have now
+    c->tp_latest = next; c->tp_valid = true; c->tp_history = true; c->sv_valid = variance; c->tp_motion_valid = motion;
     return VPT_OK;
 }
 
@@ -319,6 +355,33 @@ int read_variance_result(vpt_ctx* c, float* host, bool moments) {
 }  // namespace
 int vpt_get_temporal_variance(vpt_ctx* c, float* var_host) { return read_variance_result(c, var_host, false); }
 int vpt_get_temporal_moments(vpt_ctx* c, float* mu_host) { return read_variance_result(c, mu_host, true); }
+// ---- moved instances: the option, and the motion image of the latest temporal result made with it
+void vpt_default_temporal_options(vpt_temporal_options* o) {
+    if (o) *o = vpt_temporal_options{0u, {0u, 0u, 0u}};
+}
+int vpt_set_temporal_options(vpt_ctx* c, const vpt_temporal_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    if (o->instance_motion > 1u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "instance_motion must be 0 or 1");
+    if (o->reserved[0] | o->reserved[1] | o->reserved[2]) return fail(c, VPT_ERR_INVALID_ARGUMENT, "reserved words must be 0");
+    if (o->instance_motion != c->tp_options.instance_motion) { c->tp_history = false; c->tp_snapshot.clear(); }   // no move was followed while the option was off
+    c->tp_options = *o;
+    return VPT_OK;
+}
+int vpt_get_temporal_options(const vpt_ctx* c, vpt_temporal_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    *o = c->tp_options;
+    return VPT_OK;
+}
+int vpt_get_temporal_motion(vpt_ctx* c, float* motion_host) {
+    if (!c || !motion_host) return VPT_ERR_INVALID_ARGUMENT;
+    if (!(c->tp_options.instance_motion && c->tp_valid && c->tp_motion_valid && c->tp_motion && c->tp_w == c->P.width && c->tp_h == c->P.height))
+        return fail(c, VPT_ERR_INVALID_ARGUMENT, "no temporal result of this size made with vpt_temporal_options.instance_motion == 1");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    { int rd = quiesce(c); if (rd) return rd; }
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    HIPCHK(c, hipMemcpy(motion_host, c->tp_motion, (size_t)c->tp_w * c->tp_h * 8, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
 
 int vpt_set_denoise_source(vpt_ctx* c, uint32_t source) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;

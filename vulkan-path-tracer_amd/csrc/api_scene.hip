@@ -365,6 +365,8 @@ int vpt_set_instance_transforms(vpt_ctx* c, uint32_t first, uint32_t count, cons
     D.scene_extent = vptfp::u2f(words[1]);
     c->bvh_input = std::vector<BvhTri>(); c->lab_trees_stale = true; c->stats.bvh8_nodes = 0;   // (the trace lab's other trees were built from the old triangles)
     c->state_gen++;   // a captured batch holds the old tables' addresses
+    const bool carry = c->tp_options.instance_motion != 0u;   // vpt_set_temporal_options: the history is reprojected through the move
+    if (carry && c->tp_valid && c->tp_history) c->tp_snapshot.note_move(first, count, (uint32_t)c->instances.size(), c->instances[0].xform, sizeof(InstanceDesc));
     for (uint32_t i = 0; i < count; i++) {
         InstanceDesc& d = c->instances[first + i];
         memcpy(d.xform, transforms + (size_t)i * 16, 64);
@@ -378,7 +380,7 @@ int vpt_set_instance_transforms(vpt_ctx* c, uint32_t first, uint32_t count, cons
     if ((rc = upload_emissive(c))) return rc;
     if ((rc = refresh_material_tables(c))) return rc;
     HIPCHK(c, hipGetLastError());
-    reset_accum(c);
+    reset_accum(c, carry);
     c->set_transforms_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return VPT_OK;
 }

@@ -155,8 +155,10 @@ void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, c
 // vpt_temporal_accumulate (temporal.hpp holds the arithmetic): one launch over f.width x f.height.  cur, albedo, out: RGBA32F; depth: one float, ids: k_first_hit's
 // uint4, per pixel.  The previous record (prev_*: never read when f.have_prev is 0) and the new one are (hist F4, guide F4, inst uint32) per pixel; `guide`
 // holds the first-hit normal image on entry and the packed (n.xyz, t) on exit.  variance != nullptr: the luminance moments (two floats per pixel, previous
-// and new) are carried too and the variance image (one float per pixel) is written; min_len = min_history * m.
+// and new) are carried too and the variance image (one float per pixel) is written; min_len = min_history * m.  motion_table != nullptr: motion_count
+// records, one per instance — a hit pixel is reprojected through its instance's; motion != nullptr: the motion image (two floats per pixel) is written.
 void launch_temporal(hipStream_t s, const float* cur, const float* depth, const float* albedo, const uint32_t* ids, const float* prev_hist, const float* prev_guide, const uint32_t* prev_inst,
-                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f, const float* prev_moments, float* moments, float* variance, float min_len);
+                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f, const float* prev_moments, float* moments, float* variance, float min_len,
+                     const temporal::InstanceMotion* motion_table, uint32_t motion_count, float* motion);
 
 }  // namespace vpt

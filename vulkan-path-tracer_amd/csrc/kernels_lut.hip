@@ -8,6 +8,7 @@
 // (same fp32 additions in the same order); long runs are cut into several launches that carry the partial sums
 // in the table, like the reference's command-buffer splits.  Seed_i = PCG(i*2 + sampleCount + PCG(time_ms)): the
 // reference feeds wall-clock milliseconds there, the C-ABI takes the value as an argument so a table is reproducible.
+// Not compiled on its own: kernels_post.hip includes this file at its end (_build.py lists it with the headers).
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"

@@ -634,6 +634,8 @@ struct TpRecords {
     dn::F4* hist; dn::F4* guide; uint32_t* inst;
     // vpt_svgf_options.variance only, otherwise nullptr: the luminance moments of both records and the variance image
     const temporal::M2* prev_moments; temporal::M2* moments; float* variance;
+    // vpt_temporal_options.instance_motion only, otherwise nullptr: one record per instance (only when an instance has moved since the previous record) and the motion image
+    const temporal::InstanceMotion* motion_table; uint32_t motion_count; vptfp::V2* motion;
 };
 struct TpPrevSrc {
     const dn::F4* h; const dn::F4* g; const uint32_t* i; int w; const temporal::M2* m;
@@ -642,10 +644,11 @@ struct TpPrevSrc {
     __device__ __forceinline__ dn::F4 guide(int x, int y) const { return g[(size_t)y * w + x]; }
     __device__ __forceinline__ uint32_t inst(int x, int y) const { return i[(size_t)y * w + x]; }
 };
-// ONE kernel for both settings of vpt_svgf_options.variance, by a run-time branch on rec.variance (a second instantiation was 4.5 KB the library's size
-// bound has no page for, DESIGN.md "Library size"): temporal_pixel_variance has temporal_pixel's statements for image and record, so with the option off the
-// bits are temporal_pixel's (tests/test_gpu_temporal.py holds them to its host compile); the tap's moment record is read beside its two other reads only
-// when there is one, and nothing more is written.
+// ONE kernel for every setting of vpt_svgf_options.variance and vpt_temporal_options.instance_motion, by run-time branches on rec.variance, rec.motion_table
+// and rec.motion (a second instantiation is 4.5 KB the library's size bound has no page for, DESIGN.md "Library size"): temporal_pixel_motion has
+// temporal_pixel_variance's statements, which has temporal_pixel's for image and record, so with the options off the bits are temporal_pixel's
+// (tests/test_gpu_temporal.py holds them to its host compile); the tap's moment record is read beside its two other reads only when there is one.  A pixel of a
+// moved instance gathers its instance's record — seven 16-byte loads neighbouring lanes share — and nothing more is written than the images that are there.
 __global__ __launch_bounds__(256) void k_temporal(const dn::F4* cur, const float* depth, const dn::F4* albedo, const uint4* ids, TpRecords rec, dn::F4* out, temporal::Frame f, float min_len) {
     const int x = blockIdx.x * kTileW + (int)(threadIdx.x & 63u), y = blockIdx.y * kTileH + (int)(threadIdx.x >> 6);
     if (x >= (int)f.width || y >= (int)f.height) return;
@@ -653,20 +656,25 @@ __global__ __launch_bounds__(256) void k_temporal(const dn::F4* cur, const float
     const dn::F4 g = dn::pack_guide(rec.guide[p], depth[p]);
     const uint32_t inst = ids[p].x;
     const TpPrevSrc prev{rec.prev_hist, rec.prev_guide, rec.prev_inst, (int)f.width, rec.prev_moments};
-    const temporal::ResultV rv = temporal::temporal_pixel_variance(prev, f, min_len, x, y, cur[p], g, albedo[p], inst);
+    const temporal::ResultM rm = temporal::temporal_pixel_motion(prev, rec.motion_table, rec.motion_count, f, min_len, x, y, cur[p], g, albedo[p], inst);
+    const temporal::ResultV& rv = rm.v;
     if (rec.variance) {
         rec.moments[p] = rv.moments;
         rec.variance[p] = rv.variance;
     }
+    if (rec.motion) rec.motion[p] = rm.mv;
     out[p] = rv.r.image;
     rec.hist[p] = rv.r.record;
     rec.guide[p] = g;
     rec.inst[p] = inst;
 }
+// motion_table (motion_count records, one per instance) and motion (the motion image, two floats per pixel): vpt_temporal_options.instance_motion only, and
+// the table only when an instance has moved since the previous record; otherwise nullptr.
 void launch_temporal(hipStream_t s, const float* cur, const float* depth, const float* albedo, const uint32_t* ids, const float* prev_hist, const float* prev_guide, const uint32_t* prev_inst,
-                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f, const float* prev_moments, float* moments, float* variance, float min_len) {
+                     float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f, const float* prev_moments, float* moments, float* variance, float min_len,
+                     const temporal::InstanceMotion* motion_table, uint32_t motion_count, float* motion) {
     const TpRecords rec{reinterpret_cast<const dn::F4*>(prev_hist), reinterpret_cast<const dn::F4*>(prev_guide), prev_inst, reinterpret_cast<dn::F4*>(hist), reinterpret_cast<dn::F4*>(guide), inst,
-                        reinterpret_cast<const temporal::M2*>(prev_moments), reinterpret_cast<temporal::M2*>(moments), variance};
+                        reinterpret_cast<const temporal::M2*>(prev_moments), reinterpret_cast<temporal::M2*>(moments), variance, motion_table, motion_count, reinterpret_cast<vptfp::V2*>(motion)};
     hipLaunchKernelGGL(k_temporal, dim3(cdiv_(f.width, kTileW), cdiv_(f.height, kTileH)), dim3(256), 0, s, reinterpret_cast<const dn::F4*>(cur), depth, reinterpret_cast<const dn::F4*>(albedo),
                        reinterpret_cast<const uint4*>(ids), rec, reinterpret_cast<dn::F4*>(out), f, min_len);
 }
@@ -727,3 +735,6 @@ void launch_tonemap(hipStream_t s, const float* hdr, const float* bloom0, uint8_
 }
 
 }  // namespace vpt
+
+// The LUT generator's kernels ride in this translation unit (same flags; one fat binary and its page padding less: DESIGN.md "Library size").
+#include "kernels_lut.hip"

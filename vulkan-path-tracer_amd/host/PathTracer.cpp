@@ -318,5 +318,21 @@ void PathTracer::SetSvgfOptions(const vpt_svgf_options& options) {
     if (!m_Ctx) throw std::runtime_error("SetSvgfOptions before SetScene");
     Check(vpt_set_svgf_options(m_Ctx, &options), "vpt_set_svgf_options");
 }
+void PathTracer::SetTemporalOptions(const vpt_temporal_options& options) {
+    if (!m_Ctx) throw std::runtime_error("SetTemporalOptions before SetScene");
+    Check(vpt_set_temporal_options(m_Ctx, &options), "vpt_set_temporal_options");
+}
+vpt_temporal_options PathTracer::GetTemporalOptions() const {
+    if (!m_Ctx) throw std::runtime_error("GetTemporalOptions before SetScene");
+    vpt_temporal_options o{};
+    Check(vpt_get_temporal_options(m_Ctx, &o), "vpt_get_temporal_options");
+    return o;
+}
+std::vector<float> PathTracer::GetTemporalMotion() {
+    if (!m_Ctx) throw std::runtime_error("GetTemporalMotion before SetScene");
+    std::vector<float> out((size_t)m_Width * m_Height * 2);
+    Check(vpt_get_temporal_motion(m_Ctx, out.data()), "vpt_get_temporal_motion");
+    return out;
+}
 
 }  // namespace vpthost
