@@ -451,6 +451,15 @@ void vpt_default_atmosphere(vpt_atmosphere* out);                       /* PathT
 int vpt_set_atmosphere(vpt_ctx* ctx, const vpt_atmosphere* atmosphere); /* NULL: SetEnableAtmosphere(false). Resets accumulation. */
 /* SetCameraViewInverse / SetCameraProjectionInverse. */
 int vpt_set_camera(vpt_ctx* ctx, const float view_inverse[16], const float projection_inverse[16]);
+/* The pixels a whole-path batch (VPT_PIPELINE_WHOLE) rendered now would start paths for: rect = {x0, y0, x1, y1}, inclusive, in pixels of the whole
+ * image.  No camera ray of a pixel outside it can reach the scene's bounding box (the union of the BVH root's child boxes, projected through the
+ * current camera and grown by two pixels), so such a sample is given its frame sum — exactly zero — without a path; images and vpt_stats are
+ * what they are without the rectangle.  The whole image {0, 0, width - 1, height - 1} wherever that cannot be said: depth of field on, the camera
+ * inside or beside the box, VPT_FLAG_FURNACE, an environment that is shown directly and is not black, a scene whose BVH does not ride in LDS, a
+ * context that counts traversal steps (vpt_config.count_traversal), and a camera so far from the world's origin for its focus_distance (which
+ * counts with depth of field off too: the focus point is rounded to fp32) that the rays' rounding may pass a pixel.
+ * x0 > x1: no pixel can see the scene.  Reads the context only: it waits for nothing.  VPT_ERR_NO_SCENE before the first vpt_set_scene. */
+int vpt_get_whole_cull(const vpt_ctx* ctx, uint32_t rect[4]);
 /* All scalar setters + the #define toggles (PathTracer.cpp:1010-1015, 1623-1716). Resets accumulation — except when
  * max_samples is the only field that changed (SetMaxSamplesAccumulated keeps the image, PathTracer.cpp:1003-1006). */
 int vpt_set_params(vpt_ctx* ctx, const vpt_params* params);

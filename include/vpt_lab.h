@@ -43,14 +43,20 @@ int vpt_lab_set_rays(vpt_ctx* ctx, const vpt_ray* rays_host, uint32_t n);
  *   VPT_LAB_WHOLE_PARTS   a whole-path batch runs as this many equal parts of consecutive frames (1-8; frames / n each, the remainder goes to the first
  *                         ones; no more parts than frames), each part's resolve on the second stream beside the next part's launch.  0, the default: the
  *                         library's rule (path_plan.hpp decide: only batches of the headline's order of size are split).  Captured batches, batches on
- *                         an extra lane and split-screen dispatches always run as one part */
+ *                         an extra lane and split-screen dispatches always run as one part
+ *   VPT_LAB_WHOLE_CULL    0: a whole-path launch starts a path for every sample, also where no camera ray can reach the scene (vpt.h
+ *                         vpt_get_whole_cull then answers the whole image); 1, the default: samples outside that rectangle get their zero without a path */
 #define VPT_LAB_LANES 1u
 #define VPT_LAB_LANE_GRID 2u
 #define VPT_LAB_TAIL_GRID 3u
 #define VPT_LAB_WHOLE_FRAMES 4u
 #define VPT_LAB_WHOLE_SCHED 5u
 #define VPT_LAB_WHOLE_PARTS 6u
+#define VPT_LAB_WHOLE_CULL 7u
 int vpt_lab_set(vpt_ctx* ctx, uint32_t key, uint32_t value);
+/* Samples the latest blocking batch on the main lane (vpt_render) finished without a path because their pixel lies outside vpt_get_whole_cull's
+ * rectangle; 0 for a batch that was not a whole-path batch.  A 32-bit count on the device: batches of the headline's size stay below it. */
+int vpt_lab_whole_culled(const vpt_ctx* ctx, uint64_t* out);
 int vpt_lab_trace(vpt_ctx* ctx, uint32_t variant, uint32_t any_hit, const uint32_t* order_host, uint32_t param, uint32_t reps,
                   vpt_hit* hits_host, float* best_ms, uint64_t* visits);
 

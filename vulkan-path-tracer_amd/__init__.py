@@ -246,6 +246,20 @@ class PathTracer:
             raise VptError("vpt_lab_set: the product library has no laboratory entry points (run with VPT_LAB=1)")
         _check(self.lib, self.ctx, self.lib.vpt_lab_set(self.ctx, key, value), "vpt_lab_set")
 
+    def whole_cull(self):
+        """vpt_get_whole_cull: (x0, y0, x1, y1), inclusive — the pixels a whole-path batch rendered now would start paths for."""
+        r = (C.c_uint32 * 4)()
+        _check(self.lib, self.ctx, self.lib.vpt_get_whole_cull(self.ctx, r), "vpt_get_whole_cull")
+        return tuple(int(v) for v in r)
+
+    def lab_whole_culled(self):
+        """vpt_lab_whole_culled (laboratory build only): samples the latest vpt_render batch finished without a path."""
+        if not self.lib.has_lab:
+            raise VptError("vpt_lab_whole_culled: the product library has no laboratory entry points (run with VPT_LAB=1)")
+        n = C.c_uint64(0)
+        _check(self.lib, self.ctx, self.lib.vpt_lab_whole_culled(self.ctx, C.byref(n)), "vpt_lab_whole_culled")
+        return int(n.value)
+
     def output_device(self):
         """GetOutputImageView(): device pointer of the RGBA8 image (None before the first post-process)."""
         return self.lib.vpt_output_device(self.ctx)

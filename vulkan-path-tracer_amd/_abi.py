@@ -23,7 +23,7 @@ KERNEL_NAMES = ["primary", "extend", "shade", "connect", "bounce", "resolve", "b
 KERNEL_COUNT = 10
 PIPELINE_AUTO, PIPELINE_FUSED, PIPELINE_STAGED = 0, 1, 2
 PIPELINE_STAGED_R1, PIPELINE_STAGED_SORTED, PIPELINE_WHOLE = 3, 4, 5
-LAB_LANES, LAB_LANE_GRID, LAB_TAIL_GRID, LAB_WHOLE_FRAMES, LAB_WHOLE_SCHED, LAB_WHOLE_PARTS = 1, 2, 3, 4, 5, 6
+LAB_LANES, LAB_LANE_GRID, LAB_TAIL_GRID, LAB_WHOLE_FRAMES, LAB_WHOLE_SCHED, LAB_WHOLE_PARTS, LAB_WHOLE_CULL = 1, 2, 3, 4, 5, 6, 7
 ASYNC_MAX_BOUNCES = 32
 
 
@@ -292,6 +292,7 @@ PROTOTYPES = {
     "vpt_set_instance_transforms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "vpt_get_set_transforms_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "vpt_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "vpt_get_whole_cull": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "vpt_default_atmosphere": (None, [C.POINTER(Atmosphere)]),
     "vpt_set_atmosphere": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_add_density_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -353,6 +354,7 @@ PROTOTYPES = {
     "vpt_get_temporal_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_lab_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "vpt_lab_set_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "vpt_lab_whole_culled": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vpt_lab_trace": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
     "vpt_lut_calculate": (C.c_int, [C.c_int] + [C.c_uint32] * 6 + [C.c_void_p]),
 }
@@ -361,7 +363,7 @@ PROTOTYPES = {
 COMM_ID_BYTES = 128
 
 
-LAB_ENTRY_POINTS = ("vpt_lab_set", "vpt_lab_set_rays", "vpt_lab_trace")   # include/vpt_lab.h: exported by the laboratory build only
+LAB_ENTRY_POINTS = ("vpt_lab_set", "vpt_lab_set_rays", "vpt_lab_trace", "vpt_lab_whole_culled")   # include/vpt_lab.h: exported by the laboratory build only
 
 
 def bind(lib):

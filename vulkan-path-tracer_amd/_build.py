@@ -18,7 +18,7 @@ SOURCES = ["kernels_whole.hip", "kernels_finish.hip", "kernels_bounce.hip", "ker
 LAB_SOURCES = ["kernels_lab_r1.hip", "api_lab.hip"]   # compiled and linked into the laboratory library only
 # (kernels_lut.hip is a header here: kernels_post.hip includes it — the two share their flags, and one fat binary with its page padding less is 10 KB of the
 # product's size bound, DESIGN.md "Library size")
-HEADERS = ["kernels_lut.hip", "device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "grid_prep.hpp", "denoise.hpp", "temporal.hpp", "kernels.hpp", "api_ctx.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "bvh_refit.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp", "whole_refill.hpp", "whole_args.hpp", "camera.hpp",
+HEADERS = ["kernels_lut.hip", "device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "grid_prep.hpp", "denoise.hpp", "temporal.hpp", "kernels.hpp", "api_ctx.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "bvh_refit.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp", "whole_refill.hpp", "whole_args.hpp", "camera.hpp", "camera_cull.hpp",
            os.path.join("..", "..", "include", "vpt.h"), os.path.join("..", "..", "include", "vpt_lab.h"), os.path.join("..", "..", "include", "vpt_fp32.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-result", "-Wno-pass-failed"]
@@ -32,6 +32,10 @@ EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("kernels_trace.hip", "kernels
 EXTRA_FLAGS.update({f: ["-Os"] for f in ("api_context.hip", "api_scene.hip", "api_render.hip", "api_post.hip", "api_comm.hip")})
 # The host BVH builder at -O2 (the later -O wins): 7 KB less of unrolled and vectorised loops; its time is what vpt_stats.bvh_build_ms reports.
 EXTRA_FLAGS["bvh_build.cpp"] = ["-O2"]
+# The post chain's launch wrappers (13 KB of host code in a kernel file, a handful of calls per vpt_postprocess) for size too, on the HOST pass alone:
+# -Xarch_host keeps the flag from the device pass, so the kernels are compiled as before.  4.4 KB, which the camera cull's host code (camera_cull.hpp,
+# 3 KB) needed under the size bound.
+EXTRA_FLAGS["kernels_post.hip"] = ["-Xarch_host", "-Os"]
 
 
 def hipcc():

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "camera_cull.hpp"
 #include "kernels.hpp"
 #include "path_plan.hpp"
 #include "scene_prep.hpp"   // scene::EmissiveList, a member of the context (the functions: api_scene.hip only)
@@ -153,6 +154,10 @@ struct vpt_ctx {
                                                // (Cornell box 1080p, Msamples/s whole vs per-bounce at 1 / 4 / 16 / 64 / 226 frames per batch: 3821 / 6413 / 7737 / 8183 / 8315 vs
                                                // 2401 / 4753 / 6493 / 7244 / 7359; general instantiation 8840 vs 7713: profiles/r04_whole_ab.json)
     uint32_t lab_whole_parts = 0;    // != 0: whole-path batches run as this many equal parts (VPT_LAB_WHOLE_PARTS); 0: path_plan.hpp's rule
+    // The scene's box as the device tree holds it — the union of the root's used child boxes in nodes_wide — from vpt_set_scene, and from the refitted
+    // root after vpt_set_instance_transforms: what camera_cull.hpp bounds on the screen for every whole-path batch (whole_cull_rect).
+    cull::WorldBox whole_box{};
+    bool lab_whole_cull = true;      // false: whole-path batches skip no sample (VPT_LAB_WHOLE_CULL 0)
     bool depth_bounded = true;   // every path ends within max_depth * samples_per_frame bounces (no material scatters inside a medium): see vpt_render_async
     // asynchronous batches (vpt_render_async / vpt_postprocess_device / vpt_wait)
     hipEvent_t tick_ev[kTickets] = {};
@@ -324,6 +329,7 @@ int upload(vpt_ctx* c, const std::vector<T>& v, const T** out, size_t min_elems 
 
 // api_render.hip
 DeviceScene lane_scene(const vpt_ctx* c, const Lane& L);
+cull::Rect whole_cull_rect(const vpt_ctx* c);   // the pixels outside which the next whole-path batch starts no path (camera_cull.hpp)
 uint64_t issue_ticket(vpt_ctx* c, hipStream_t on);
 int finish_outstanding(vpt_ctx* c);
 int drain(vpt_ctx* c);

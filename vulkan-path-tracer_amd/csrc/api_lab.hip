@@ -16,8 +16,14 @@ int vpt_lab_set(vpt_ctx* c, uint32_t key, uint32_t value) {
     else if (key == VPT_LAB_WHOLE_SCHED && (value & 15u) >= 1u && (value >> 4) <= 3u) c->lab_whole_sched = value;
     else if (key == VPT_LAB_WHOLE_FRAMES) c->lab_whole_frames = value == 0xffffu ? 0xffffffffu : value;   // (0xffff: no bound, the default)
     else if (key == VPT_LAB_WHOLE_PARTS && value <= plan::kMaxParts) c->lab_whole_parts = value;
+    else if (key == VPT_LAB_WHOLE_CULL && value <= 1u) c->lab_whole_cull = value != 0u;
     else return VPT_ERR_INVALID_ARGUMENT;
     c->state_gen++;   // captured batches hold the old grids
+    return VPT_OK;
+}
+int vpt_lab_whole_culled(const vpt_ctx* c, uint64_t* out) {
+    if (!c || !out) return VPT_ERR_INVALID_ARGUMENT;
+    *out = c->main.h_ctr ? c->main.h_ctr->ctr.whole_culled : 0u;   // (the counters a batch copies to pinned memory behind its resolve: batch_resolve)
     return VPT_OK;
 }
 int vpt_lab_set_rays(vpt_ctx* c, const vpt_ray* rays, uint32_t n) {

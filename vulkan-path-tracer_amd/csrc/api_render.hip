@@ -77,6 +77,7 @@ int batch_begin(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, 
     const DeviceScene dsc = lane_scene(c, L);
     if (sd.kind == Kind::Whole) {  // the batch's paths from camera ray to their end, one launch per part; no queue is written, alive3[] stays 0 for the resolve's guard
         b.parity = 1; b.k3 = 1; b.iter = 1;
+        const cull::Packed rect = cull::pack(whole_cull_rect(c));   // samples outside it start no path (camera_cull.hpp); the same for every part
         for (uint32_t i = 0; i < sd.parts.n; i++) {
             const uint32_t first = sd.parts.first[i], n_part = sd.parts.n > 1u ? (sd.parts.first[i + 1] - first) * c->P.shard_pixels : n_slots;
             const uint32_t grid = std::max(1u, std::min<uint32_t>((uint32_t)std::min(c->whole_blocks, b.primary_grid), (n_part + 255u) / 256u));   // (blocks of 256 lanes)
@@ -85,7 +86,7 @@ int batch_begin(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, 
             const uint32_t static_rounds = (mode == 0u || mode == 3u) ? std::min(rounds, 1u) : mode == 1u ? (rounds >= 2u ? rounds - 1u : 0u) : rounds / 2u;
             // (mode 3: mode 0 with guided chunks — at most the given tiles per atomic, fewer towards the end of the batch)
             if (i) HIPCHK(c, hipMemsetAsync(&L.ctr->extend_head, 0, 4, s));   // the tile cursor starts at 0 in every part
-            TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, part_state(c, L, first), L.ctr, n_part, dispatch_base + first, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u)));
+            TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, part_state(c, L, first), L.ctr, n_part, dispatch_base + first, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u), rect.x, rect.y));
             if (i + 1u < sd.parts.n) {   // this part's resolve on the second stream, beside the next part's launch (the last part's: batch_resolve)
                 HIPCHK(c, hipEventRecord(L.ev_shade, s));
                 HIPCHK(c, hipStreamWaitEvent(L.stream2, L.ev_shade, 0));
@@ -397,6 +398,11 @@ DeviceScene lane_scene(const vpt_ctx* c, const Lane& L) {
     d.stack_overflow = L.spill;
     return d;
 }
+cull::Rect whole_cull_rect(const vpt_ctx* c) {
+    cull::WorldBox box = c->whole_box;
+    box.valid = box.valid && c->has_scene && c->lab_whole_cull && c->cfg.count_traversal == 0;   // (k_whole's counting instantiations have no test: kernels_whole.hip)
+    return cull::screen_bound(c->P.view_inv, c->P.proj_inv, c->P.width, c->P.height, c->P.focus_distance, c->P.dof_strength, c->P.flags, c->dsc.env_black != 0u, box);
+}
 
 // ---- asynchronous batches: tickets, and what waits for them
 // The ticket of everything enqueued up to here; `on`: the stream the latest of it went to (vpt_wait).
@@ -642,6 +648,14 @@ int vpt_reset_stats(vpt_ctx* c) {
     c->stats = vpt_stats{};
     for (int k = 0; k < kLanes; k++)
         if (Lane* L = c->lane(k)) { HIPCHK(c, memset_now(L->stream, L->ctr, 0, sizeof(Counters))); memset(L->h_ctr, 0, sizeof(HostCounters)); }
+    return VPT_OK;
+}
+
+int vpt_get_whole_cull(const vpt_ctx* c, uint32_t* rect) {
+    if (!c || !rect) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c->has_scene) return VPT_ERR_NO_SCENE;
+    const cull::Rect r = whole_cull_rect(c);
+    rect[0] = r.x0; rect[1] = r.y0; rect[2] = r.x1; rect[3] = r.y1;
     return VPT_OK;
 }
 

@@ -78,6 +78,18 @@ int update_class_present(vpt_ctx* c) {
     return VPT_OK;
 }
 
+// The box camera_cull.hpp bounds on the screen: the union of the root's used child boxes as nodes_wide holds them (padded fp32).
+cull::WorldBox root_box(const BvhNodeWide& n) {
+    cull::WorldBox b{{3.0e38f, 3.0e38f, 3.0e38f}, {-3.0e38f, -3.0e38f, -3.0e38f}, false};
+    for (int k = 0; k < 4; k++)
+        if (refit::slot_used(n, k)) {
+            const float* f = n.minx;   // minx, miny, minz, maxx, maxy, maxz: four floats each, back to back
+            for (int a = 0; a < 3; a++) { b.lo[a] = std::min(b.lo[a], f[a * 4 + k]); b.hi[a] = std::max(b.hi[a], f[12 + a * 4 + k]); }
+            b.valid = true;
+        }
+    return b;
+}
+
 // The tree build_bvh makes of a prepared scene's triangles.
 struct SceneBvh {
     std::vector<BvhNode> nodes; std::vector<BvhNodeWide> wide; std::vector<BvhTri> leaf_tris; int depth = 0;
@@ -107,6 +119,7 @@ int upload_scene(vpt_ctx* c, const vpt_scene_desc& sd, scene::HostScene& hs, con
     vpt_ctx::Writable& W = c->dw;
     int rc;
     c->lds_scene = scene::rides_in_lds(bvh.nodes.size(), bvh.leaf_tris.size());
+    c->whole_box = c->lds_scene && !bvh.wide.empty() ? root_box(bvh.wide[0]) : cull::WorldBox{};
     c->bvh_depth = (uint32_t)bvh.depth;
     D.nodes_wide = nullptr; D.nodes8 = nullptr; D.nodes4s = nullptr;
     if ((rc = upload(c, bvh.nodes, &D.nodes))) return rc;
@@ -338,6 +351,7 @@ int vpt_set_instance_transforms(vpt_ctx* c, uint32_t first, uint32_t count, cons
     if (!rc) rc = alloc_table(c, D.node_count, &nodes, &w_nodes);
     if (!rc && D.nodes_wide) rc = alloc_table(c, D.node_count, &wide, &w_wide);
     uint32_t words[2] = {0u, 0u};
+    cull::WorldBox box{};   // of the refitted tree: the root's entry of the refit, padded as put_boxes pads its children (read behind the wait the refit ends with anyway)
     auto staged = [&]() -> int {
         HIPCHK(c, hipMalloc((void**)&scratch, scratch_bytes));
         HIPCHK(c, hipMemsetAsync(scratch, 0, 256, s));
@@ -351,6 +365,11 @@ int vpt_set_instance_transforms(vpt_ctx* c, uint32_t first, uint32_t count, cons
             launch_refit_level(s, D, c->refit_order, c->refit_level_off[h], c->refit_level_off[h + 1], w_tris, pad, (float*)(scratch + 256 + xf_bytes), w_nodes, w_wide);
         HIPCHK(c, hipStreamSynchronize(s));
         HIPCHK(c, hipGetLastError());
+        if (w_wide) {
+            HIPCHK(c, hipMemcpy(box.lo, scratch + 256 + xf_bytes, 24, hipMemcpyDeviceToHost));   // (lo and hi lie back to back, in the struct as in the entry)
+            box.valid = box.lo[0] <= box.hi[0];
+            for (int a = 0; a < 3; a++) { box.lo[a] -= pad; box.hi[a] += pad; }
+        }
         return VPT_OK;
     };
     if (!rc) rc = staged();
@@ -363,6 +382,7 @@ int vpt_set_instance_transforms(vpt_ctx* c, uint32_t first, uint32_t count, cons
     release_tables(c, {D.tris, D.nodes, D.nodes_wide, D.nodes8, D.nodes4s});
     D.tris = tris; D.nodes = nodes; D.nodes_wide = wide; D.nodes8 = nullptr; D.nodes4s = nullptr;
     D.scene_extent = vptfp::u2f(words[1]);
+    c->whole_box = box;
     c->bvh_input = std::vector<BvhTri>(); c->lab_trees_stale = true; c->stats.bvh8_nodes = 0;   // (the trace lab's other trees were built from the old triangles)
     c->state_gen++;   // a captured batch holds the old tables' addresses
     const bool carry = c->tp_options.instance_motion != 0u;   // vpt_set_temporal_options: the history is reprojected through the move

@@ -332,7 +332,7 @@ struct Counters {
     uint32_t connect_back;    //                emission/finalize-only entries from the back
     uint32_t extend_head, connect_head;  // persistent-kernel work cursors
     uint32_t shadow_rays;     // shadow rays queued by shade this bounce
-    uint32_t pad;
+    uint32_t whole_culled;    // whole-path launches of the laboratory build: samples of this batch that were finished without a path (camera_cull.hpp)
     // fused pipeline: three rotating queue sizes — bounce k reads rc3[k % 3], appends to rc3[(k + 1) % 3] and zeroes
     // rc3[(k + 2) % 3] (idle during bounce k), so no separate reset kernel sits between two bounces
     uint32_t rc3[4];          // dynamically reserved part of the three rotating queues' lengths

@@ -8,6 +8,7 @@
 #include "shade_core.hpp"
 #include "whole_refill.hpp"
 #include "whole_args.hpp"
+#include "camera_cull.hpp"
 
 namespace vpt {
 
@@ -21,6 +22,9 @@ template <> struct OneSampleFrames<VPT_KERNARG WholeParams> { static constexpr b
 // batch, so a launch runs until the batch's samples are used up and no path record, queue or counter crosses HBM in between —
 // only the per-sample frame sums (ACC) do.  One launch per batch (or part of one) instead of max_depth: what a 1-frame batch at 1080p needs (its
 // later bounces are launches of 10^5 paths that do not fill the chip, vpt_render_async).
+// A sample whose pixel lies outside the launch's screen rectangle of the scene's box (camera_cull.hpp; the host bounds the box per batch:
+// api_render.hip batch_begin) never becomes a path: its camera ray could only miss, so the refill step writes its zero frame sum and counts
+// its one ray (53.8 % of the samples of Cornell 1080p: profiles/r18_whole_camera_cull_ab.md).
 // A wave alternates two steps, each on full lanes:
 //   trace   every lane holds a ray — a survivor of the shade step or a fresh camera ray — and finds its closest hit; misses run the
 //           miss shader and end there, hits are parked in a wave-private ring in LDS (hit record + the path's registers);
@@ -39,7 +43,8 @@ __device__ __forceinline__ V3 whole_finish(const Pm& P, const Ps& ps, uint32_t s
 // (Measured and not kept: one-wave blocks, which leave the CU as soon as THEIR paths have ended and so let the next frame's launch in earlier —
 // a 1-frame launch at 1080p 542 us against 509 us, and slower with two or three frames in flight too: profiles/r04_whole_lanes.json.)
 template <bool COUNT, bool STRICT, bool PLAIN>
-__global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeArgs a) {   // (ONE parameter: the argument segment is a WholeArgs)
+__global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {   // (ONE parameter: the argument segment is a WholeLaunch, a WholeArgs at its start)
+    const WholeArgs& a = wl.a;
     // what runs once, before the loop, reads the arguments as any kernel does
     const DeviceScene sc = a.sc;
     const RenderParams P = a.P;
@@ -79,6 +84,9 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeArgs a) {   //
     uint32_t hit_head = 0u, hit_count = 0u;   // wave-uniform
     TravStats st, sst; st.nodes = 0; st.tris = 0; sst.nodes = 0; sst.tris = 0;
     uint32_t w_paths = 0u, w_rays = 0u, w_hits0 = 0u, w_alive0 = 0u, w_rays0 = 0u, w_parked = 0u;   // wave totals (uniform); *0: bounce 0 only; parked: hits of later bounces (their pathLight waits in ACC)
+#if VPT_LAB
+    uint32_t w_culled = 0u;   // samples the refill step finished without a path (the laboratory reports them: vpt_lab_whole_culled)
+#endif
     // the lane's path between two steps
     bool has_ray = false;
     uint32_t slot = 0u, rng_s = 0u, depth = 0u;
@@ -146,11 +154,15 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeArgs a) {   //
             w_rays0 += (uint32_t)__popcll(__ballot(first && nrays >= 1u)) + (uint32_t)__popcll(__ballot(first && nrays >= 2u));
             w_alive0 += (uint32_t)__popcll(__ballot(first && alive));
         }
-        // ---- refill: free lanes take the next unstarted samples from the front of the wave's buffer; when it runs out, ALL lanes generate the next
-        // tile of camera rays into it (a second pass when the buffer ran out half-way)
+        // ---- refill: free lanes take the next unstarted samples from the front of the wave's buffer; when it runs out, ALL lanes take the next
+        // tile of launch indices.  A sample whose pixel lies outside the launch's rectangle (camera_cull.hpp: no camera ray of that pixel reaches the
+        // scene's box) ends where it stands — its frame sum is exactly zero, and it counts as the one closest-hit ray its path would have been;
+        // the others get their camera rays, compacted into the buffer by a ballot.  The wave goes on taking tiles until its free lanes are
+        // served or it is out of samples: a run of background tiles sends no trace step out with idle lanes.  (Per-lane test and ballot, not a
+        // decomposition of the tile against the rectangle: profiles/REJECTED.md r11, r16.)
         if (!refill::exhausted(cur, fresh)) {
 #pragma unroll 1
-            for (int pass = 0; pass < 2; pass++) {
+            for (;;) {
                 const unsigned long long m_free = __ballot(!has_ray);
                 if (m_free == 0ull) break;
                 if (fresh.count == 0u) {
@@ -162,23 +174,43 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeArgs a) {   //
                     }
                     if (refill::exhausted(cur, fresh)) break;
                     const uint32_t g = refill::gen_count(cur);
-                    if (lane_id() < g) {
-                        uint32_t gslot, x, y, f;
-                        const uint32_t dispatch_base = uP.dispatch_base_dev ? *uP.dispatch_base_dev : ka->dispatch_base;   // (a replayed graph: the batch's first dispatch index lives in device memory)
+                    const uint32_t dispatch_base = uP.dispatch_base_dev ? *uP.dispatch_base_dev : ka->dispatch_base;   // (a replayed graph: the batch's first dispatch index lives in device memory)
+                    uint32_t gslot = 0u, x = 0u, y = 0u, f = 0u;
+                    // (a launch without a rectangle pays nothing for the test: `bounded` comes from two argument words, a scalar branch)
+                    const VPT_KERNARG WholeLaunch* kl = (const VPT_KERNARG WholeLaunch*)ka;
+                    const cull::Packed rect{kl->cull_x, kl->cull_y};
+                    // The counting instantiations have no test at all — the library's size bound (tests/test_abi.py) has no room for it five times — and the
+                    // host gives their launches no rectangle (api_render.hip whole_cull_rect): their figures are those of the search itself.
+                    const bool bounded = !COUNT && (rect.x != cull::kAxisAll || rect.y != cull::kAxisAll);
+                    bool keep = lane_id() < g;
+                    if (keep) {
                         launch_pixel(uP, cur.w_next + lane_id(), dispatch_base, gslot, x, y, f);
+                        if (bounded && cull::outside(rect, x, y)) {
+                            keep = false;
+                            ups.ACC[gslot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        }
+                    }
+                    const unsigned long long m_keep = bounded ? __ballot(keep) : ~0ull >> (64u - g);   // (g >= 1: the range is not empty)
+                    if (keep) {
                         const uint32_t seed = pcg_hash(uP.base_seed + dispatch_base + f);  // PathTracer.cpp:139 with an explicit seed
                         Rng r; r.s = y + uP.width * x + seed;                              // RayGen.slang:28
                         V3 go, gd;
                         camera_ray(cam, r, x, y, go, gd);
-                        const uint32_t j = lane_id();
+                        const uint32_t j = bounded ? lanes_below(m_keep) : lane_id();
                         f_slot[wave][j] = gslot; f_rng[wave][j] = r.s;
                         f_ox[wave][j] = go.x; f_oy[wave][j] = go.y; f_oz[wave][j] = go.z;
                         f_dx[wave][j] = gd.x; f_dy[wave][j] = gd.y; f_dz[wave][j] = gd.z;
                     }
-                    refill::generated(cur, fresh, g);
+                    const uint32_t kept = (uint32_t)__popcll(m_keep);
+                    w_paths += g - kept;
+#if VPT_LAB
+                    w_culled += g - kept;
+#endif
+                    refill::generated_kept(cur, fresh, g, kept);
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    if (kept == 0u) continue;   // a tile of background: the next one
                 }
                 const uint32_t q = fresh.head + lanes_below(m_free);
                 refill::pop(fresh, (uint32_t)__popcll(m_free));
@@ -237,6 +269,9 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeArgs a) {   //
         if (w_alive0) atomicAdd(&ctr->stat_primary_alive, (unsigned long long)w_alive0);
         if (w_rays0) atomicAdd(&ctr->stat_primary_rays, (unsigned long long)w_rays0);
         if (w_parked) atomicAdd(&ctr->stat_connect, (unsigned long long)w_parked);   // vpt_stats.connect_paths: here, the hits whose pathLight made the round trip through ACC
+#if VPT_LAB
+        if (w_culled) atomicAdd(&ctr->whole_culled, w_culled);
+#endif
     }
     if (COUNT) {
         atomicAdd(&ctr->stat_nodes, (unsigned long long)st.nodes);
@@ -248,15 +283,15 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeArgs a) {   //
 
 // Whole paths in one launch (k_whole): LDS-resident scenes without media, one sample per pixel and frame.
 void launch_whole(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, Counters* ctr, uint32_t n_slots,
-                  uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles) {
+                  uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles, uint32_t cull_x, uint32_t cull_y) {
     const size_t lds = traverse_lds_bytes(sc, true, kWholeStackRows);
     const dim3 g(blocks), b(kTraverseBlock);
     // one launch site for the five instantiations (the argument marshalling is host code the library's size bound pays for five times otherwise)
-    void (*k)(WholeArgs);
+    void (*k)(WholeLaunch);
     if (plain && !count && !sc.strict_hits && sc.env_black) k = k_whole<false, false, true>;
     else if (sc.strict_hits) k = count ? k_whole<true, true, false> : k_whole<false, true, false>;
     else k = count ? k_whole<true, false, false> : k_whole<false, false, false>;
-    hipLaunchKernelGGL(k, g, b, lds, s, WholeArgs{sc, P, ps, ctr, n_slots, dispatch_base, static_rounds, chunk_tiles});
+    hipLaunchKernelGGL(k, g, b, lds, s, WholeLaunch{WholeArgs{sc, P, ps, ctr, n_slots, dispatch_base, static_rounds, chunk_tiles}, cull_x, cull_y});
 }
 int whole_blocks_per_cu(const DeviceScene& sc, bool plain) {
     int nb = 0;

@@ -11,6 +11,8 @@
 // DeviceScene in memory is read as a WholeScene.
 // Compiled for the device and — by tests/tools/whole_uniforms_driver.cpp — for the host (tests/test_whole_uniforms_cpu.py).
 #pragma once
+#include <stddef.h>
+
 #include "device_types.hpp"
 
 namespace vpt {
@@ -23,6 +25,15 @@ struct WholeArgs {
     uint32_t n_slots, dispatch_base;
     uint32_t static_rounds, chunk_tiles;
 };
+
+// What a launch hands over: the arguments, and behind them the rectangle of the image outside which no camera ray can reach the scene, as
+// camera_cull.hpp packs it (cull::Packed; both words cull::kAxisAll: every sample runs).  The kernel's one parameter is this struct, so a
+// WholeArgs still lies at offset 0 of the argument segment.
+struct WholeLaunch {
+    WholeArgs a;
+    uint32_t cull_x, cull_y;
+};
+static_assert(offsetof(WholeLaunch, a) == 0, "the loop reads the argument segment as a WholeArgs");
 
 template <bool STRICT, bool PLAIN>
 struct WholeScene : DeviceScene {
