@@ -32,7 +32,9 @@ EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("kernels_trace.hip", "kernels
 EXTRA_FLAGS.update({f: ["-Os"] for f in ("api_context.hip", "api_scene.hip", "api_render.hip", "api_post.hip", "api_comm.hip")})
 # The host BVH builder at -O2 (the later -O wins): 7 KB less of unrolled and vectorised loops; its time is what vpt_stats.bvh_build_ms reports.
 EXTRA_FLAGS["bvh_build.cpp"] = ["-O2"]
-# The post chain's launch wrappers (13 KB of host code in a kernel file, a handful of calls per vpt_postprocess) for size too, on the HOST pass alone:
+# The post chain's launch wrappers (host code in a kernel file, 13 KB of it when this flag was taken, a handful of calls per vpt_postprocess; like every
+# launch_* wrapper they pick a kernel's instantiation as a pointer and launch ONCE, each launch site being argument marshalling the size bound pays for:
+# DESIGN.md §9) for size too, on the HOST pass alone:
 # -Xarch_host keeps the flag from the device pass, so the kernels are compiled as before.  4.4 KB, which the camera cull's host code (camera_cull.hpp,
 # 3 KB) needed under the size bound.
 EXTRA_FLAGS["kernels_post.hip"] = ["-Xarch_host", "-Os"]

@@ -43,13 +43,8 @@ void free_render_buffers(vpt_ctx* c) {
     c->mips.clear(); c->mip_sizes.clear();
     if (c->post_out) (void)hipFree(c->post_out);
     c->post_out = nullptr; c->post_w = c->post_h = 0;
-    if (c->dn_block) (void)hipFree(c->dn_block);   // the denoiser's images: re-made by the next vpt_denoise*, whose result is gone with them
-    c->dn_block = nullptr; c->dn_w = c->dn_h = 0; c->dn_valid = false;
-    if (c->tp_block) (void)hipFree(c->tp_block);   // the temporal records and result: gone with the size they were made for
-    c->tp_block = nullptr; c->tp_w = c->tp_h = 0; c->tp_valid = c->tp_history = false;
-    if (c->sv_block) (void)hipFree(c->sv_block);   // ... and the luminance moments that went with them
-    c->sv_block = nullptr; c->sv_valid = false;
-    free_motion_buffers(c);
+    free_denoise_buffers(c);
+    free_temporal_buffers(c);
 }
 
 // Size checks of a (width, height) before anything is freed or changed; *frames_out = the largest batch this context will render.
@@ -371,7 +366,18 @@ int ensure_legacy_buffers(vpt_ctx* c, Lane& L) {
 }
 
 void reset_accum(vpt_ctx* c, bool keep_history) { c->frame_count = 0; c->dispatch_count = 0; c->samples_accum = 0; if (!keep_history) { c->tp_history = false; c->tp_snapshot.clear(); } }  // PathTracer.h:183
-void free_motion_buffers(vpt_ctx* c) {
+// The denoiser's images: re-made by the next vpt_denoise*, whose result is gone with them.
+void free_denoise_buffers(vpt_ctx* c) {
+    if (c->dn_block) (void)hipFree(c->dn_block);
+    c->dn_block = nullptr; c->dn_w = c->dn_h = 0; c->dn_valid = false;
+}
+// The temporal records and result, gone with the size they were made for, and what was allocated beside them for that size: the luminance moments
+// (vpt_svgf_options.variance), the motion image and the per-instance tables (vpt_temporal_options.instance_motion).
+void free_temporal_buffers(vpt_ctx* c) {
+    if (c->tp_block) (void)hipFree(c->tp_block);
+    c->tp_block = nullptr; c->tp_w = c->tp_h = 0; c->tp_valid = c->tp_history = false;
+    if (c->sv_block) (void)hipFree(c->sv_block);
+    c->sv_block = nullptr; c->sv_valid = false;
     if (c->tp_motion) (void)hipFree(c->tp_motion);
     for (int k = 0; k < 2; k++) { if (c->tp_motion_table[k]) (void)hipFree(c->tp_motion_table[k]); c->tp_motion_table[k] = nullptr; }
     c->tp_motion = nullptr; c->tp_motion_cap = 0; c->tp_motion_valid = false;

@@ -3,7 +3,7 @@
 //   api_context.hip  the context's life: create, size, configure, tear down; lanes, path buffers, the timing pool
 //   api_scene.hip    what a batch only reads: scene installation and its partial updates
 //   api_render.hip   a batch from decision to resolve; asynchronous batches, tickets, statistics
-//   api_post.hip     the post-process schedule
+//   api_post.hip     the image passes behind a render: post-process (bloom, tonemap, RGBA8), denoise, temporal accumulation with SVGF's variance and instance motion
 //   api_comm.hip     shards and gathers (the only file that sees RCCL)
 //   api_lab.hip      the vpt_lab_* entry points (laboratory library only)
 // None of them defines a __global__ function or launches one directly: the host layer calls the launch_* wrappers of kernels.hpp only.  That is
@@ -289,7 +289,8 @@ int ensure_legacy_buffers(vpt_ctx* c, Lane& L);
 // The accumulation starts afresh (PathTracer.h:183).  keep_history: the caller changed nothing a pixel's history depends on but the camera, which
 // vpt_temporal_accumulate reprojects through (vpt_set_camera, vpt_reset); every other caller drops the temporal history with the accumulation.
 void reset_accum(vpt_ctx* c, bool keep_history = false);
-void free_motion_buffers(vpt_ctx* c);   // the motion image and tables of vpt_temporal_options.instance_motion: wherever tp_block goes
+void free_denoise_buffers(vpt_ctx* c);    // dn_block and the result in it
+void free_temporal_buffers(vpt_ctx* c);   // tp_block with its result and history, and what goes wherever it goes: sv_block, the motion image and tables
 int alloc_spill(vpt_ctx* c, Lane& L, int regions);
 Lane* get_lane(vpt_ctx* c, int k);
 int ensure_lane_buffers(vpt_ctx* c, Lane& L);

@@ -1,4 +1,8 @@
-// api_post.hip — the post-process schedule (bloom chain + tonemap, kernels_post.hip) and the RGBA8 output.
+// api_post.hip — the image passes that run behind a render, each as a blocking entry and a _device entry queued behind the frames in flight:
+//   vpt_postprocess           the bloom chain + tonemap schedule (kernels_post.hip) and the RGBA8 output
+//   vpt_denoise               the edge-avoiding a-trous filter over first-hit guides, variance-guided with vpt_svgf_options.variance
+//   vpt_temporal_accumulate   the image carried across camera and instance moves: the two records, SVGF's luminance moments and variance, the per-instance
+//                             motion tables and the motion image, with their options and read-backs
 #include "api_ctx.hpp"
 
 using namespace vpt::api;
@@ -97,6 +101,9 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
     }
     return VPT_OK;
 }
+// A temporal result / a denoised image of the current size exists: not before the first call, and not after a resize.
+bool temporal_ready(const vpt_ctx* c) { return c->tp_valid && c->tp_w == c->P.width && c->tp_h == c->P.height; }
+bool denoised_ready(const vpt_ctx* c) { return c->dn_valid && c->dn_w == c->P.width && c->dn_h == c->P.height; }
 int post_preconditions(vpt_ctx* c) {
     if (!c->buffers_ok) return fail(c, VPT_ERR_DEVICE, "no render buffers: the last vpt_resize failed");
     if (c->P.shard_count > 1 && !c->full_valid) return fail(c, VPT_ERR_INVALID_ARGUMENT, "sharded context: call vpt_assemble_shards first");
@@ -104,7 +111,7 @@ int post_preconditions(vpt_ctx* c) {
 }
 // VPT_POST_SOURCE_DENOISED needs a denoised image of the current size: never denoised, or resized since, is the caller's error.
 int post_source_ready(vpt_ctx* c) {
-    if (c->post_source == VPT_POST_SOURCE_DENOISED && !(c->dn_valid && c->dn_w == c->P.width && c->dn_h == c->P.height))
+    if (c->post_source == VPT_POST_SOURCE_DENOISED && !denoised_ready(c))
         return fail(c, VPT_ERR_INVALID_ARGUMENT, "post source is the denoised image and there is none of this size: call vpt_denoise first");
     return VPT_OK;
 }
@@ -117,7 +124,7 @@ int check_denoise(vpt_ctx* c, const vpt_denoise_params* dp, const void* device_o
     if (dp->flags & ~VPT_DENOISE_DEMODULATE) return fail(c, VPT_ERR_INVALID_ARGUMENT, "unknown denoise flag bits");
     if (((uintptr_t)device_out & 15u) != 0u) return fail(c, VPT_ERR_INVALID_ARGUMENT, "the device image must be 16-byte aligned");
     if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
-    if (c->denoise_source == VPT_DENOISE_SOURCE_TEMPORAL && !(c->tp_valid && c->tp_w == c->P.width && c->tp_h == c->P.height))
+    if (c->denoise_source == VPT_DENOISE_SOURCE_TEMPORAL && !temporal_ready(c))
         return fail(c, VPT_ERR_INVALID_ARGUMENT, "denoise source is the temporal image and there is none of this size: call vpt_temporal_accumulate first");
     if (c->denoise_source == VPT_DENOISE_SOURCE_TEMPORAL && c->svgf.variance && !c->sv_valid)
         return fail(c, VPT_ERR_INVALID_ARGUMENT, "the variance-guided filter needs a temporal result made with vpt_svgf_options.variance == 1");
@@ -126,8 +133,7 @@ int check_denoise(vpt_ctx* c, const vpt_denoise_params* dp, const void* device_o
 int ensure_denoise_buffers(vpt_ctx* c) {
     const uint32_t w = c->P.width, h = c->P.height;
     if (c->dn_block && c->dn_w == w && c->dn_h == h) return VPT_OK;
-    if (c->dn_block) (void)hipFree(c->dn_block);
-    c->dn_block = nullptr; c->dn_valid = false; c->dn_w = c->dn_h = 0;
+    free_denoise_buffers(c);
     const size_t npx = (size_t)w * h;
     HIPCHK(c, hipMalloc((void**)&c->dn_block, npx * (5 * 16 + 4)));   // five RGBA32F images, then the depths: every image 16-byte aligned
     float* p = c->dn_block;
@@ -184,11 +190,7 @@ int check_temporal(vpt_ctx* c, const vpt_temporal_params* tp, const void* device
 int ensure_temporal_buffers(vpt_ctx* c) {
     const uint32_t w = c->P.width, h = c->P.height;
     if (c->tp_block && c->tp_w == w && c->tp_h == h) return VPT_OK;
-    if (c->tp_block) (void)hipFree(c->tp_block);
-    c->tp_block = nullptr; c->tp_valid = c->tp_history = false; c->tp_w = c->tp_h = 0;
-    if (c->sv_block) (void)hipFree(c->sv_block);   // (made for the old size)
-    c->sv_block = nullptr; c->sv_valid = false;
-    free_motion_buffers(c);
+    free_temporal_buffers(c);   // (the moments, the motion image and tables were made for the old size too)
     const size_t npx = (size_t)w * h;
     HIPCHK(c, hipMalloc((void**)&c->tp_block, npx * (7 * 16 + 3 * 4)));   // seven 16-byte images first (every one 16-byte aligned), then the three of one word
     float* p = c->tp_block;
@@ -270,6 +272,54 @@ int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
     return VPT_OK;
 }
 
+// ---- what the entry points share around their enqueue_* call (`enqueue`: that call, returning its error code)
+// A blocking entry: every frame in flight drained first, the pass waited for.  timing: its launches go to the kernel statistics (vpt_postprocess).
+template <class Enqueue>
+int run_blocking(vpt_ctx* c, Enqueue enqueue, bool timing = false) {
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    int rc = drain(c);
+    if (rc || (rc = enqueue())) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    if (timing) collect_timing(c);
+    HIPCHK(c, hipGetLastError());
+    return VPT_OK;
+}
+// A _device entry: the pass goes behind the frames in flight on the context's stream and nothing is waited for; the next frame's resolve waits for ev_post
+// (the pass reads the image).  With dst, `bytes` of the context's image `src` are copied there behind the pass: src is read after the enqueue, which
+// allocates it on its first call.
+template <class Enqueue, class T>
+int run_behind_frames(vpt_ctx* c, Enqueue enqueue, void* dst, T* vpt_ctx::*src, size_t bytes, uint64_t* ticket) {
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    int rc = finish_outstanding(c);   // the image must be complete: an unfinished batch is finished first
+    if (rc) return rc;
+    if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));   // the latest frame was resolved on another lane
+    if ((rc = enqueue())) return rc;
+    if (dst) HIPCHK(c, hipMemcpyAsync(dst, c->*src, bytes, hipMemcpyDeviceToDevice, c->main.stream));
+    HIPCHK(c, hipEventRecord(c->ev_post, c->main.stream));
+    c->post_pending = true;
+    const uint64_t t = issue_ticket(c, c->main.stream);
+    if (ticket) *ticket = t;
+    return VPT_OK;
+}
+// A read-back: nothing in flight and the main stream idle, so a blocking copy finds what the latest pass left.
+int settle_for_readback(vpt_ctx* c, bool set_device = true) {
+    if (set_device) HIPCHK(c, hipSetDevice(c->cfg.device));
+    int rc = quiesce(c);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    return VPT_OK;
+}
+// The moment record (two floats per pixel) or the variance image (one) of the latest temporal result, which must have been made with the option on.
+int read_variance_result(vpt_ctx* c, float* host, bool moments) {
+    if (!c || !host) return VPT_ERR_INVALID_ARGUMENT;
+    if (!(temporal_ready(c) && c->sv_valid)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "no temporal result of this size made with vpt_svgf_options.variance == 1");
+    int rc = settle_for_readback(c);
+    if (rc) return rc;
+    const size_t npx = (size_t)c->tp_w * c->tp_h;
+    HIPCHK(c, hipMemcpy(host, moments ? c->sv_moments[c->tp_latest] : c->sv_variance, npx * (moments ? 8 : 4), hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -279,12 +329,7 @@ void vpt_default_temporal_params(vpt_temporal_params* p) {
 }
 int vpt_temporal_accumulate(vpt_ctx* c, const vpt_temporal_params* tp, float* rgba_host) {
     int rc = check_temporal(c, tp, nullptr);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if ((rc = drain(c))) return rc;
-    if ((rc = enqueue_temporal(c, tp))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    HIPCHK(c, hipGetLastError());
+    if (rc || (rc = run_blocking(c, [&] { return enqueue_temporal(c, tp); }))) return rc;
     if (rgba_host) HIPCHK(c, hipMemcpy(rgba_host, c->tp_out, (size_t)c->tp_w * c->tp_h * 16, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
@@ -292,16 +337,7 @@ int vpt_temporal_accumulate(vpt_ctx* c, const vpt_temporal_params* tp, float* rg
 int vpt_temporal_accumulate_device(vpt_ctx* c, const vpt_temporal_params* tp, void* rgba_device, uint64_t* ticket) {
     int rc = check_temporal(c, tp, rgba_device);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if ((rc = finish_outstanding(c))) return rc;
-    if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));
-    if ((rc = enqueue_temporal(c, tp))) return rc;
-    if (rgba_device) HIPCHK(c, hipMemcpyAsync(rgba_device, c->tp_out, (size_t)c->tp_w * c->tp_h * 16, hipMemcpyDeviceToDevice, c->main.stream));
-    HIPCHK(c, hipEventRecord(c->ev_post, c->main.stream));
-    c->post_pending = true;
-    const uint64_t t = issue_ticket(c, c->main.stream);
-    if (ticket) *ticket = t;
-    return VPT_OK;
+    return run_behind_frames(c, [&] { return enqueue_temporal(c, tp); }, rgba_device, &vpt_ctx::tp_out, (size_t)c->P.width * c->P.height * 16, ticket);
 }
 int vpt_temporal_reset(vpt_ctx* c) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
@@ -310,10 +346,9 @@ int vpt_temporal_reset(vpt_ctx* c) {
 }
 int vpt_get_temporal_history(vpt_ctx* c, float* length_host) {
     if (!c || !length_host) return VPT_ERR_INVALID_ARGUMENT;
-    if (!(c->tp_valid && c->tp_w == c->P.width && c->tp_h == c->P.height)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "no temporal result of this size: call vpt_temporal_accumulate first");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = quiesce(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    if (!temporal_ready(c)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "no temporal result of this size: call vpt_temporal_accumulate first");
+    int rc = settle_for_readback(c);
+    if (rc) return rc;
     const size_t npx = (size_t)c->tp_w * c->tp_h;
     std::vector<float> rec(npx * 4);   // (r, g, b, length) per pixel
     HIPCHK(c, hipMemcpy(rec.data(), c->tp_hist[c->tp_latest], npx * 16, hipMemcpyDeviceToHost));
@@ -339,20 +374,6 @@ int vpt_get_svgf_options(const vpt_ctx* c, vpt_svgf_options* o) {
     *o = c->svgf;
     return VPT_OK;
 }
-namespace {
-// The moment record (two floats per pixel) or the variance image (one) of the latest temporal result, which must have been made with the option on.
-int read_variance_result(vpt_ctx* c, float* host, bool moments) {
-    if (!c || !host) return VPT_ERR_INVALID_ARGUMENT;
-    if (!(c->tp_valid && c->sv_valid && c->tp_w == c->P.width && c->tp_h == c->P.height))
-        return fail(c, VPT_ERR_INVALID_ARGUMENT, "no temporal result of this size made with vpt_svgf_options.variance == 1");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = quiesce(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    const size_t npx = (size_t)c->tp_w * c->tp_h;
-    HIPCHK(c, hipMemcpy(host, moments ? c->sv_moments[c->tp_latest] : c->sv_variance, npx * (moments ? 8 : 4), hipMemcpyDeviceToHost));
-    return VPT_OK;
-}
-}  // namespace
 int vpt_get_temporal_variance(vpt_ctx* c, float* var_host) { return read_variance_result(c, var_host, false); }
 int vpt_get_temporal_moments(vpt_ctx* c, float* mu_host) { return read_variance_result(c, mu_host, true); }
 // ---- moved instances: the option, and the motion image of the latest temporal result made with it
@@ -374,11 +395,10 @@ int vpt_get_temporal_options(const vpt_ctx* c, vpt_temporal_options* o) {
 }
 int vpt_get_temporal_motion(vpt_ctx* c, float* motion_host) {
     if (!c || !motion_host) return VPT_ERR_INVALID_ARGUMENT;
-    if (!(c->tp_options.instance_motion && c->tp_valid && c->tp_motion_valid && c->tp_motion && c->tp_w == c->P.width && c->tp_h == c->P.height))
+    if (!(temporal_ready(c) && c->tp_options.instance_motion && c->tp_motion_valid && c->tp_motion))
         return fail(c, VPT_ERR_INVALID_ARGUMENT, "no temporal result of this size made with vpt_temporal_options.instance_motion == 1");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rd = quiesce(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    int rc = settle_for_readback(c);
+    if (rc) return rc;
     HIPCHK(c, hipMemcpy(motion_host, c->tp_motion, (size_t)c->tp_w * c->tp_h * 8, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
@@ -395,12 +415,7 @@ void vpt_default_denoise_params(vpt_denoise_params* p) {
 }
 int vpt_denoise(vpt_ctx* c, const vpt_denoise_params* dp, float* rgba_host) {
     int rc = check_denoise(c, dp, nullptr);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if ((rc = drain(c))) return rc;
-    if ((rc = enqueue_denoise(c, dp))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    HIPCHK(c, hipGetLastError());
+    if (rc || (rc = run_blocking(c, [&] { return enqueue_denoise(c, dp); }))) return rc;
     if (rgba_host) HIPCHK(c, hipMemcpy(rgba_host, c->dn_out, (size_t)c->dn_w * c->dn_h * 16, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
@@ -408,16 +423,7 @@ int vpt_denoise(vpt_ctx* c, const vpt_denoise_params* dp, float* rgba_host) {
 int vpt_denoise_device(vpt_ctx* c, const vpt_denoise_params* dp, void* rgba_device, uint64_t* ticket) {
     int rc = check_denoise(c, dp, rgba_device);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if ((rc = finish_outstanding(c))) return rc;
-    if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));
-    if ((rc = enqueue_denoise(c, dp))) return rc;
-    if (rgba_device) HIPCHK(c, hipMemcpyAsync(rgba_device, c->dn_out, (size_t)c->dn_w * c->dn_h * 16, hipMemcpyDeviceToDevice, c->main.stream));
-    HIPCHK(c, hipEventRecord(c->ev_post, c->main.stream));
-    c->post_pending = true;
-    const uint64_t t = issue_ticket(c, c->main.stream);
-    if (ticket) *ticket = t;
-    return VPT_OK;
+    return run_behind_frames(c, [&] { return enqueue_denoise(c, dp); }, rgba_device, &vpt_ctx::dn_out, (size_t)c->P.width * c->P.height * 16, ticket);
 }
 int vpt_set_post_source(vpt_ctx* c, uint32_t source) {
     if (!c) return VPT_ERR_INVALID_ARGUMENT;
@@ -430,14 +436,8 @@ int vpt_postprocess(vpt_ctx* c, const vpt_post_params* pp, uint8_t* out8, float*
     if (!c || !pp || !out8) return VPT_ERR_INVALID_ARGUMENT;
     int rc = post_preconditions(c);
     if (rc) return rc;
-    if ((rc = post_source_ready(c))) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if ((rc = drain(c))) return rc;
-    if ((rc = enqueue_post(c, pp, bloom0 != nullptr))) return rc;
+    if ((rc = post_source_ready(c)) || (rc = run_blocking(c, [&] { return enqueue_post(c, pp, bloom0 != nullptr); }, true))) return rc;
     const uint32_t W = c->P.width, H = c->P.height;
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    collect_timing(c);
-    HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpy(out8, c->post_out, (size_t)W * H * 4, hipMemcpyDeviceToHost));
     if (bloom0) HIPCHK(c, hipMemcpy(bloom0, c->mips[0], (size_t)W * H * 16, hipMemcpyDeviceToHost));
     return VPT_OK;
@@ -449,23 +449,14 @@ int vpt_postprocess_device(vpt_ctx* c, const vpt_post_params* pp, void* rgba8_de
     int rc = post_preconditions(c);
     if (rc) return rc;
     if ((rc = post_source_ready(c))) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if ((rc = finish_outstanding(c))) return rc;   // the image must be complete: an unfinished batch is finished first
-    if (c->order_lane && c->order_lane != &c->main) HIPCHK(c, hipStreamWaitEvent(c->main.stream, c->order_lane->ev_resolved, 0));   // the latest frame was resolved on another lane
-    if ((rc = enqueue_post(c, pp, false))) return rc;
-    if (rgba8_device) HIPCHK(c, hipMemcpyAsync(rgba8_device, c->post_out, (size_t)c->P.width * c->P.height * 4, hipMemcpyDeviceToDevice, c->main.stream));
-    HIPCHK(c, hipEventRecord(c->ev_post, c->main.stream));
-    c->post_pending = true;
-    const uint64_t t = issue_ticket(c, c->main.stream);
-    if (ticket) *ticket = t;
-    return VPT_OK;
+    return run_behind_frames(c, [&] { return enqueue_post(c, pp, false); }, rgba8_device, &vpt_ctx::post_out, (size_t)c->P.width * c->P.height * 4, ticket);
 }
 const void* vpt_output_device(vpt_ctx* c) { return c ? c->post_out : nullptr; }
 int vpt_get_output(vpt_ctx* c, uint8_t* out8) {
     if (!c || !out8) return VPT_ERR_INVALID_ARGUMENT;
     if (!c->post_out) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_get_output before the first post-process");
-    { int rd = quiesce(c); if (rd) return rd; }
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    int rc = settle_for_readback(c, false);   // (the one read-back that leaves the calling thread's device as it is)
+    if (rc) return rc;
     HIPCHK(c, hipMemcpy(out8, c->post_out, (size_t)c->post_w * c->post_h * 4, hipMemcpyDeviceToHost));
     return VPT_OK;
 }

@@ -292,31 +292,30 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_bounce(DeviceScene sc, Re
 void launch_bounce(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, bool first, const DeviceScene& sc, const RenderParams& P,
                    const PathState& ps, const StreamState& ss, const uint32_t* queue, uint32_t* queue_next, Counters* ctr, uint32_t parity, uint32_t n_slots,
                    uint32_t dispatch_base, uint32_t k3, bool plain) {
-    size_t lds = traverse_lds_bytes(sc, lds_scene, kStackDepth);
-    dim3 g(blocks), b(kTraverseBlock);
+    const size_t lds = traverse_lds_bytes(sc, lds_scene, kStackDepth);
+    const dim3 g(blocks), b(kTraverseBlock);
+    // one launch site for the sixteen instantiations: each site copies the scene, the parameters and both path states by value, host code the library's
+    // size bound (DESIGN.md "Library size") would pay for sixteen times
+    void (*k)(DeviceScene, RenderParams, PathState, StreamState, const uint32_t*, uint32_t*, Counters*, uint32_t, uint32_t, uint32_t, uint32_t);
     if (plain && lds_scene && !count && !sc.strict_hits && sc.volume_count == 0u && !sc.atm_on && sc.env_black) {   // the scene-class instantiation
-        if (first) hipLaunchKernelGGL((k_bounce<true, false, true, false, false, true>), g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3);
-        else hipLaunchKernelGGL((k_bounce<true, false, false, false, false, true>), g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3);
-        return;
-    }
-#define VPT_LAUNCH_BOUNCE_V(L, C, F, V) do { if (sc.strict_hits) hipLaunchKernelGGL((k_bounce<L, C, F, V, true>), g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3); \
-        else hipLaunchKernelGGL((k_bounce<L, C, F, V, false>), g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3); } while (0)
-#define VPT_LAUNCH_BOUNCE(L, C, F) VPT_LAUNCH_BOUNCE_V(L, C, F, false)
-#define VPT_LAUNCH_MEDIA(L, F) hipLaunchKernelGGL((k_bounce<L, false, F, true, false>), g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3)
-    if (sc.volume_count > 0u || sc.atm_on) {  // the media variants carry no traversal counters and read VPT_FLAG_LOCAL_HITS at run time
-        if (lds_scene) { if (first) VPT_LAUNCH_MEDIA(true, true); else VPT_LAUNCH_MEDIA(true, false); }
-        else { if (first) VPT_LAUNCH_MEDIA(false, true); else VPT_LAUNCH_MEDIA(false, false); }
+        k = first ? k_bounce<true, false, true, false, false, true> : k_bounce<true, false, false, false, false, true>;
+    } else if (sc.volume_count > 0u || sc.atm_on) {  // the media variants carry no traversal counters and read VPT_FLAG_LOCAL_HITS at run time
+        if (lds_scene) k = first ? k_bounce<true, false, true, true, false> : k_bounce<true, false, false, true, false>;
+        else k = first ? k_bounce<false, false, true, true, false> : k_bounce<false, false, false, true, false>;
     } else if (lds_scene) {
-        if (count) { if (first) VPT_LAUNCH_BOUNCE(true, true, true); else VPT_LAUNCH_BOUNCE(true, true, false); }
-        else { if (first) VPT_LAUNCH_BOUNCE(true, false, true); else VPT_LAUNCH_BOUNCE(true, false, false); }
+        const bool strict = sc.strict_hits;
+        if (count) {
+            if (first) k = strict ? k_bounce<true, true, true, false, true> : k_bounce<true, true, true, false, false>;
+            else k = strict ? k_bounce<true, true, false, false, true> : k_bounce<true, true, false, false, false>;
+        } else {
+            if (first) k = strict ? k_bounce<true, false, true, false, true> : k_bounce<true, false, true, false, false>;
+            else k = strict ? k_bounce<true, false, false, false, true> : k_bounce<true, false, false, false, false>;
+        }
     } else {   // a tree in memory: the hit rule is read at run time (above), and the visit counters always run (two adds per visit in a kernel
                // that is the slow side of an A/B anyway: one instantiation per bounce kind instead of four)
-        if (first) hipLaunchKernelGGL((k_bounce<false, true, true, false, false>), g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3);
-        else hipLaunchKernelGGL((k_bounce<false, true, false, false, false>), g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3);
+        k = first ? k_bounce<false, true, true, false, false> : k_bounce<false, true, false, false, false>;
     }
-#undef VPT_LAUNCH_MEDIA
-#undef VPT_LAUNCH_BOUNCE
-#undef VPT_LAUNCH_BOUNCE_V
+    hipLaunchKernelGGL(k, g, b, lds, s, sc, P, ps, ss, queue, queue_next, ctr, parity, n_slots, dispatch_base, k3);
 }
 int bounce_blocks_per_cu(bool lds_scene, const DeviceScene& sc, bool plain) {
     int nb = 0;

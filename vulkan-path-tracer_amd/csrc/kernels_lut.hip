@@ -96,9 +96,11 @@ __global__ __launch_bounds__(64) void k_lut(float* table, uint32_t sx, uint32_t 
 void launch_lut(hipStream_t s, int kind, float* table, uint32_t sx, uint32_t sy, uint32_t sz, uint32_t sample_count, uint32_t time_hash,
                 uint32_t first_dispatch, uint32_t n_dispatches) {
     const uint32_t cells = sx * sy * sz, blocks = (cells + 63u) / 64u;
-    if (kind == 0) hipLaunchKernelGGL(k_lut<0>, dim3(blocks), dim3(64), 0, s, table, sx, sy, sz, sample_count, time_hash, first_dispatch, n_dispatches);
-    else if (kind == 1) hipLaunchKernelGGL(k_lut<1>, dim3(blocks), dim3(64), 0, s, table, sx, sy, sz, sample_count, time_hash, first_dispatch, n_dispatches);
-    else hipLaunchKernelGGL(k_lut<2>, dim3(blocks), dim3(64), 0, s, table, sx, sy, sz, sample_count, time_hash, first_dispatch, n_dispatches);
+    void (*k)(float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
+    if (kind == 0) k = k_lut<0>;
+    else if (kind == 1) k = k_lut<1>;
+    else k = k_lut<2>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(64), 0, s, table, sx, sy, sz, sample_count, time_hash, first_dispatch, n_dispatches);
 }
 
 }  // namespace vpt

@@ -617,10 +617,11 @@ void launch_denoise_prepare(hipStream_t s, const float* c, const float* depth, f
 void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, const float* albedo, float* out, uint32_t w, uint32_t h, const denoise::Pass& ps, bool remodulate,
                            bool variance, float sigma_luminance, bool last) {
     const dim3 g(cdiv_(w, kTileW), cdiv_(h, kTileH)), b(256);
-#define VPT_DN(T, V) hipLaunchKernelGGL((k_denoise_atrous<T, V>), g, b, 0, s, reinterpret_cast<const dn::F4*>(in), reinterpret_cast<const dn::F4*>(guide), reinterpret_cast<const dn::F4*>(albedo), \
-                                        reinterpret_cast<dn::F4*>(out), (int)w, (int)h, ps, remodulate ? 1 : 0, sigma_luminance, last ? 1 : 0)
-    if (variance) VPT_DN(false, true); else if (2 * ps.step <= kDnMaxHalo) VPT_DN(true, false); else VPT_DN(false, false);
-#undef VPT_DN
+    void (*k)(const dn::F4*, const dn::F4*, const dn::F4*, dn::F4*, int, int, dn::Pass, int, float, int);
+    if (variance) k = k_denoise_atrous<false, true>;
+    else k = 2 * ps.step <= kDnMaxHalo ? k_denoise_atrous<true, false> : k_denoise_atrous<false, false>;
+    hipLaunchKernelGGL(k, g, b, 0, s, reinterpret_cast<const dn::F4*>(in), reinterpret_cast<const dn::F4*>(guide), reinterpret_cast<const dn::F4*>(albedo),
+                       reinterpret_cast<dn::F4*>(out), (int)w, (int)h, ps, remodulate ? 1 : 0, sigma_luminance, last ? 1 : 0);
 }
 
 // ---- vpt_temporal_accumulate (api_post.hip enqueue_temporal): temporal.hpp's temporal_pixel does all the arithmetic; the kernel only decides where a
@@ -697,17 +698,17 @@ void launch_bloom_tail(hipStream_t s, float* base, float* top_out, uint32_t bw, 
     t.base = reinterpret_cast<float4*>(base); t.top_out = reinterpret_cast<float4*>(top_out); t.bw = (int)bw; t.bh = (int)bh; t.levels = (int)levels; t.strength = strength;
     int off = 0;
     for (uint32_t k = 0; k < levels; k++) { t.w[k] = (int)w[k]; t.h[k] = (int)h[k]; t.off[k] = off; off += (int)(w[k] * h[k]); }
-    if (bloom_tail_is_staged(bw, bh)) hipLaunchKernelGGL(k_bloom_tail<true>, dim3(1), dim3(kTailThreads), 0, s, t);
-    else hipLaunchKernelGGL(k_bloom_tail<false>, dim3(1), dim3(kTailThreads), 0, s, t);
+    void (*k)(BloomTail) = bloom_tail_is_staged(bw, bh) ? k_bloom_tail<true> : k_bloom_tail<false>;
+    hipLaunchKernelGGL(k, dim3(1), dim3(kTailThreads), 0, s, t);
 }
 void launch_post_final(hipStream_t s, const float* hdr, const float* mip1, uint32_t mw, uint32_t mh, float* bloom0_out, uint8_t* out, uint32_t w, uint32_t h,
                        float threshold, float falloff, float strength, float exposure, float gamma, bool linear_tap) {
     const dim3 g(cdiv_(w, 64), cdiv_(h, 4)), b(256);
-#define VPT_PF(UP, LIN) hipLaunchKernelGGL((k_post_final<UP, LIN>), g, b, 0, s, reinterpret_cast<const float4*>(hdr), reinterpret_cast<const float4*>(mip1), (int)mw, (int)mh, \
-                                           reinterpret_cast<float4*>(bloom0_out), reinterpret_cast<uchar4*>(out), (int)w, (int)h, threshold, falloff, strength, exposure, gamma)
-    if (mip1) { if (linear_tap) VPT_PF(true, true); else VPT_PF(true, false); }
-    else { if (linear_tap) VPT_PF(false, true); else VPT_PF(false, false); }
-#undef VPT_PF
+    void (*k)(const float4*, const float4*, int, int, float4*, uchar4*, int, int, float, float, float, float, float);
+    if (mip1) k = linear_tap ? k_post_final<true, true> : k_post_final<true, false>;
+    else k = linear_tap ? k_post_final<false, true> : k_post_final<false, false>;
+    hipLaunchKernelGGL(k, g, b, 0, s, reinterpret_cast<const float4*>(hdr), reinterpret_cast<const float4*>(mip1), (int)mw, (int)mh,
+                       reinterpret_cast<float4*>(bloom0_out), reinterpret_cast<uchar4*>(out), (int)w, (int)h, threshold, falloff, strength, exposure, gamma);
 }
 void launch_bloom_up(hipStream_t s, const float* in, uint32_t iw, uint32_t ih, float* out, uint32_t ow, uint32_t oh, float strength) {
     hipLaunchKernelGGL(k_bloom_up, dim3(cdiv_(ow, 64), cdiv_(oh, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(in), (int)iw, (int)ih,

@@ -415,10 +415,12 @@ void launch_layout_single(hipStream_t s, StreamCounters* sc, uint32_t parity, ui
 void launch_shade_stream(hipStream_t s, uint32_t blocks, uint32_t cls, bool sorted, const DeviceScene& sc, const RenderParams& P, const PathState& ps, const StreamState& ss,
                          const uint32_t* queue, const uint32_t* order, uint32_t* queue_next, Counters* ctr, StreamCounters* sctr, uint32_t parity) {
     const dim3 g(blocks), b(256);
-    if (!sorted) hipLaunchKernelGGL((k_shade_stream<kShadeAny>), g, b, 0, s, sc, P, ps, ss, queue, nullptr, queue_next, ctr, sctr, parity, 0u);
-    else if (cls == kShadeMiss) hipLaunchKernelGGL((k_shade_stream<(int)kShadeMiss>), g, b, 0, s, sc, P, ps, ss, queue, order, queue_next, ctr, sctr, parity, cls);
-    else if (cls == kShadePlain) hipLaunchKernelGGL((k_shade_stream<(int)kShadePlain>), g, b, 0, s, sc, P, ps, ss, queue, order, queue_next, ctr, sctr, parity, cls);
-    else hipLaunchKernelGGL((k_shade_stream<(int)kShadeTextured>), g, b, 0, s, sc, P, ps, ss, queue, order, queue_next, ctr, sctr, parity, cls);  // textured, glass, emissive: the general hit code
+    void (*k)(DeviceScene, RenderParams, PathState, StreamState, const uint32_t*, const uint32_t*, uint32_t*, Counters*, StreamCounters*, uint32_t, uint32_t);
+    if (!sorted) { k = k_shade_stream<kShadeAny>; order = nullptr; cls = 0u; }   // the unsorted queue: no order table, class slot 0
+    else if (cls == kShadeMiss) k = k_shade_stream<(int)kShadeMiss>;
+    else if (cls == kShadePlain) k = k_shade_stream<(int)kShadePlain>;
+    else k = k_shade_stream<(int)kShadeTextured>;  // textured, glass, emissive: the general hit code
+    hipLaunchKernelGGL(k, g, b, 0, s, sc, P, ps, ss, queue, order, queue_next, ctr, sctr, parity, cls);
 }
 void launch_join(hipStream_t s, uint32_t blocks, const RenderParams& P, const PathState& ps, const StreamState& ss, const StreamCounters* sctr, const uint32_t* queue,
                  const uint32_t* queue_next, uint32_t parity) {

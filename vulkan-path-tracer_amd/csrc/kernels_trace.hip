@@ -692,87 +692,69 @@ int trace_blocks_per_cu(uint32_t variant, bool any) {
     return nb > 0 ? nb : 1;
 }
 
+// every kernel of this file that works through a closest-hit / any-hit ray stream
+using TraceKernel = void (*)(DeviceScene, TraceArgs, Counters*);
+
 void launch_trace(hipStream_t s, uint32_t blocks, uint32_t variant, bool any, bool count, const DeviceScene& sc, const TraceArgs& a, Counters* ctr) {
+    TraceKernel k = nullptr;   // one launch site: a laboratory variant where the trace lab asks for one, else (still nullptr) the product's search
+    uint32_t grid = blocks;
+    size_t lds = kVoteLdsBytes;
 #if VPT_LAB
     if (variant == VPT_TRACE_PAIR) {   // closest hit only
-        if (count) hipLaunchKernelGGL((k_trace_pair<true>), dim3(blocks), dim3(kTraverseBlock), kPairLdsBytes, s, sc, a, ctr);
-        else hipLaunchKernelGGL((k_trace_pair<false>), dim3(blocks), dim3(kTraverseBlock), kPairLdsBytes, s, sc, a, ctr);
-        return;
-    }
-    if (variant == VPT_TRACE_POOL) {   // closest hit only (the lab refuses the any-hit form).  param bits 8-9: slots per wave / LDS stack entries 128/10, 96/10, 80/8, 64/8
+        k = count ? k_trace_pair<true> : k_trace_pair<false>;
+        lds = kPairLdsBytes;
+    } else if (variant == VPT_TRACE_POOL) {   // closest hit only (the lab refuses the any-hit form).  param bits 8-9: slots per wave / LDS stack entries 128/10, 96/10, 80/8, 64/8
         // (3, 4, 5, 6 blocks per CU: the grid — and with it the slot-indexed spill region — keeps blocks x slots constant); bit 10: DUAL
         const uint32_t cfg = (a.param >> 8) & 3u;
         const bool dual = ((a.param >> 10) & 1u) != 0u;
-        const dim3 b(kTraverseBlock);
-#define VPT_LP(SL, STK, G) do { const dim3 g(G); const size_t lds = pool_lds_bytes(SL, STK);                                                   \
-            if (dual) { if (count) hipLaunchKernelGGL((k_trace_pool<true, SL, STK, true>), g, b, lds, s, sc, a, ctr);                               \
-                        else hipLaunchKernelGGL((k_trace_pool<false, SL, STK, true>), g, b, lds, s, sc, a, ctr); }                                 \
-            else { if (count) hipLaunchKernelGGL((k_trace_pool<true, SL, STK, false>), g, b, lds, s, sc, a, ctr);                                  \
-                   else hipLaunchKernelGGL((k_trace_pool<false, SL, STK, false>), g, b, lds, s, sc, a, ctr); } } while (0)
-        if (cfg == 0u) VPT_LP(128, 10, blocks);
-        else if (cfg == 1u) VPT_LP(96, 10, blocks + blocks / 3u);
-        else if (cfg == 2u) VPT_LP(80, 8, blocks + (blocks * 2u) / 3u);
-        else VPT_LP(64, 8, blocks * 2u);
-#undef VPT_LP
-        return;
-    }
-    {
-        const size_t lds = variant == VPT_TRACE_BASE ? kVoteStackBytes : kVoteLdsBytes;
-        const dim3 g(blocks), b(kTraverseBlock);
-#define VPT_LT(K) do { if (any) { if (count) hipLaunchKernelGGL((K<true, true>), g, b, lds, s, sc, a, ctr); else hipLaunchKernelGGL((K<true, false>), g, b, lds, s, sc, a, ctr); } \
-                       else { if (count) hipLaunchKernelGGL((K<false, true>), g, b, lds, s, sc, a, ctr); else hipLaunchKernelGGL((K<false, false>), g, b, lds, s, sc, a, ctr); } } while (0)
-#define VPT_LV(W, T) do { if (any) { if (count) hipLaunchKernelGGL((k_trace_vote<true, true, W, T>), g, b, lds, s, sc, a, ctr); else hipLaunchKernelGGL((k_trace_vote<true, false, W, T>), g, b, lds, s, sc, a, ctr); } \
-                          else { if (count) hipLaunchKernelGGL((k_trace_vote<false, true, W, T>), g, b, lds, s, sc, a, ctr); else hipLaunchKernelGGL((k_trace_vote<false, false, W, T>), g, b, lds, s, sc, a, ctr); } } while (0)
-        if (variant == VPT_TRACE_VOTE4S) {   // product vote parameters, two triangles per step; the counting form one.  Any-hit: the plain node step on the split-order tree (its order tables masked off)
-            if (any) {
-                if (count) hipLaunchKernelGGL((k_trace_vote<true, true, false, true, false, false, false, false, true>), g, b, lds, s, sc, a, ctr);
-                else hipLaunchKernelGGL((k_trace_vote<true, false, false, true, false, false, false, true, true>), g, b, lds, s, sc, a, ctr);
-            } else if (count) hipLaunchKernelGGL((k_trace_vote<false, true, false, true, false, false, false, false, true>), g, b, lds, s, sc, a, ctr);
-            else hipLaunchKernelGGL((k_trace_vote<false, false, false, true, false, false, false, true, true>), g, b, lds, s, sc, a, ctr);
-            return;
+        if (cfg == 0u) {
+            k = dual ? (count ? k_trace_pool<true, 128, 10, true> : k_trace_pool<false, 128, 10, true>) : (count ? k_trace_pool<true, 128, 10, false> : k_trace_pool<false, 128, 10, false>);
+            lds = pool_lds_bytes(128, 10);
+        } else if (cfg == 1u) {
+            k = dual ? (count ? k_trace_pool<true, 96, 10, true> : k_trace_pool<false, 96, 10, true>) : (count ? k_trace_pool<true, 96, 10, false> : k_trace_pool<false, 96, 10, false>);
+            grid = blocks + blocks / 3u; lds = pool_lds_bytes(96, 10);
+        } else if (cfg == 2u) {
+            k = dual ? (count ? k_trace_pool<true, 80, 8, true> : k_trace_pool<false, 80, 8, true>) : (count ? k_trace_pool<true, 80, 8, false> : k_trace_pool<false, 80, 8, false>);
+            grid = blocks + (blocks * 2u) / 3u; lds = pool_lds_bytes(80, 8);
+        } else {
+            k = dual ? (count ? k_trace_pool<true, 64, 8, true> : k_trace_pool<false, 64, 8, true>) : (count ? k_trace_pool<true, 64, 8, false> : k_trace_pool<false, 64, 8, false>);
+            grid = blocks * 2u; lds = pool_lds_bytes(64, 8);
         }
-        if (variant == VPT_TRACE_BASE) { VPT_LT(k_trace_base); return; }
-        if (variant == VPT_TRACE_VOTE8) { VPT_LV(true, false); return; }
-        if (!sc.strict_hits) {
-            if (a.one_tri && !count) {   // trace lab bit 19: ONE triangle per triangle step (round 3's step) with the product vote parameters, for the A/B against the product's two
-                if (any) hipLaunchKernelGGL((k_trace_vote<true, false, false, true, false, false, false, false>), g, b, lds, s, sc, a, ctr);
-                else hipLaunchKernelGGL((k_trace_vote<false, false, false, true, false, false, false, false>), g, b, lds, s, sc, a, ctr);
-                return;
-            }
-            if (a.packed) {   // trace lab bit 18: packed plane arithmetic in the node step, product vote parameters
-                if (any) { if (count) hipLaunchKernelGGL((k_trace_vote<true, true, false, true, false, false, true>), g, b, lds, s, sc, a, ctr); else hipLaunchKernelGGL((k_trace_vote<true, false, false, true, false, false, true>), g, b, lds, s, sc, a, ctr); }
-                else { if (count) hipLaunchKernelGGL((k_trace_vote<false, true, false, true, false, false, true>), g, b, lds, s, sc, a, ctr); else hipLaunchKernelGGL((k_trace_vote<false, false, false, true, false, false, true>), g, b, lds, s, sc, a, ctr); }
-                return;
-            }
-            if (a.cull && !any) {   // stale-entry culling (closest-hit only)
-                if (count) hipLaunchKernelGGL((k_trace_vote<false, true, false, false, false, true>), g, b, lds, s, sc, a, ctr);
-                else if (a.param == kVoteParamDefault) hipLaunchKernelGGL((k_trace_vote<false, false, false, true, false, true>), g, b, lds, s, sc, a, ctr);
-                else hipLaunchKernelGGL((k_trace_vote<false, false, false, false, false, true>), g, b, lds, s, sc, a, ctr);
-                return;
-            }
-            if (a.param != kVoteParamDefault) { VPT_LV(false, false); return; }   // run-time vote parameters
-            if (any) {   // (the pipeline's shadow rays go through k_trace_shadow: the any-hit form of k_trace_vote exists for the lab's ray sets)
-                if (count) hipLaunchKernelGGL((k_trace_vote<true, true, false, true>), g, b, lds, s, sc, a, ctr);
-                else hipLaunchKernelGGL((k_trace_vote<true, false, false, true, false, false, false, true>), g, b, lds, s, sc, a, ctr);
-                return;
-            }
-        } else if (any) {
-            if (count) hipLaunchKernelGGL((k_trace_vote<true, true, false, true, true>), g, b, lds, s, sc, a, ctr);
-            else hipLaunchKernelGGL((k_trace_vote<true, false, false, true, true>), g, b, lds, s, sc, a, ctr);
-            return;
+    } else if (variant == VPT_TRACE_VOTE4S) {   // product vote parameters, two triangles per step; the counting form one.  Any-hit: the plain node step on the split-order tree (its order tables masked off)
+        if (any) k = count ? k_trace_vote<true, true, false, true, false, false, false, false, true> : k_trace_vote<true, false, false, true, false, false, false, true, true>;
+        else k = count ? k_trace_vote<false, true, false, true, false, false, false, false, true> : k_trace_vote<false, false, false, true, false, false, false, true, true>;
+    } else if (variant == VPT_TRACE_BASE) {
+        if (any) k = count ? k_trace_base<true, true> : k_trace_base<true, false>;
+        else k = count ? k_trace_base<false, true> : k_trace_base<false, false>;
+        lds = kVoteStackBytes;
+    } else if (variant == VPT_TRACE_VOTE8) {
+        if (any) k = count ? k_trace_vote<true, true, true, false> : k_trace_vote<true, false, true, false>;
+        else k = count ? k_trace_vote<false, true, true, false> : k_trace_vote<false, false, true, false>;
+    } else if (!sc.strict_hits) {
+        if (a.one_tri && !count) {   // trace lab bit 19: ONE triangle per triangle step (round 3's step) with the product vote parameters, for the A/B against the product's two
+            k = any ? k_trace_vote<true, false, false, true, false, false, false, false> : k_trace_vote<false, false, false, true, false, false, false, false>;
+        } else if (a.packed) {   // trace lab bit 18: packed plane arithmetic in the node step, product vote parameters
+            if (any) k = count ? k_trace_vote<true, true, false, true, false, false, true> : k_trace_vote<true, false, false, true, false, false, true>;
+            else k = count ? k_trace_vote<false, true, false, true, false, false, true> : k_trace_vote<false, false, false, true, false, false, true>;
+        } else if (a.cull && !any) {   // stale-entry culling (closest-hit only)
+            if (count) k = k_trace_vote<false, true, false, false, false, true>;
+            else k = a.param == kVoteParamDefault ? k_trace_vote<false, false, false, true, false, true> : k_trace_vote<false, false, false, false, false, true>;
+        } else if (a.param != kVoteParamDefault) {   // run-time vote parameters
+            if (any) k = count ? k_trace_vote<true, true, false, false> : k_trace_vote<true, false, false, false>;
+            else k = count ? k_trace_vote<false, true, false, false> : k_trace_vote<false, false, false, false>;
+        } else if (any) {   // (the pipeline's shadow rays go through k_trace_shadow: the any-hit form of k_trace_vote exists for the lab's ray sets)
+            k = count ? k_trace_vote<true, true, false, true> : k_trace_vote<true, false, false, true, false, false, false, true>;
         }
-#undef VPT_LV
-#undef VPT_LT
+    } else if (any) {
+        k = count ? k_trace_vote<true, true, false, true, true> : k_trace_vote<true, false, false, true, true>;
     }
 #endif
-    // ---- the product's closest-hit search: compile-time vote parameters; two triangles per triangle step unless visits are counted or hits validated
     (void)variant; (void)any;
-    const dim3 g(blocks), b(kTraverseBlock);
-    if (sc.strict_hits) {   // VPT_FLAG_LOCAL_HITS: the validating instantiations
-        if (count) hipLaunchKernelGGL((k_trace_vote<false, true, false, true, true>), g, b, kVoteLdsBytes, s, sc, a, ctr);
-        else hipLaunchKernelGGL((k_trace_vote<false, false, false, true, true>), g, b, kVoteLdsBytes, s, sc, a, ctr);
-    } else if (count) hipLaunchKernelGGL((k_trace_vote<false, true, false, true>), g, b, kVoteLdsBytes, s, sc, a, ctr);
-    else hipLaunchKernelGGL((k_trace_vote<false, false, false, true, false, false, false, true>), g, b, kVoteLdsBytes, s, sc, a, ctr);
+    if (!k) {   // ---- the product's closest-hit search: compile-time vote parameters; two triangles per triangle step unless visits are counted or hits validated
+        if (sc.strict_hits) k = count ? k_trace_vote<false, true, false, true, true> : k_trace_vote<false, false, false, true, true>;   // VPT_FLAG_LOCAL_HITS: the validating instantiations
+        else k = count ? k_trace_vote<false, true, false, true> : k_trace_vote<false, false, false, true, false, false, false, true>;
+    }
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kTraverseBlock), lds, s, sc, a, ctr);
 }
 
 void launch_trace_shadow(hipStream_t s, uint32_t blocks, bool light, bool count, const DeviceScene& sc, const StreamState& ss, Counters* ctr,
@@ -782,25 +764,24 @@ void launch_trace_shadow(hipStream_t s, uint32_t blocks, bool light, bool count,
     const float4 *RO = light ? ss.LTO : ss.SKO, *RD = light ? ss.LTD : ss.SKD;
     unsigned char* vis = light ? ss.vis_light : ss.vis_sky;
     uint32_t *len = light ? &sctr->light_len.v : &sctr->sky_len.v, *head = light ? &sctr->light_head.v : &sctr->sky_head.v;
-#define VPT_LS(L, C, T, ST, T2) hipLaunchKernelGGL((k_trace_shadow<L, C, T, ST, T2>), g, b, lds, s, sc, RO, RD, vis, len, head, ctr, param, ray_queries)
+    void (*k)(DeviceScene, const float4*, const float4*, unsigned char*, const uint32_t*, uint32_t*, Counters*, uint32_t, uint32_t);
 #if VPT_LAB
     if (param != kVoteParamDefault && !sc.strict_hits) {   // run-time vote parameters (trace-lab sweeps through the pipeline)
-        if (light) { if (count) VPT_LS(true, true, false, false, false); else VPT_LS(true, false, false, false, false); }
-        else { if (count) VPT_LS(false, true, false, false, false); else VPT_LS(false, false, false, false, false); }
-        return;
-    }
+        if (light) k = count ? k_trace_shadow<true, true, false, false, false> : k_trace_shadow<true, false, false, false, false>;
+        else k = count ? k_trace_shadow<false, true, false, false, false> : k_trace_shadow<false, false, false, false, false>;
+    } else
 #endif
     // the product instantiations: compile-time vote parameters; two triangles per triangle step unless visits are counted or hits validated
     // (VPT_FLAG_LOCAL_HITS with vpt_config.count_traversal runs the counting + validating one, so the visit statistics are not silently zero)
     if (sc.strict_hits) {
-        if (light) { if (count) VPT_LS(true, true, true, true, false); else VPT_LS(true, false, true, true, false); }
-        else { if (count) VPT_LS(false, true, true, true, false); else VPT_LS(false, false, true, true, false); }
+        if (light) k = count ? k_trace_shadow<true, true, true, true, false> : k_trace_shadow<true, false, true, true, false>;
+        else k = count ? k_trace_shadow<false, true, true, true, false> : k_trace_shadow<false, false, true, true, false>;
     } else if (count) {
-        if (light) VPT_LS(true, true, true, false, false); else VPT_LS(false, true, true, false, false);
+        k = light ? k_trace_shadow<true, true, true, false, false> : k_trace_shadow<false, true, true, false, false>;
     } else {
-        if (light) VPT_LS(true, false, true, false, true); else VPT_LS(false, false, true, false, true);
+        k = light ? k_trace_shadow<true, false, true, false, true> : k_trace_shadow<false, false, true, false, true>;
     }
-#undef VPT_LS
+    hipLaunchKernelGGL(k, g, b, lds, s, sc, RO, RD, vis, len, head, ctr, param, ray_queries);
 }
 int trace_shadow_blocks_per_cu() {
     int a = 0, b = 0;
