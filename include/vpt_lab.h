@@ -18,7 +18,8 @@ extern "C" {
  * 0..n-1: e.g. sorted by origin cell and direction octant).  All rays of a set share ray 0's tmin / tmax.  Results are
  * per ray whatever the variant or order: hits_host (optional, n entries; any-hit: t = 1 occluded / -1 clear).
  * best_ms = fastest of `reps` launches (HIP events on the context's stream); visits (optional) = {nodes, triangles}
- * visited, from one extra counting launch. */
+ * visited, from one extra counting launch (hits_host is then that launch's).  tests/test_gpu_trace_stream.py holds VPT_TRACE_VOTE and the shadow
+ * kernels to brute force through these entry points. */
 #define VPT_TRACE_BASE 0u  /* one ray per lane, 64 rays per wave at a time (round 1's extend / shadow loop) */
 #define VPT_TRACE_VOTE 1u  /* persistent lanes, wave-level vote between node / triangle / fetch steps, ray replacement */
 #define VPT_TRACE_VOTE8 2u /* the same on an eight-wide tree with octant-ordered children (BVH8 experiment; built on first use) */
@@ -30,6 +31,8 @@ extern "C" {
                             * (kernels_trace.hip k_trace_pair).  param: low byte = idle rays (of 128 per wave) that trigger a fetch (0: 48) */
 #define VPT_TRACE_VOTE4S 5u /* the vote kernel on the SPLIT-ORDER four-wide tree — hit children visited in the order the node's binary splits give for the
                              * ray's direction octant (three table bits, a three-exchange butterfly) instead of sorted by entry distance (vote.hpp vote_node4s_step; built on first use) */
+/* The resident buffers end in a guard of 1024 entries (the largest chunk a fetch step takes) whose results are filled before every launch of
+ * vpt_lab_trace / vpt_lab_trace_shadow: a launch that writes there has worked on entries beyond n and fails with VPT_ERR_DEVICE. */
 int vpt_lab_set_rays(vpt_ctx* ctx, const vpt_ray* rays_host, uint32_t n);
 /* Measurement hook on the scheduling of pipelined 1-frame batches (vpt_render_async; tests/tools/latency_probe.py): images never depend on it.
  *   VPT_LAB_LANES       lanes consecutive frames are dealt to (1-3; default 3: a frame takes the first lane whose previous frame is resolved)
@@ -59,6 +62,20 @@ int vpt_lab_set(vpt_ctx* ctx, uint32_t key, uint32_t value);
 int vpt_lab_whole_culled(const vpt_ctx* ctx, uint64_t* out);
 int vpt_lab_trace(vpt_ctx* ctx, uint32_t variant, uint32_t any_hit, const uint32_t* order_host, uint32_t param, uint32_t reps,
                   vpt_hit* hits_host, float* best_ms, uint64_t* visits);
+/* A hole mask beside the resident rays (n bytes, non-zero: ray i is a HOLE, a stream entry nobody wrote; NULL: no holes, as after vpt_lab_set_rays).
+ * While one is installed, VPT_TRACE_VOTE launches of vpt_lab_trace see the holes the way the pipeline's queues show them (TraceArgs::valid, or the
+ * hole word in place of the entry of `order` that names a hole), every launch starts from result buffers filled with the byte 0xAA, and a hole's
+ * entry of hits_host comes back as that byte.  The other variants know no holes and refuse to run. */
+int vpt_lab_set_holes(vpt_ctx* ctx, const unsigned char* hole_host);
+/* The shadow kernels of the stream pipelines on the resident rays: ONE launch of k_trace_shadow through the product's launch_trace_shadow — the sky
+ * form (light = 0: visible <=> nothing is hit) or the light form (visible <=> the closest hit is triangle expect_host[i], a global triangle id; a
+ * ray with media_host[i] != 0 is also visible when it hits nothing at all) — over a stream packed the way the shade stage queues its shadow rays,
+ * with the kernel's own window ([1e-4, 1e6] on the direction as it is with ray_queries, [1e-5, 1000] on the normalised direction without; the
+ * resident set's tmin / tmax play no part).  The instantiation is the one the pipeline would run: the product's, the counting one when `visits`
+ * ({nodes, triangles}) is given, the validating ones under VPT_FLAG_LOCAL_HITS.  expect_host: n ids, light form only; media_host, hole_host: n
+ * bytes each or NULL; vis_host: n bytes out — 1 visible, 0 not, 0xAA for an entry the kernel did not write (a hole). */
+int vpt_lab_trace_shadow(vpt_ctx* ctx, uint32_t light, uint32_t ray_queries, const uint32_t* expect_host, const unsigned char* media_host,
+                         const unsigned char* hole_host, unsigned char* vis_host, uint64_t* visits);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from test_gpu_parity import assert_parity
+from trace_ray_sets import far_rays, scaled, scaled_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -29,24 +30,11 @@ def test_tiny_and_ragged_image_sizes(vpt, oracle, scenes, w, h, pipeline):
     assert np.array_equal(out8, ref8)       # bloom chain stops when a mip would fall below 2 px (PostProcessor.cpp:136-157)
 
 
-def scaled(sc, k):
-    s = copy.deepcopy(sc)
-    s.instances = [(m, mat, (np.diag([k, k, k, 1.0]) @ x).astype(np.float32)) for m, mat, x in s.instances]
-    v = np.linalg.inv(s.view_inverse.astype(np.float64)); cam = s.view_inverse.astype(np.float64).copy(); cam[:3, 3] *= k
-    s.view_inverse = cam.astype(np.float32)
-    return s
-
-
 @pytest.mark.parametrize("k", [1e-3, 1e3, 3.7e4])
 def test_scene_scale_does_not_break_the_quantised_bvh(vpt, oracle, scenes, k):
     """Random rays against the viking room scaled by k: closest hits equal the oracle's (its own BVH / brute force)."""
     sc = scaled(scenes("viking_room"), k)
-    rng = np.random.default_rng(3)
-    n = 60000
-    rays = np.zeros((n, 8), np.float32)
-    rays[:, 0:3] = rng.uniform(-2 * k, 2 * k, (n, 3))
-    d = rng.normal(size=(n, 3)); rays[:, 4:7] = d / np.linalg.norm(d, axis=1, keepdims=True)
-    rays[:, 3] = 1e-4 * k; rays[:, 7] = 1e6 * k
+    rays = scaled_rays(k)
     o = oracle.Oracle(sc, 8, 8); ref = o.trace_rays(rays); o.close()
     g = vpt.PathTracer(8, 8); g.set_scene(sc); got = g.trace_rays(rays); g.close()
     for f in ("t", "u", "v", "primitive", "instance"):
@@ -87,14 +75,7 @@ def test_rays_from_far_outside_the_scene(vpt, oracle, scenes, far):
     ray origin is larger than the triangles, and no fixed box padding can follow what the fp32 triangle test accepts;
     the integrator never starts a ray that far from the geometry it can hit: DESIGN.md §6.)"""
     sc = scenes("viking_room")
-    rng = np.random.default_rng(11)
-    n = 40000
-    d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
-    target = rng.uniform(-0.8, 0.8, (n, 3))
-    rays = np.zeros((n, 8), np.float32)
-    rays[:, 0:3] = target - d * far * 2.0
-    rays[:, 4:7] = d
-    rays[:, 3] = 1e-4; rays[:, 7] = 1e9
+    rays = far_rays(far)
     o = oracle.Oracle(sc, 8, 8); o.set_brute_force(True); ref = o.trace_rays(rays); o.close()   # no box test on the oracle side at all
     g = vpt.PathTracer(8, 8); g.set_scene(sc); got = g.trace_rays(rays); g.close()
     for f in ("t", "u", "v", "primitive", "instance"):

@@ -15,7 +15,7 @@ import pytest
 
 import material_scenes
 from test_gpu_parity import assert_parity
-from test_oracle_kat import random_rays
+from trace_ray_sets import affine_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -124,20 +124,7 @@ def test_closest_hits_on_affine_instances(vpt, oracle):
     non-uniformly scaled instances (t, u, v, primitive, instance all equal)."""
     sc, info = material_scenes.variant("affine_instances")
     material_scenes.check_preconditions(sc, info)
-    rng = np.random.default_rng(9)
-    parts = [random_rays(100000, 13, 8.0)]
-    for inst in sorted(set(info["mirrored"] + info["sheared"] + info["nonuniform"])):
-        M = sc.instances[inst][2].astype(np.float64)
-        v = sc.meshes[sc.instances[inst][0]][0]["position"].astype(np.float64)
-        lo, hi = v.min(0), v.max(0)
-        n = 20000
-        target = rng.uniform(lo, hi, (n, 3)) @ M[:3, :3].T + M[:3, 3]
-        origin = rng.uniform(-5.5, 5.5, (n, 3)) + np.array([0.0, 0.0, -5.8])
-        d = target - origin
-        r = np.zeros((n, 8), np.float32)
-        r[:, 0:3] = origin; r[:, 3] = 1e-4; r[:, 4:7] = d / np.linalg.norm(d, axis=1, keepdims=True); r[:, 7] = 1e6
-        parts.append(r)
-    rays = np.concatenate(parts)
+    rays = affine_rays(sc, info)
     o = oracle.Oracle(sc, 8, 8); o.set_brute_force(True); ref = o.trace_rays(rays); o.close()
     g = vpt.PathTracer(8, 8); g.set_scene(sc); got = g.trace_rays(rays); g.close()
     for k in ("t", "u", "v", "primitive", "instance"):

@@ -1,9 +1,10 @@
-"""The extend kernel alone (vpt_trace_rays) against the oracle's brute-force closest hit: (t,u,v) bit-exact,
-primitive/instance identical, ties and degenerate rays included."""
+"""vpt_trace_rays against the oracle's brute-force closest hit: (t,u,v) bit-exact, primitive/instance identical, ties and degenerate rays
+included.  vpt_trace_rays is k_first_hit (kernels_aux.hip), a per-lane trace_closest loop out of traverse.hpp; the kernels that trace the rays of
+the stream pipelines (k_trace_vote, k_trace_shadow) take the same ray sets (tests/trace_ray_sets.py) in tests/test_gpu_trace_stream.py."""
 import numpy as np
 import pytest
 
-from test_oracle_kat import random_rays
+from trace_ray_sets import axis_aligned_rays, random_rays, window_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -34,28 +35,11 @@ def test_random_rays(vpt, oracle, scenes, name, scale, n):
 
 def test_axis_aligned_and_degenerate_rays(vpt, oracle, scenes):
     """Zero direction components (0 * inf in slab tests), origins on walls, rays along box edges."""
-    sc = scenes("cornell_box")
-    rays = []
-    for ax in range(3):
-        for sgn in (-1.0, 1.0):
-            for ox in np.linspace(-6, 6, 25):
-                for oy in np.linspace(-6, 6, 25):
-                    o = [ox, oy, -5.8]
-                    d = [0.0, 0.0, 0.0]
-                    d[ax] = sgn
-                    rays.append(o + [1e-4] + d + [1e6])
-    rays = np.array(rays, np.float32)
-    # exact wall coordinates as origins (coplanar rays) and exact corner directions
-    extra = rays.copy()
-    extra[:, 0] = np.float32(5.709264755249023)
-    compare(vpt, oracle, sc, np.concatenate([rays, extra]))
+    compare(vpt, oracle, scenes("cornell_box"), axis_aligned_rays())
 
 
 def test_tmin_tmax_window(vpt, oracle, scenes):
-    rays = random_rays(50000, 8, 6.0)
-    rays[:, 3] = 2.0   # tmin beyond near hits
-    rays[:, 7] = 9.0   # tmax before far hits
-    ref, _ = compare(vpt, oracle, scenes("cornell_box_glass"), rays)
+    ref, _ = compare(vpt, oracle, scenes("cornell_box_glass"), window_rays())   # tmin 2.0 beyond near hits, tmax 9.0 before far hits
     hit = ref["t"] >= 0
     assert hit.any() and (ref["t"][hit] > 2.0).all() and (ref["t"][hit] < 9.0).all()
 

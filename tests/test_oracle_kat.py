@@ -6,6 +6,8 @@
 import numpy as np
 import pytest
 
+from trace_ray_sets import random_rays
+
 
 def test_reflection_lut_cells(oracle, vpt):
     lut = vpt.scenes.load_luts()[0]  # [z,y,x] 32x64x64
@@ -111,18 +113,6 @@ def test_black_env_tables(oracle, scenes):
     oracle.lib().orc_get_env_tables(o.h_, alias.ctypes.data, imp.ctypes.data, pdf.ctypes.data)
     assert alias[0] == 0 and imp[0] == 0 and pdf[0] == 0
     o.close()
-
-
-def random_rays(n, seed, scale=12.0):
-    rng = np.random.RandomState(seed)
-    r = np.zeros((n, 8), np.float32)
-    r[:, 0:3] = (rng.rand(n, 3) * 2 - 1) * scale
-    d = rng.randn(n, 3)
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    r[:, 4:7] = d
-    r[:, 3] = 1e-4
-    r[:, 7] = 1e6
-    return r
 
 
 @pytest.mark.parametrize("name", ["cornell_box", "cornell_box_glass", "viking_room"])

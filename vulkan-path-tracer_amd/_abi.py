@@ -356,6 +356,8 @@ PROTOTYPES = {
     "vpt_lab_set_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "vpt_lab_whole_culled": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vpt_lab_trace": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+    "vpt_lab_set_holes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vpt_lab_trace_shadow": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "vpt_lut_calculate": (C.c_int, [C.c_int] + [C.c_uint32] * 6 + [C.c_void_p]),
 }
 
@@ -363,7 +365,7 @@ PROTOTYPES = {
 COMM_ID_BYTES = 128
 
 
-LAB_ENTRY_POINTS = ("vpt_lab_set", "vpt_lab_set_rays", "vpt_lab_trace", "vpt_lab_whole_culled")   # include/vpt_lab.h: exported by the laboratory build only
+LAB_ENTRY_POINTS = ("vpt_lab_set", "vpt_lab_set_holes", "vpt_lab_set_rays", "vpt_lab_trace", "vpt_lab_trace_shadow", "vpt_lab_whole_culled")   # include/vpt_lab.h: exported by the laboratory build only
 
 
 def bind(lib):

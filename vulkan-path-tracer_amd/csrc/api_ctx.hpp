@@ -111,6 +111,9 @@ struct vpt_ctx {
     float4 *lab_ro = nullptr, *lab_rd = nullptr, *lab_hit = nullptr;
     uint32_t *lab_hinst = nullptr, *lab_order = nullptr;
     uint32_t lab_n = 0; float lab_tmin = 0.0f, lab_tmax = 0.0f;
+#if VPT_LAB
+    std::vector<unsigned char> lab_holes;   // vpt_lab_set_holes: empty, or lab_n bytes; the device's copy (TraceArgs::valid) is the second half of lab_order
+#endif
     std::vector<vpt_material> materials;
     std::vector<MeshDesc> meshes;
     std::vector<InstanceDesc> instances;

@@ -26,21 +26,50 @@ int vpt_lab_whole_culled(const vpt_ctx* c, uint64_t* out) {
     *out = c->main.h_ctr ? c->main.h_ctr->ctr.whole_culled : 0u;   // (the counters a batch copies to pinned memory behind its resolve: batch_resolve)
     return VPT_OK;
 }
+// Every buffer of the resident set is kLabGuard entries longer than the set: wave.hpp fetch_chunk's largest chunk, which is as far as a fetch step that
+// forgot the end of the stream could reach.  The guard holds rays a kernel can trace (zeros), entries of `order` and of the hole mask that name
+// themselves, and results filled with 0xAA before every launch: a launch that leaves another byte there has worked on entries beyond n, and fails.
+static constexpr uint32_t kLabGuard = 1024u;
+// (vote.hpp kHole / kRayHole: what a stream entry nobody wrote holds in a ray queue / in RD.z of a shadow-ray stream)
+static constexpr uint32_t kLabHole = 0xffffffffu, kLabRayHole = 0xfffffffeu;
+static int guard_untouched(vpt_ctx* c, const void* dev, size_t bytes) {
+    std::vector<unsigned char> g(bytes);
+    HIPCHK(c, hipMemcpy(g.data(), dev, bytes, hipMemcpyDeviceToHost));
+    for (unsigned char b : g) if (b != 0xAA) return fail(c, VPT_ERR_DEVICE, "the launch wrote results beyond the last ray of the set");
+    return VPT_OK;
+}
 int vpt_lab_set_rays(vpt_ctx* c, const vpt_ray* rays, uint32_t n) {
-    if (!c || !rays || n == 0) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c || !rays || n == 0 || n > 0xffffffffu - kLabGuard) return VPT_ERR_INVALID_ARGUMENT;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     free_lab(c);
-    std::vector<float4> ro(n), rd(n);
+    const size_t m = (size_t)n + kLabGuard;
+    std::vector<float4> ro(m, make_float4(0.0f, 0.0f, 0.0f, 0.0f)), rd(m, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     for (uint32_t i = 0; i < n; i++) {
         ro[i] = make_float4(rays[i].origin[0], rays[i].origin[1], rays[i].origin[2], 0.0f);
         rd[i] = make_float4(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2], 0.0f);
     }
-    HIPCHK(c, hipMalloc((void**)&c->lab_ro, (size_t)n * 16)); HIPCHK(c, hipMalloc((void**)&c->lab_rd, (size_t)n * 16));
-    HIPCHK(c, hipMalloc((void**)&c->lab_hit, (size_t)n * 16)); HIPCHK(c, hipMalloc((void**)&c->lab_hinst, (size_t)n * 4));
-    HIPCHK(c, hipMalloc((void**)&c->lab_order, (size_t)n * 4));
-    HIPCHK(c, hipMemcpy(c->lab_ro, ro.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->lab_rd, rd.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMalloc((void**)&c->lab_ro, m * 16)); HIPCHK(c, hipMalloc((void**)&c->lab_rd, m * 16));
+    HIPCHK(c, hipMalloc((void**)&c->lab_hit, m * 16)); HIPCHK(c, hipMalloc((void**)&c->lab_hinst, m * 4));
+    HIPCHK(c, hipMalloc((void**)&c->lab_order, m * 8));   // the caller's order | the hole mask as TraceArgs::valid wants it (vpt_lab_set_holes)
+    c->lab_holes.clear();
+    HIPCHK(c, hipMemcpy(c->lab_ro, ro.data(), m * 16, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->lab_rd, rd.data(), m * 16, hipMemcpyHostToDevice));
     c->lab_n = n; c->lab_tmin = rays[0].tmin; c->lab_tmax = rays[0].tmax;
+    return VPT_OK;
+}
+int vpt_lab_set_holes(vpt_ctx* c, const unsigned char* hole) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    if (c->lab_n == 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_lab_set_holes before vpt_lab_set_rays");
+    { int rd = quiesce(c); if (rd) return rd; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    c->lab_holes.clear();
+    if (!hole) return VPT_OK;
+    const uint32_t n = c->lab_n;
+    const size_t m = (size_t)n + kLabGuard;
+    std::vector<uint32_t> valid(m);
+    for (size_t i = 0; i < m; i++) valid[i] = (i < n && hole[i]) ? kLabHole : (uint32_t)i;
+    HIPCHK(c, hipMemcpy(c->lab_order + m, valid.data(), m * 4, hipMemcpyHostToDevice));
+    c->lab_holes.assign(hole, hole + n);
     return VPT_OK;
 }
 int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t* order, uint32_t param, uint32_t reps, vpt_hit* hits, float* best_ms,
@@ -68,10 +97,22 @@ int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t
         c->stats.bvh8_nodes = (uint32_t)n8.size();
     }
     const uint32_t n = c->lab_n;
+    const bool holes = !c->lab_holes.empty();
+    if (holes && variant != VPT_TRACE_VOTE) return fail(c, VPT_ERR_UNSUPPORTED, "only VPT_TRACE_VOTE knows holes: vpt_lab_set_holes(ctx, NULL) first");
     c->spill_dirty = true;   // traversal kernels run: vpt_get_stats recounts the spill regions
-    if (order) HIPCHK(c, hipMemcpy(c->lab_order, order, (size_t)n * 4, hipMemcpyHostToDevice));
+    const size_t m = (size_t)n + kLabGuard;
+    if (order) {   // (with holes: an entry that names a hole holds the hole word instead, as in a queue of the pipeline)
+        std::vector<uint32_t> o(m);
+        for (size_t i = 0; i < m; i++) o[i] = i < n ? order[i] : (uint32_t)i;
+        if (holes) for (uint32_t i = 0; i < n; i++) {
+            if (o[i] >= n) return fail(c, VPT_ERR_INVALID_ARGUMENT, "order_host is no permutation of the resident rays");
+            if (c->lab_holes[o[i]]) o[i] = kLabHole;
+        }
+        HIPCHK(c, hipMemcpy(c->lab_order, o.data(), m * 4, hipMemcpyHostToDevice));
+    }
     TraceArgs a{};
     a.ro = c->lab_ro; a.rd = c->lab_rd; a.order = order ? c->lab_order : nullptr; a.hit = c->lab_hit; a.hinst = c->lab_hinst;
+    a.valid = holes && !order ? c->lab_order + m : nullptr;
     a.n = n; a.head = &c->main.ctr->extend_head; a.tmin = c->lab_tmin; a.tmax = c->lab_tmax; a.normalize_dir = 0u; a.param = (variant == VPT_TRACE_POOL || variant == VPT_TRACE_PAIR) ? param : param & 0xfff1ffffu;
     a.cull = variant == VPT_TRACE_VOTE ? (param >> 17) & 1u : 0u;     // lab: bit 17 = stale-entry culling (closest-hit, VPT_TRACE_VOTE)
     a.one_tri = variant == VPT_TRACE_VOTE ? (param >> 19) & 1u : 0u;     // lab: bit 19 = one triangle per triangle step, as before round 4 (VPT_TRACE_VOTE, product vote parameters)
@@ -84,11 +125,17 @@ int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t
     for (uint32_t r = 0; r < reps + (visits ? 1u : 0u); r++) {
         const bool count = visits && r == reps;
         HIPCHK(c, hipMemsetAsync(c->main.ctr, 0, sizeof(Counters), c->main.stream));
+        // what a launch leaves untouched shows: the guard always, the whole set when it has holes
+        HIPCHK(c, hipMemsetAsync(c->lab_hit + (holes ? 0u : n), 0xAA, (holes ? m : kLabGuard) * 16, c->main.stream));
+        HIPCHK(c, hipMemsetAsync(c->lab_hinst + (holes ? 0u : n), 0xAA, (holes ? m : kLabGuard) * 4, c->main.stream));
         HIPCHK(c, hipEventRecord(e0, c->main.stream));
         launch_trace(c->main.stream, blocks, variant, any_hit != 0, count, lane_scene(c, c->main), a, c->main.ctr);
         HIPCHK(c, hipEventRecord(e1, c->main.stream));
         HIPCHK(c, hipStreamSynchronize(c->main.stream));
         HIPCHK(c, hipGetLastError());
+        int rg = guard_untouched(c, c->lab_hit + n, kLabGuard * 16);
+        if (!rg) rg = guard_untouched(c, c->lab_hinst + n, kLabGuard * 4);
+        if (rg) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rg; }
         float ms = 0.0f;
         HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
         if (!count) best = std::min(best, ms);
@@ -112,6 +159,65 @@ int vpt_lab_trace(vpt_ctx* c, uint32_t variant, uint32_t any_hit, const uint32_t
         }
     }
     return VPT_OK;
+}
+
+namespace {
+struct ShadowLabBuffers {   // what one vpt_lab_trace_shadow call allocates, freed however it ends
+    float4 *ro = nullptr, *rd = nullptr;
+    unsigned char* vis = nullptr;
+    StreamCounters* sctr = nullptr;
+    ~ShadowLabBuffers() { for (void* p : {(void*)ro, (void*)rd, (void*)vis, (void*)sctr}) if (p) (void)hipFree(p); }
+};
+}  // namespace
+int vpt_lab_trace_shadow(vpt_ctx* c, uint32_t light, uint32_t ray_queries, const uint32_t* expect, const unsigned char* media, const unsigned char* hole,
+                         unsigned char* vis, uint64_t* visits) {
+    if (!c || !vis || (light && !expect)) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c->has_scene) return fail(c, VPT_ERR_NO_SCENE, "no scene");
+    if (c->lds_scene) return fail(c, VPT_ERR_UNSUPPORTED, "the trace lab runs on scenes whose BVH lives in memory");
+    if (c->lab_n == 0) return fail(c, VPT_ERR_INVALID_ARGUMENT, "vpt_lab_trace_shadow before vpt_lab_set_rays");
+    if (light && !ray_queries) return fail(c, VPT_ERR_UNSUPPORTED, "without ray queries the pipeline queues no light rays");   // (shade_core.hpp)
+    const uint32_t n = c->lab_n;
+    if (light) for (uint32_t i = 0; i < n; i++)
+        if (expect[i] >= c->total_tris) return fail(c, VPT_ERR_INVALID_ARGUMENT, "expect_host: no such triangle");   // (the kernel looks it up in tri_slot_of_gid)
+    { int rd = quiesce(c); if (rd) return rd; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // the stream as shade_core queues it: RO = origin | d.x, RD = d.y, d.z, bits of the sampled triangle's id (sky rays: 0xffffffff; a hole: kRayHole), media flag
+    const size_t m = (size_t)n + kLabGuard;   // (the guard: sky rays of zeros, or light rays that expect ray 0's triangle)
+    float guard_id; { const uint32_t id = light ? expect[0] : 0xffffffffu; memcpy(&guard_id, &id, 4); }
+    std::vector<float4> o(n), d(n), ro(m, make_float4(0.0f, 0.0f, 0.0f, 0.0f)), rd(m, make_float4(0.0f, 0.0f, guard_id, 0.0f));
+    HIPCHK(c, hipMemcpy(o.data(), c->lab_ro, (size_t)n * 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(d.data(), c->lab_rd, (size_t)n * 16, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t id = (hole && hole[i]) ? kLabRayHole : light ? expect[i] : 0xffffffffu;
+        float idf; memcpy(&idf, &id, 4);
+        ro[i] = make_float4(o[i].x, o[i].y, o[i].z, d[i].x);
+        rd[i] = make_float4(d[i].y, d[i].z, idf, (media && media[i]) ? 1.0f : 0.0f);
+    }
+    ShadowLabBuffers b;
+    HIPCHK(c, hipMalloc((void**)&b.ro, m * 16)); HIPCHK(c, hipMalloc((void**)&b.rd, m * 16));
+    HIPCHK(c, hipMalloc((void**)&b.vis, m)); HIPCHK(c, hipMalloc((void**)&b.sctr, sizeof(StreamCounters)));
+    HIPCHK(c, hipMemcpy(b.ro, ro.data(), m * 16, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b.rd, rd.data(), m * 16, hipMemcpyHostToDevice));
+    StreamCounters* const sc = b.sctr;
+    hipStream_t s = c->main.stream;
+    HIPCHK(c, hipMemsetAsync(b.vis, 0xAA, m, s));   // untouched entries show
+    HIPCHK(c, hipMemsetAsync(sc, 0, sizeof(StreamCounters), s));   // (the cursor among them)
+    HIPCHK(c, hipMemcpyAsync(light ? &sc->light_len.v : &sc->sky_len.v, &n, 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->main.ctr, 0, sizeof(Counters), s));
+    StreamState ss{};
+    ss.SKO = b.ro; ss.SKD = b.rd; ss.LTO = b.ro; ss.LTD = b.rd; ss.vis_sky = b.vis; ss.vis_light = b.vis; ss.cap = n;
+    c->spill_dirty = true;
+    launch_trace_shadow(s, (uint32_t)c->shadow_blocks, light != 0u, visits != nullptr, lane_scene(c, c->main), ss, c->main.ctr, sc, c->vote_param, ray_queries ? 1u : 0u);
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    if (visits) {
+        Counters h{};
+        HIPCHK(c, hipMemcpy(&h, c->main.ctr, sizeof(Counters), hipMemcpyDeviceToHost));
+        visits[0] = h.stat_shadow_nodes; visits[1] = h.stat_shadow_tris;
+    }
+    HIPCHK(c, memset_now(s, c->main.ctr, 0, sizeof(Counters)));
+    HIPCHK(c, hipMemcpy(vis, b.vis, (size_t)n, hipMemcpyDeviceToHost));
+    return guard_untouched(c, b.vis + n, kLabGuard);
 }
 
 }  // extern "C"
