@@ -55,9 +55,15 @@ int batch_begin(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, 
     b.primary_grid = grids.primary; b.tail_grid = grids.tail;
     c->spill_dirty = true;
     const uint32_t n_slots = batch_slots(c->P, frames, dispatch_base);
+    // A whole-path batch whose camera sees the scene's box inside a rectangle of the image (camera_cull.hpp) deals its launch indices over the
+    // samples inside it alone (whole_deal.hpp); the same rectangle for every part.
+    const cull::Rect wrect = sd.kind == Kind::Whole ? whole_cull_rect(c) : cull::everything(c->P.width, c->P.height);
+    uint32_t n_split_dealt = 0;   // split-screen dispatch with a rectangle: the batch's launch indices
     if (c->P.split > 1) {   // launch-grid prefix sums of the batch's dispatches
         std::vector<uint32_t> off(frames + 1, 0u);
-        for (uint32_t k = 0; k < frames; k++) off[k + 1] = off[k] + split_dispatch_slots(c->P, dispatch_base + k);
+        for (uint32_t k = 0; k < frames; k++)
+            off[k + 1] = off[k] + (wrect.all ? split_dispatch_slots(c->P, dispatch_base + k) : deal::split_rect_px(wrect, (dispatch_base + k) % (c->P.split * c->P.split), c->P.split));
+        n_split_dealt = off[frames];
         HIPCHK(c, hipMemcpyAsync(c->d_launch_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipStreamSynchronize(s));  // `off` is a stack-lifetime staging buffer
     }
@@ -77,16 +83,28 @@ int batch_begin(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, 
     const DeviceScene dsc = lane_scene(c, L);
     if (sd.kind == Kind::Whole) {  // the batch's paths from camera ray to their end, one launch per part; no queue is written, alive3[] stays 0 for the resolve's guard
         b.parity = 1; b.k3 = 1; b.iter = 1;
-        const cull::Packed rect = cull::pack(whole_cull_rect(c));   // samples outside it start no path (camera_cull.hpp); the same for every part
+        const bool dealt = !wrect.all, split = c->P.split > 1;
+        const cull::Packed rect = cull::pack(wrect);
         for (uint32_t i = 0; i < sd.parts.n; i++) {
-            const uint32_t first = sd.parts.first[i], n_part = sd.parts.n > 1u ? (sd.parts.first[i + 1] - first) * c->P.shard_pixels : n_slots;
+            // a part's launch indices: its frames' samples — those inside the rectangle, where there is one; the others are the constant the launch adds
+            // to its closest-hit rays (parts are counted in frames, and a split-screen batch is never split into parts: path_plan.hpp decide)
+            const uint32_t first = sd.parts.first[i], part_frames = sd.parts.n > 1u ? sd.parts.first[i + 1] - first : frames;
+            const uint32_t part_slots = sd.parts.n > 1u ? part_frames * c->P.shard_pixels : n_slots;
+            const deal::Deal dl = dealt ? deal::make(wrect, c->P.shard_rank, c->P.shard_count, c->P.width, part_slots) : deal::Deal{};
+            const uint32_t n_part = !dealt ? part_slots : split ? n_split_dealt : part_frames * dl.rect_px;
+            const uint64_t culled = part_slots - n_part;
+            // The zero frame sums of the samples outside: the launch's waves write them, in runs, as they deal the rows of the rectangle (whole_deal.hpp
+            // run_after).  Where no wave does — the rectangle holds none of this context's samples (n_part == 0), or split-screen dispatch, whose chunks have
+            // no such runs — a fill of the part's sums does.  A part without a sample inside is still launched, one block with no index to deal: its one
+            // lane adds the part's culled rays on the device, so a replayed graph (enqueue_graph) counts them in every replay as it counts every other ray.
+            if (dealt && (n_part == 0u || split)) HIPCHK(c, hipMemsetAsync(part_state(c, L, first).ACC, 0, (size_t)(split ? frames * c->P.shard_pixels : part_slots) * 16, s));
             const uint32_t grid = std::max(1u, std::min<uint32_t>((uint32_t)std::min(c->whole_blocks, b.primary_grid), (n_part + 255u) / 256u));   // (blocks of 256 lanes)
             // tiles of 64 samples: `rounds` per wave; mode 0: the first round static, mode 1: all but the last, mode 2: half of them; the rest through the counter
             const uint32_t n_waves = grid * 4u, rounds = ((n_part + 63u) / 64u) / n_waves, mode = c->lab_whole_sched >> 4;
             const uint32_t static_rounds = (mode == 0u || mode == 3u) ? std::min(rounds, 1u) : mode == 1u ? (rounds >= 2u ? rounds - 1u : 0u) : rounds / 2u;
             // (mode 3: mode 0 with guided chunks — at most the given tiles per atomic, fewer towards the end of the batch)
             if (i) HIPCHK(c, hipMemsetAsync(&L.ctr->extend_head, 0, 4, s));   // the tile cursor starts at 0 in every part
-            TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, part_state(c, L, first), L.ctr, n_part, dispatch_base + first, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u), rect.x, rect.y));
+            TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, part_state(c, L, first), L.ctr, n_part, dispatch_base + first, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u), rect, dl, culled));
             if (i + 1u < sd.parts.n) {   // this part's resolve on the second stream, beside the next part's launch (the last part's: batch_resolve)
                 HIPCHK(c, hipEventRecord(L.ev_shade, s));
                 HIPCHK(c, hipStreamWaitEvent(L.stream2, L.ev_shade, 0));

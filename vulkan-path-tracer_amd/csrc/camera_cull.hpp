@@ -1,6 +1,6 @@
 // camera_cull.hpp — which pixels' camera rays can reach the scene at all: a rectangle of the image outside which no camera ray, whatever its
-// jitter, enters the scene's box.  The whole-path kernel (kernels_whole.hip k_whole) starts no path for a sample outside it: it writes the
-// sample's frame sum, which is exactly zero, and takes the next one.  screen_bound is host code in double (api_render.hip batch_begin calls it
+// jitter, enters the scene's box.  The whole-path kernel (kernels_whole.hip k_whole) starts no path for a sample outside it: its launch
+// indices run over the samples inside alone (whole_deal.hpp), and the others' frame sum, which is exactly zero, is written in runs.  screen_bound is host code in double (api_render.hip batch_begin calls it
 // once per batch); Packed / outside are what the kernel sees.  Plain arithmetic, compiled for the device and — by
 // tests/tools/camera_cull_driver.cpp — for the host (tests/test_camera_cull_cpu.py).  k_bounce<FIRST> and k_raygen_stream do not use it yet;
 // nothing here knows of k_whole.

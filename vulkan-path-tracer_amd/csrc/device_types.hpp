@@ -290,6 +290,7 @@ struct alignas(256) HotWord {
 // (ClosestHit.slang:20, Miss.slang:8).  kShadePlain promises what its kernel instantiation relies on: every value texture
 // and the normal map of the material are 1x1 (MatResolved.flags == 3), so no texel is ever fetched; the other hit classes
 // run the general closest-hit code and differ only in what their waves have in common.
+constexpr uint32_t kMaxDepthLimit = 1000000u;   // the largest vpt_params.max_depth vpt_set_params admits: the "path ended" marker (shading.hpp kMaxDepthMarker; shade_core.hpp's miss shader leans on it)
 constexpr uint32_t kShadeMiss = 0, kShadePlain = 1, kShadeTextured = 2, kShadeGlass = 3, kShadeEmissive = 4, kShadeClasses = 5;
 constexpr int kShadeAny = -1;  // template value: no class knowledge (fused kernels, round-1 shade stage)
 

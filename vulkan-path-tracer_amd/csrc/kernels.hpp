@@ -3,6 +3,7 @@
 #include "device_types.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
+#include "whole_deal.hpp"   // + camera_cull.hpp
 #include "../../include/vpt_lab.h"   // VPT_TRACE_* / VPT_LAB_* constants (the functions exist in the laboratory build only)
 #ifndef VPT_LAB
 #define VPT_LAB 0
@@ -15,7 +16,7 @@ void launch_bounce(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, b
                    uint32_t dispatch_base, uint32_t k3, bool plain = false);
 int bounce_blocks_per_cu(bool lds_scene, const DeviceScene& sc, bool plain = false);
 void launch_whole(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, Counters* ctr, uint32_t n_slots,
-                  uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles, uint32_t cull_x, uint32_t cull_y);   // cull_*: camera_cull.hpp Packed
+                  uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles, cull::Packed rect, const deal::Deal& deal, uint64_t culled);   // rect "everything": n_slots slots; else n_slots launch indices over the rectangle, zeros for the other slots of deal.slots (whole_deal.hpp)
 int whole_blocks_per_cu(const DeviceScene& sc, bool plain);
 // the rest of a streams batch in one launch (kernels_finish.hip k_finish): every path of queue[parity] run to its end
 void launch_finish(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, const StreamState& ss, const uint32_t* queue,

@@ -23,8 +23,10 @@ template <> struct OneSampleFrames<VPT_KERNARG WholeParams> { static constexpr b
 // only the per-sample frame sums (ACC) do.  One launch per batch (or part of one) instead of max_depth: what a 1-frame batch at 1080p needs (its
 // later bounces are launches of 10^5 paths that do not fill the chip, vpt_render_async).
 // A sample whose pixel lies outside the launch's screen rectangle of the scene's box (camera_cull.hpp; the host bounds the box per batch:
-// api_render.hip batch_begin) never becomes a path: its camera ray could only miss, so the refill step writes its zero frame sum and counts
-// its one ray (53.8 % of the samples of Cornell 1080p: profiles/r18_whole_camera_cull_ab.md).
+// api_render.hip batch_begin) never becomes a path, and the kernel never sees it: its camera ray could only miss, so the launch's indices are
+// dealt over the samples inside the rectangle alone (whole_deal.hpp), the zero frame sums of the others are written in runs of whole-wave stores
+// by the waves that deal the rectangle's rows, and their one ray each is a constant the launch adds to its count (53.8 % of the samples of Cornell
+// 1080p: profiles/r18_whole_camera_cull_ab.md, profiles/r21_whole_deal_ab.md).
 // A wave alternates two steps, each on full lanes:
 //   trace   every lane holds a ray — a survivor of the shade step or a fresh camera ray — and finds its closest hit; misses run the
 //           miss shader and end there, hits are parked in a wave-private ring in LDS (hit record + the path's registers);
@@ -38,6 +40,15 @@ __device__ __forceinline__ V3 whole_finish(const Pm& P, const Ps& ps, uint32_t s
     if (o.terminated) ps.ACC[slot] = finite3(light) ? f4(v3s(0.0f) + light, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // end of the sample: the frame sum
     return light;
 }
+// Zero frame sums for slots [first, end), every lane of the wave storing (wave-uniform arguments).  A function of its own, not inlined: inlined, its
+// registers raised the headline instantiation from 160 to 167 VGPRs, k_resolve (24) no longer fitted beside three of its waves on a SIMD, and a
+// part's resolve ran past the next launch (profiles/r21_whole_deal_ab.md).  The margin is thin — 158 VGPRs reported, 160 allocated, and 8 B of
+// scratch reserved for the call — and a compiler update can take it back without a word: tests/tools/spill_report.py shows the figure
+// (k_whole<false, false, true> must stay at or below 160 VGPRs).
+__device__ __attribute__((noinline)) void whole_zero_run(float4* acc, uint32_t first, uint32_t end) {
+    for (uint32_t i = first + lane_id(); i < end; i += 64u) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
 // Samples are dealt in tiles of 64 (consecutive pixels of a row).  Wave w of W takes tiles w, w + W, ... for the first `static_rounds` rounds
 // without an atomic, and the tiles behind them `chunk_tiles` at a time through ctr->extend_head (the host picks both: api_render.hip batch_begin).
 // (Measured and not kept: one-wave blocks, which leave the CU as soon as THEIR paths have ended and so let the next frame's launch in earlier —
@@ -84,9 +95,6 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
     uint32_t hit_head = 0u, hit_count = 0u;   // wave-uniform
     TravStats st, sst; st.nodes = 0; st.tris = 0; sst.nodes = 0; sst.tris = 0;
     uint32_t w_paths = 0u, w_rays = 0u, w_hits0 = 0u, w_alive0 = 0u, w_rays0 = 0u, w_parked = 0u;   // wave totals (uniform); *0: bounce 0 only; parked: hits of later bounces (their pathLight waits in ACC)
-#if VPT_LAB
-    uint32_t w_culled = 0u;   // samples the refill step finished without a path (the laboratory reports them: vpt_lab_whole_culled)
-#endif
     // the lane's path between two steps
     bool has_ray = false;
     uint32_t slot = 0u, rng_s = 0u, depth = 0u;
@@ -155,11 +163,9 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
             w_alive0 += (uint32_t)__popcll(__ballot(first && alive));
         }
         // ---- refill: free lanes take the next unstarted samples from the front of the wave's buffer; when it runs out, ALL lanes take the next
-        // tile of launch indices.  A sample whose pixel lies outside the launch's rectangle (camera_cull.hpp: no camera ray of that pixel reaches the
-        // scene's box) ends where it stands — its frame sum is exactly zero, and it counts as the one closest-hit ray its path would have been;
-        // the others get their camera rays, compacted into the buffer by a ballot.  The wave goes on taking tiles until its free lanes are
-        // served or it is out of samples: a run of background tiles sends no trace step out with idle lanes.  (Per-lane test and ballot, not a
-        // decomposition of the tile against the rectangle: profiles/REJECTED.md r11, r16.)
+        // tile of launch indices and write their camera rays into the buffer.  A launch with a rectangle (camera_cull.hpp) deals its indices over
+        // the samples inside it (whole_deal.hpp): a lane takes its index apart by the rectangle's size and width, where a launch without one divides
+        // by shard_pixels and width (pixel_of_slot).  Either way every index is a path.
         if (!refill::exhausted(cur, fresh)) {
 #pragma unroll 1
             for (;;) {
@@ -176,41 +182,54 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
                     const uint32_t g = refill::gen_count(cur);
                     const uint32_t dispatch_base = uP.dispatch_base_dev ? *uP.dispatch_base_dev : ka->dispatch_base;   // (a replayed graph: the batch's first dispatch index lives in device memory)
                     uint32_t gslot = 0u, x = 0u, y = 0u, f = 0u;
-                    // (a launch without a rectangle pays nothing for the test: `bounded` comes from two argument words, a scalar branch)
+                    // (a launch without a rectangle pays nothing for the other decode: `bounded` comes from two argument words, a scalar branch)
                     const VPT_KERNARG WholeLaunch* kl = (const VPT_KERNARG WholeLaunch*)ka;
                     const cull::Packed rect{kl->cull_x, kl->cull_y};
-                    // The counting instantiations have no test at all — the library's size bound (tests/test_abi.py) has no room for it five times — and the
-                    // host gives their launches no rectangle (api_render.hip whole_cull_rect): their figures are those of the search itself.
+                    // The counting instantiations have one decode only — the library's size bound (tests/test_abi.py) has no room for the other five times —
+                    // and the host gives their launches no rectangle (api_render.hip whole_cull_rect): their figures are those of the search itself.
                     const bool bounded = !COUNT && (rect.x != cull::kAxisAll || rect.y != cull::kAxisAll);
-                    bool keep = lane_id() < g;
-                    if (keep) {
-                        launch_pixel(uP, cur.w_next + lane_id(), dispatch_base, gslot, x, y, f);
-                        if (bounded && cull::outside(rect, x, y)) {
-                            keep = false;
-                            ups.ACC[gslot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                        }
-                    }
-                    const unsigned long long m_keep = bounded ? __ballot(keep) : ~0ull >> (64u - g);   // (g >= 1: the range is not empty)
-                    if (keep) {
+                    bool row_end = false, at_frame_end = false;
+                    if (lane_id() < g) {
+                        const uint32_t li = cur.w_next + lane_id();
+                        if (uP.split != 1u) {   // split-screen dispatch: one decode, over the rectangle or the image (not what anything is timed on)
+                            const uint32_t x0 = bounded ? cull::axis_first(rect.x) : 0u, y0 = bounded ? cull::axis_first(rect.y) : 0u;
+                            deal::decode_split(x0, bounded ? x0 + cull::axis_span(rect.x) : uP.width - 1u, y0, bounded ? y0 + cull::axis_span(rect.y) : uP.height - 1u,
+                                               uP.split, uP.width, uP.shard_pixels, uP.launch_off, dispatch_base, li, gslot, x, y, f);
+                        } else if (bounded) {
+                            const deal::Deal d{kl->deal.x0, kl->deal.rw, kl->deal.ys0, kl->deal.rect_px, 0u, kl->deal.last_in_frame, 0u, 0u};   // (argument words: scalar loads)
+                            deal::decode(d, uP.shard_pixels, uP.width, uP.shard_rank, uP.shard_count, li, gslot, x, y, f);
+                            row_end = x == kl->deal.x0 + kl->deal.rw - 1u; at_frame_end = deal::frame_end(d, uP.shard_pixels, f, gslot);
+                        } else { gslot = li; pixel_of_slot(uP, li, x, y, f); }
                         const uint32_t seed = pcg_hash(uP.base_seed + dispatch_base + f);  // PathTracer.cpp:139 with an explicit seed
                         Rng r; r.s = y + uP.width * x + seed;                              // RayGen.slang:28
                         V3 go, gd;
                         camera_ray(cam, r, x, y, go, gd);
-                        const uint32_t j = bounded ? lanes_below(m_keep) : lane_id();
+                        const uint32_t j = lane_id();
                         f_slot[wave][j] = gslot; f_rng[wave][j] = r.s;
                         f_ox[wave][j] = go.x; f_oy[wave][j] = go.y; f_oz[wave][j] = go.z;
                         f_dx[wave][j] = gd.x; f_dy[wave][j] = gd.y; f_dz[wave][j] = gd.z;
                     }
-                    const uint32_t kept = (uint32_t)__popcll(m_keep);
-                    w_paths += g - kept;
-#if VPT_LAB
-                    w_culled += g - kept;
-#endif
-                    refill::generated_kept(cur, fresh, g, kept);
+                    const bool first_tile = cur.w_next == 0u;
+                    refill::generated(cur, fresh, g);
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    if (kept == 0u) continue;   // a tile of background: the next one
+                    // The samples outside the rectangle: their zero frame sums, in the runs between the rectangle's rows (whole_deal.hpp frame_end and run_after, on
+                    // wave-uniform values).  The wave that deals a row's last sample writes the run behind it, and the one that deals index 0 the slots before.
+                    if (bounded && uP.split == 1u) {
+                        unsigned long long m_end = __ballot(row_end);
+                        const unsigned long long m_last = __ballot(at_frame_end);
+                        if (first_tile)
+                            whole_zero_run(ups.ACC, 0u, kl->deal.head);
+                        const deal::Deal dz{kl->deal.x0, kl->deal.rw, kl->deal.ys0, kl->deal.rect_px, kl->deal.gap, kl->deal.last_in_frame, kl->deal.head, kl->deal.slots};
+                        while (m_end != 0ull) {
+                            const uint32_t b = (uint32_t)__builtin_ctzll(m_end);
+                            uint32_t first, end;
+                            deal::run_after(dz, uP.shard_pixels, __builtin_amdgcn_readfirstlane(f_slot[wave][b]), ((m_last >> b) & 1ull) != 0ull, first, end);
+                            m_end &= m_end - 1ull;
+                            whole_zero_run(ups.ACC, first, end);
+                        }
+                    }
                 }
                 const uint32_t q = fresh.head + lanes_below(m_free);
                 refill::pop(fresh, (uint32_t)__popcll(m_free));
@@ -269,9 +288,17 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
         if (w_alive0) atomicAdd(&ctr->stat_primary_alive, (unsigned long long)w_alive0);
         if (w_rays0) atomicAdd(&ctr->stat_primary_rays, (unsigned long long)w_rays0);
         if (w_parked) atomicAdd(&ctr->stat_connect, (unsigned long long)w_parked);   // vpt_stats.connect_paths: here, the hits whose pathLight made the round trip through ACC
+    }
+    // The samples outside the launch's rectangle, which no lane ever saw: one closest-hit ray each, as the paths they would have been.  The host
+    // counted them (whole_deal.hpp culled); one lane of the launch adds the figure.
+    if (!COUNT && blockIdx.x == 0u && threadIdx.x == 0u) {
+        const unsigned long long culled = ((const VPT_KERNARG WholeLaunch*)ka)->culled;
+        if (culled) {
+            atomicAdd(&ctr->stat_closest, culled);
 #if VPT_LAB
-        if (w_culled) atomicAdd(&ctr->whole_culled, w_culled);
+            atomicAdd(&ctr->whole_culled, (uint32_t)culled);   // (the laboratory reports them: vpt_lab_whole_culled)
 #endif
+        }
     }
     if (COUNT) {
         atomicAdd(&ctr->stat_nodes, (unsigned long long)st.nodes);
@@ -283,7 +310,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
 
 // Whole paths in one launch (k_whole): LDS-resident scenes without media, one sample per pixel and frame.
 void launch_whole(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, Counters* ctr, uint32_t n_slots,
-                  uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles, uint32_t cull_x, uint32_t cull_y) {
+                  uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles, cull::Packed rect, const deal::Deal& deal, uint64_t culled) {
     const size_t lds = traverse_lds_bytes(sc, true, kWholeStackRows);
     const dim3 g(blocks), b(kTraverseBlock);
     // one launch site for the five instantiations (the argument marshalling is host code the library's size bound pays for five times otherwise)
@@ -291,7 +318,7 @@ void launch_whole(hipStream_t s, uint32_t blocks, bool count, const DeviceScene&
     if (plain && !count && !sc.strict_hits && sc.env_black) k = k_whole<false, false, true>;
     else if (sc.strict_hits) k = count ? k_whole<true, true, false> : k_whole<false, true, false>;
     else k = count ? k_whole<true, false, false> : k_whole<false, false, false>;
-    hipLaunchKernelGGL(k, g, b, lds, s, WholeLaunch{WholeArgs{sc, P, ps, ctr, n_slots, dispatch_base, static_rounds, chunk_tiles}, cull_x, cull_y});
+    hipLaunchKernelGGL(k, g, b, lds, s, WholeLaunch{WholeArgs{sc, P, ps, ctr, n_slots, dispatch_base, static_rounds, chunk_tiles}, rect.x, rect.y, deal, culled});
 }
 int whole_blocks_per_cu(const DeviceScene& sc, bool plain) {
     int nb = 0;

@@ -223,6 +223,15 @@ __device__ __forceinline__ void shade_core(const Sc& sc, const Pm& P, const Ps& 
         if (P.flags & VPT_FLAG_FURNACE) emitted = v3s(1.0f);
         if ((P.flags & VPT_FLAG_SKY_MIS) && depth > 0) emitted = emitted * power_heuristics(prev_pdf, cp.w);
         new_depth = kMaxDepthMarker;  // payload.BxDF / PDF stay stale; the path ends here
+        // A caller that knows all of its paths missed and runs one-sample frames (the whole-path kernel's trace step) reads `emitted`, `cflags` and
+        // `terminated` alone (kernels_whole.hip whole_finish), and the tail below can only answer one thing: vpt_set_params admits no max_depth
+        // above kMaxDepthLimit == kMaxDepthMarker, so !(new_depth < P.max_depth) holds and the path is terminated whatever the roulette draws;
+        // no want flag is set here and new_depth != 1.  The compiler cannot know the bound and would keep the throughput, its reciprocal and the draw.
+        if constexpr (!VOL && CLS == (int)kShadeMiss && OneSampleFrames<Pm>::value) {
+            static_assert(kMaxDepthLimit <= kMaxDepthMarker, "a miss must end its path whatever max_depth is");
+            out.alive = false; out.terminated = true; out.cflags = kCF_Clamp | kCF_Finalize; out.emitted = emitted;
+            return;
+        }
     } else {
         // ---- ClosestHit.slang:20-378
         V3 rd = normalize(pdir);  // WorldRayDirection()

@@ -14,6 +14,7 @@
 #include <stddef.h>
 
 #include "device_types.hpp"
+#include "whole_deal.hpp"
 
 namespace vpt {
 
@@ -27,11 +28,15 @@ struct WholeArgs {
 };
 
 // What a launch hands over: the arguments, and behind them the rectangle of the image outside which no camera ray can reach the scene, as
-// camera_cull.hpp packs it (cull::Packed; both words cull::kAxisAll: every sample runs).  The kernel's one parameter is this struct, so a
-// WholeArgs still lies at offset 0 of the argument segment.
+// camera_cull.hpp packs it (cull::Packed; both words cull::kAxisAll: every sample runs, launch index = slot).  With a rectangle the launch's
+// indices run over the samples inside it alone (whole_deal.hpp: `deal`, a.n_slots counts those; the others get their zero frame sums in runs), and
+// `culled` is what the launch adds to the closest-hit rays for the samples it never sees.  The kernel's one parameter is this struct, so a WholeArgs still lies at offset 0 of the
+// argument segment.
 struct WholeLaunch {
     WholeArgs a;
     uint32_t cull_x, cull_y;
+    deal::Deal deal;
+    unsigned long long culled;
 };
 static_assert(offsetof(WholeLaunch, a) == 0, "the loop reads the argument segment as a WholeArgs");
 

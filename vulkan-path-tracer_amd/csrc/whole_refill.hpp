@@ -8,8 +8,8 @@
 // A wave never generates a camera ray on part of its lanes: when its free lanes want more rays than its buffer holds they first take
 // what is left (pop), and then ALL lanes generate the next kTile launch indices of the wave's range — lane j takes w_next + j, live
 // where j < gen_count() — into the buffer, from whose front the free lanes go on popping.  The buffer is only ever filled when it is
-// empty, so `head` runs from 0 and it needs no wrap.  Launch indices whose pixel cannot see the scene (camera_cull.hpp) get no ray: the pass
-// finishes them, writes the others' rays compacted (generated_kept), and the wave takes tiles until its free lanes are served.
+// empty, so `head` runs from 0 and it needs no wrap.  Every launch index is a path: a launch with a screen rectangle (camera_cull.hpp) has
+// no index for a sample outside it (whole_deal.hpp).
 // A wave is out of fresh samples when its cursor is done AND its buffer is empty;
 // the cursor is only asked for more with an empty buffer, so a wave cannot stop with entries left.
 #pragma once
@@ -77,10 +77,6 @@ VPT_HD Fresh make_fresh() { Fresh f; f.head = 0u; f.count = 0u; return f; }
 // Lanes that generate in a pass over a non-empty range: lane j < gen_count takes launch index w_next + j and writes entry j.
 VPT_HD uint32_t gen_count(const Cursor& c) { const uint32_t left = c.w_end - c.w_next; return left < kTile ? left : kTile; }
 VPT_HD void generated(Cursor& c, Fresh& f, uint32_t g) { c.w_next += g; f.head = 0u; f.count = g; }
-// The same pass when only `kept` <= g of the g launch indices got a ray (camera_cull.hpp: the others can reach nothing and were finished where they
-// stood): the cursor still moves by g, and the kept rays lie compacted in entries 0 .. kept - 1, in lane order.  kept may be 0: the buffer stays
-// empty and the wave takes its next tile.
-VPT_HD void generated_kept(Cursor& c, Fresh& f, uint32_t g, uint32_t kept) { c.w_next += g; f.head = 0u; f.count = kept; }
 // `want` free lanes pop: the lane with r free lanes below it takes entry head_before + r when r < the returned count.
 VPT_HD uint32_t pop(Fresh& f, uint32_t want) {
     const uint32_t k = want < f.count ? want : f.count;
