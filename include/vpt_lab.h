@@ -48,7 +48,9 @@ int vpt_lab_set_rays(vpt_ctx* ctx, const vpt_ray* rays_host, uint32_t n);
  *                         library's rule (path_plan.hpp decide: only batches of the headline's order of size are split).  Captured batches, batches on
  *                         an extra lane and split-screen dispatches always run as one part
  *   VPT_LAB_WHOLE_CULL    0: a whole-path launch starts a path for every sample, also where no camera ray can reach the scene (vpt.h
- *                         vpt_get_whole_cull then answers the whole image); 1, the default: samples outside that rectangle get their zero without a path */
+ *                         vpt_get_whole_cull then answers the whole image); 1, the default: samples outside that rectangle get their zero without a path
+ *   VPT_LAB_NARROW_OFF    1: a whole-path launch flags no child word of its LDS tree, so every node step is the four-wide one (node_step.hpp); 0, the
+ *                         default: the closest-hit search of the PLAIN instantiation takes the two-slot step at nodes that use slots 0 and 1 only */
 #define VPT_LAB_LANES 1u
 #define VPT_LAB_LANE_GRID 2u
 #define VPT_LAB_TAIL_GRID 3u
@@ -56,6 +58,7 @@ int vpt_lab_set_rays(vpt_ctx* ctx, const vpt_ray* rays_host, uint32_t n);
 #define VPT_LAB_WHOLE_SCHED 5u
 #define VPT_LAB_WHOLE_PARTS 6u
 #define VPT_LAB_WHOLE_CULL 7u
+#define VPT_LAB_NARROW_OFF 8u
 int vpt_lab_set(vpt_ctx* ctx, uint32_t key, uint32_t value);
 /* Samples the latest blocking batch on the main lane (vpt_render) finished without a path because their pixel lies outside vpt_get_whole_cull's
  * rectangle; 0 for a batch that was not a whole-path batch.  A 32-bit count on the device: batches of the headline's size stay below it. */

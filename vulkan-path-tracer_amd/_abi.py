@@ -23,7 +23,7 @@ KERNEL_NAMES = ["primary", "extend", "shade", "connect", "bounce", "resolve", "b
 KERNEL_COUNT = 10
 PIPELINE_AUTO, PIPELINE_FUSED, PIPELINE_STAGED = 0, 1, 2
 PIPELINE_STAGED_R1, PIPELINE_STAGED_SORTED, PIPELINE_WHOLE = 3, 4, 5
-LAB_LANES, LAB_LANE_GRID, LAB_TAIL_GRID, LAB_WHOLE_FRAMES, LAB_WHOLE_SCHED, LAB_WHOLE_PARTS, LAB_WHOLE_CULL = 1, 2, 3, 4, 5, 6, 7
+LAB_LANES, LAB_LANE_GRID, LAB_TAIL_GRID, LAB_WHOLE_FRAMES, LAB_WHOLE_SCHED, LAB_WHOLE_PARTS, LAB_WHOLE_CULL, LAB_NARROW_OFF = 1, 2, 3, 4, 5, 6, 7, 8
 ASYNC_MAX_BOUNCES = 32
 
 

@@ -161,6 +161,7 @@ struct vpt_ctx {
     // root after vpt_set_instance_transforms: what camera_cull.hpp bounds on the screen for every whole-path batch (whole_cull_rect).
     cull::WorldBox whole_box{};
     bool lab_whole_cull = true;      // false: whole-path batches skip no sample (VPT_LAB_WHOLE_CULL 0)
+    bool lab_narrow_off = false;     // true: whole-path launches flag no child word, every node step is four-wide (VPT_LAB_NARROW_OFF 1)
     bool depth_bounded = true;   // every path ends within max_depth * samples_per_frame bounces (no material scatters inside a medium): see vpt_render_async
     // asynchronous batches (vpt_render_async / vpt_postprocess_device / vpt_wait)
     hipEvent_t tick_ev[kTickets] = {};

@@ -17,6 +17,7 @@ int vpt_lab_set(vpt_ctx* c, uint32_t key, uint32_t value) {
     else if (key == VPT_LAB_WHOLE_FRAMES) c->lab_whole_frames = value == 0xffffu ? 0xffffffffu : value;   // (0xffff: no bound, the default)
     else if (key == VPT_LAB_WHOLE_PARTS && value <= plan::kMaxParts) c->lab_whole_parts = value;
     else if (key == VPT_LAB_WHOLE_CULL && value <= 1u) c->lab_whole_cull = value != 0u;
+    else if (key == VPT_LAB_NARROW_OFF && value <= 1u) c->lab_narrow_off = value != 0u;
     else return VPT_ERR_INVALID_ARGUMENT;
     c->state_gen++;   // captured batches hold the old grids
     return VPT_OK;

@@ -104,7 +104,7 @@ int batch_begin(vpt_ctx* c, Lane& L, const plan::Schedule& sd, uint32_t frames, 
             const uint32_t static_rounds = (mode == 0u || mode == 3u) ? std::min(rounds, 1u) : mode == 1u ? (rounds >= 2u ? rounds - 1u : 0u) : rounds / 2u;
             // (mode 3: mode 0 with guided chunks — at most the given tiles per atomic, fewer towards the end of the batch)
             if (i) HIPCHK(c, hipMemsetAsync(&L.ctr->extend_head, 0, 4, s));   // the tile cursor starts at 0 in every part
-            TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, part_state(c, L, first), L.ctr, n_part, dispatch_base + first, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u), rect, dl, culled));
+            TIMED(c, s, VPT_K_PRIMARY, launch_whole(s, grid, b.count, dsc, c->P, part_state(c, L, first), L.ctr, n_part, dispatch_base + first, c->scene_plain, static_rounds, std::max(1u, c->lab_whole_sched & 15u) | (mode == 3u ? 0x100u : 0u) | (c->lab_narrow_off ? kWholeNarrowOff : 0u), rect, dl, culled));
             if (i + 1u < sd.parts.n) {   // this part's resolve on the second stream, beside the next part's launch (the last part's: batch_resolve)
                 HIPCHK(c, hipEventRecord(L.ev_shade, s));
                 HIPCHK(c, hipStreamWaitEvent(L.stream2, L.ev_shade, 0));

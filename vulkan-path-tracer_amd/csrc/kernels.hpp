@@ -17,6 +17,7 @@ void launch_bounce(hipStream_t s, uint32_t blocks, bool lds_scene, bool count, b
 int bounce_blocks_per_cu(bool lds_scene, const DeviceScene& sc, bool plain = false);
 void launch_whole(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, Counters* ctr, uint32_t n_slots,
                   uint32_t dispatch_base, bool plain, uint32_t static_rounds, uint32_t chunk_tiles, cull::Packed rect, const deal::Deal& deal, uint64_t culled);   // rect "everything": n_slots slots; else n_slots launch indices over the rectangle, zeros for the other slots of deal.slots (whole_deal.hpp)
+constexpr uint32_t kWholeNarrowOff = 1u << 9;   // in launch_whole's chunk_tiles, laboratory build only (VPT_LAB_NARROW_OFF): the launch flags no child word of its LDS tree, every node step is four-wide
 int whole_blocks_per_cu(const DeviceScene& sc, bool plain);
 // the rest of a streams batch in one launch (kernels_finish.hip k_finish): every path of queue[parity] run to its end
 void launch_finish(hipStream_t s, uint32_t blocks, bool count, const DeviceScene& sc, const RenderParams& P, const PathState& ps, const StreamState& ss, const uint32_t* queue,

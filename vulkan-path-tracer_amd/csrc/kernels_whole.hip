@@ -78,7 +78,16 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
     // Cornell 1080p, same box, alternating: 9250-9269 Msamples/s against 9100-9109 with the arguments held in registers and VGPR lanes
     // (profiles/r14_whole_uniforms_ab.md).
     const VPT_KERNARG WholeArgs* ka = (const VPT_KERNARG WholeArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    stage_scene<true>(sc, lds_nodes, lds_tris);
+    // The PLAIN instantiation's closest-hit search takes the two-slot step at half-empty nodes (node_step.hpp; the Cornell tree's nodes 1 and 2): their
+    // child words are flagged here, in the LDS copy.  The other four keep the four-wide step and compile as they did — the counting and validating ones
+    // make the same visits by construction, and the general one lost 0.4 % on the compact scene, whose tree has one such node in seven
+    // (profiles/r22_narrow_node_ab.md).  In the light query the step was measured slower, and issued MORE instructions (profiles/REJECTED.md).
+    constexpr bool NARROW = PLAIN && !COUNT && !STRICT;
+#if VPT_LAB
+    stage_scene<true, NARROW>(sc, lds_nodes, lds_tris, (a.chunk_tiles & kWholeNarrowOff) == 0u);   // (VPT_LAB_NARROW_OFF: no word is flagged, every step four-wide)
+#else
+    stage_scene<true, NARROW>(sc, lds_nodes, lds_tris);
+#endif
     constexpr uint32_t kWaves = kTraverseBlock / 64u;
     __shared__ uint32_t r_slot[kWaves][128], r_prim[kWaves][128], r_inst[kWaves][128];
     __shared__ float r_t[kWaves][128], r_u[kWaves][128], r_v[kWaves][128];
@@ -136,11 +145,11 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
                 V3 E = o.emitted;
                 if (o.want_sky) {
                     const bool rq = (uP.flags & VPT_FLAG_RAY_QUERIES) != 0u;
-                    if (sky_visible<true, COUNT>(usc, lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq)) E = E + o.csky;
+                    if (sky_visible<true, COUNT, NARROW>(usc, lds_nodes, lds_tris, o.sky_o, o.sky_d, stack, sst, rq)) E = E + o.csky;
                     nrays++;
                 }
                 if (o.want_light) {
-                    if (light_visible<true, COUNT>(usc, lds_nodes, lds_tris, o.light_o, o.light_d, o.light_gid, stack, sst)) E = E + o.clight;
+                    if (light_visible<true, COUNT, NARROW>(usc, lds_nodes, lds_tris, o.light_o, o.light_d, o.light_gid, stack, sst)) E = E + o.clight;
                     nrays++;
                 }
                 // contribution and the survivor's registers: the same statements as a closure called once.  Nothing else differs, and why the compiler
@@ -250,7 +259,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
         {
             HitRec hr;
             bool hit = false;
-            if (has_ray) hit = trace_any<true, COUNT>(usc, lds_nodes, lds_tris, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st);
+            if (has_ray) hit = trace_any<true, COUNT, NARROW>(usc, lds_nodes, lds_tris, porg, normalize(pdir), 0.01f, 100000.0f, stack, hr, st);
             const unsigned long long mh = __ballot(has_ray && hit);
             if (has_ray && hit) {
                 const uint32_t q = (hit_head + hit_count + lanes_below(mh)) & 127u;

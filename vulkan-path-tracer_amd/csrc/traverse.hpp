@@ -15,6 +15,7 @@
 #pragma once
 #include "device_types.hpp"
 #include "slab.hpp"
+#include "node_step.hpp"
 
 namespace vpt {
 
@@ -84,10 +85,7 @@ __device__ inline void unpack_node(const uint4& w0, const uint4& w1, const uint4
 // near* / far*: the planes of the four children this ray meets first / last on each axis.  load_node reads each axis' near and far plane vectors by
 // the sign of the ray's direction and the box test sorts nothing (slab.hpp box_entry_dir).  Cornell 1080p, same box, alternating: 9110-9125
 // Msamples/s against 8932-8935 with the planes read as stored and sorted per axis (profiles/r13_lds_node_step_ab.md).
-struct NodeDataWide {
-    float4 nearx, neary, nearz, farx, fary, farz;
-    int c0, c1, c2, c3;
-};
+// (struct NodeDataWide, and NodeDataNarrow for the two-slot step of a half-empty node: node_step.hpp)
 
 // Scene access either from global memory (quantised nodes) or from an LDS copy (small scenes, fp32 nodes).
 struct GlobalSceneSrc {
@@ -104,8 +102,13 @@ struct GlobalSceneSrc {
         a = p[0]; b = p[1]; c = p[2];
     }
 };
-struct LdsSceneSrc {
+// NARROW: the tree's child words may carry kNarrowBit (node_step.hpp; flagged by stage_scene<true, true>): the closest-hit search takes the two-slot
+// step at nodes so named, and every search's node address drops the flag.  The whole-path kernel's PLAIN instantiation (k_whole<false, false, true>)
+// opts in; every other kernel and instantiation has LdsSceneSrc.
+template <bool NARROW>
+struct LdsSceneSrcT {
     using Node = NodeDataWide;
+    static constexpr bool kNarrow = NARROW;
     const float4* nodes;  // LDS, BvhNodeWide
     const float4* tris;   // LDS
     bool strict;          // DeviceScene::strict_hits
@@ -115,6 +118,7 @@ struct LdsSceneSrc {
         a = p[0]; b = p[1]; c = p[2];
     }
 };
+using LdsSceneSrc = LdsSceneSrcT<false>;
 
 // (fmin_, fmax_, kMissT, safe_inverse and the slab test of an fp32 box: slab.hpp)
 
@@ -135,12 +139,8 @@ template <bool STRICT> __device__ inline RaySlab make_slab(const GlobalSceneSrc&
 // instantiations keep the subtract form and carry no guard: they are not where the time goes, and the library stays under its size bound.
 // selx / sely / selz: where in a node (BvhNodeWide: float4 0..2 = min x y z, 3..5 = max x y z) this ray's NEAR plane vector of the axis is — the max
 // one for a negative reciprocal, as RaySlab::neg* picks the plane byte of a quantised node; the far one is the other of the pair (load_node).
-struct RaySlabWide {
-    V3 o, inv, oi;
-    bool fused;
-    int selx, sely, selz;
-};
-template <bool STRICT> __device__ inline RaySlabWide make_slab(const LdsSceneSrc& src, V3 o, V3 d) {
+// (struct RaySlabWide: node_step.hpp)
+template <bool STRICT, bool NARROW> __device__ inline RaySlabWide make_slab(const LdsSceneSrcT<NARROW>& src, V3 o, V3 d) {
     RaySlabWide r;
     r.o = o; r.inv = safe_inverse(d); r.oi = slab_oi(o, r.inv);
     r.selx = r.inv.x < 0.0f ? 3 : 0; r.sely = r.inv.y < 0.0f ? 4 : 1; r.selz = r.inv.z < 0.0f ? 5 : 2;
@@ -151,12 +151,10 @@ template <bool STRICT> __device__ inline RaySlabWide make_slab(const LdsSceneSrc
 // The node a search stands at.  Quantised nodes as they are; fp32 nodes in LDS with every axis' near and far plane vectors read from the min or
 // the max vector by per-lane address (the node is 128-byte aligned data either way: six 16-byte reads and the child word, as before).
 __device__ inline void load_node(const GlobalSceneSrc& src, const RaySlab&, int i, NodeData& n) { src.node(i, n); }
-__device__ inline void load_node(const LdsSceneSrc& src, const RaySlabWide& r, int i, NodeDataWide& n) {
-    const float4* p = src.nodes + i * 8;
-    n.nearx = p[r.selx]; n.neary = p[r.sely]; n.nearz = p[r.selz]; n.farx = p[3 - r.selx]; n.fary = p[5 - r.sely]; n.farz = p[7 - r.selz];
-    float4 c = p[6];
-    n.c0 = __float_as_int(c.x); n.c1 = __float_as_int(c.y); n.c2 = __float_as_int(c.z); n.c3 = __float_as_int(c.w);
-}
+__device__ inline void load_node(const LdsSceneSrcT<false>& src, const RaySlabWide& r, int i, NodeDataWide& n) { load_node_wide(src.nodes + i * 8, r, n); }
+// ... of a tree whose child words may carry kNarrowBit: the flag falls out of the address (node_step.hpp node_at), so a search that takes no two-slot
+// step — the any-hit searches — runs on flagged words as it is
+__device__ inline void load_node(const LdsSceneSrcT<true>& src, const RaySlabWide& r, int i, NodeDataWide& n) { load_node_wide(node_at(src.nodes, (uint32_t)i), r, n); }
 template <int K> __device__ inline float byte_f(uint32_t w) { return (float)((w >> (8 * K)) & 0xffu); }  // v_cvt_f32_ubyteK
 
 // Entry distances of the ray into the four child boxes ([tmin, tlimit] clipped), kMissT for a miss.
@@ -205,27 +203,13 @@ __device__ inline void node_entries_pk(const NodeData& n, const RaySlab& r, floa
     const vpt_f2 s01 = tf01 * slack, s23 = tf23 * slack;
     t0 = (tn0 <= s01.x) ? tn0 : kMissT; t1 = (tn1 <= s01.y) ? tn1 : kMissT; t2 = (tn2 <= s23.x) ? tn2 : kMissT; t3 = (tn3 <= s23.y) ? tn3 : kMissT;
 }
-// fp32 nodes: the plain slab test (slab.hpp), one fma per plane (24 instead of 48 fp32 operations per node step) when the wave's origins allow it,
-// on planes load_node has sorted by the ray's direction (box_entry_dir: the values of box_entry_fma without its six min / max per box).
-// (Measured and not taken: skipping the tests of slots 2 and 3 where no lane of the wave stands at a node that uses them — the Cornell tree's nodes 1 and 2
-// have two unused slots each — behind a ballot on the loaded plane: it issues fewer VALU instructions and is slower, profiles/REJECTED.md.)
-__device__ inline void node_entries(const NodeDataWide& n, const RaySlabWide& r, float tmin, float tlimit, float& t0, float& t1, float& t2, float& t3) {
-    float4 nx = n.nearx, ny = n.neary, nz = n.nearz, fx = n.farx, fy = n.fary, fz = n.farz;
-    if (!r.fused) {   // box_entry(): the 24 subtractions here, oi == 0 behind them
-        nx.x -= r.o.x; nx.y -= r.o.x; nx.z -= r.o.x; nx.w -= r.o.x; fx.x -= r.o.x; fx.y -= r.o.x; fx.z -= r.o.x; fx.w -= r.o.x;
-        ny.x -= r.o.y; ny.y -= r.o.y; ny.z -= r.o.y; ny.w -= r.o.y; fy.x -= r.o.y; fy.y -= r.o.y; fy.z -= r.o.y; fy.w -= r.o.y;
-        nz.x -= r.o.z; nz.y -= r.o.z; nz.z -= r.o.z; nz.w -= r.o.z; fz.x -= r.o.z; fz.y -= r.o.z; fz.z -= r.o.z; fz.w -= r.o.z;
-    }
-#define VPT_BOX(C) box_entry_dir(nx.C, ny.C, nz.C, fx.C, fy.C, fz.C, r.oi, r.inv, tmin, tlimit)
-    t0 = VPT_BOX(x); t1 = VPT_BOX(y); t2 = VPT_BOX(z); t3 = VPT_BOX(w);
-#undef VPT_BOX
-}
-__device__ inline void cswap(float& ta, int& ca, float& tb, int& cb) {
-    bool sw = tb < ta;
-    float tt = sw ? tb : ta; int ct = sw ? cb : ca;
-    tb = sw ? ta : tb; cb = sw ? ca : cb;
-    ta = tt; ca = ct;
-}
+// fp32 nodes: node_entries(NodeDataWide ...) and cswap live in node_step.hpp, with the two-slot step of a half-empty node beside them.
+// (Measured and not taken: skipping the tests of slots 2 and 3 where no lane of the wave stands at a node that uses them behind a ballot on the LOADED
+// plane: it issues fewer VALU instructions and is slower, profiles/REJECTED.md.  The two-slot step decides from the child word instead.)
+
+// Does a closest-hit search on Src take the two-slot step?  Only the non-validating pass of a source that opted in.
+template <bool STRICT, class Src> struct TakesNarrow { static constexpr bool value = false; };
+template <bool STRICT> struct TakesNarrow<STRICT, LdsSceneSrcT<true>> { static constexpr bool value = !STRICT; };
 
 // One closest-hit search (tmin < t < tmax; ties -> smaller global triangle id) that ignores triangles ex0 / ex1.
 template <bool COUNT, bool STRICT, class Src, class Stack>
@@ -238,19 +222,48 @@ __device__ inline bool trace_closest_pass(const Src& src, V3 o, V3 d, float tmin
     int cur = 0;  // root is inner node 0
     while (true) {
         if (cur >= 0) {
-            typename Src::Node n;
-            load_node(src, slab, cur, n);
-            if (COUNT) st.nodes++;
-            float t0, t1, t2, t3;
-            node_entries(n, slab, tmin, best.t, t0, t1, t2, t3);
-            int c0 = n.c0, c1 = n.c1, c2 = n.c2, c3 = n.c3;
-            cswap(t0, c0, t1, c1); cswap(t2, c2, t3, c3); cswap(t0, c0, t2, c2); cswap(t1, c1, t3, c3); cswap(t1, c1, t2, c2);
-            if (t0 < kMissT) {  // nearest child next, the others pushed far -> near
-                if (t3 < kMissT) stack.push((uint32_t)c3);
-                if (t2 < kMissT) stack.push((uint32_t)c2);
-                if (t1 < kMissT) stack.push((uint32_t)c1);
-                cur = c0;
-                continue;
+            if constexpr (!TakesNarrow<STRICT, Src>::value) {   // every search but the whole-path kernel's PLAIN one: the four-wide step
+                typename Src::Node n;
+                load_node(src, slab, cur, n);
+                if (COUNT) st.nodes++;
+                float t0, t1, t2, t3;
+                node_entries(n, slab, tmin, best.t, t0, t1, t2, t3);
+                int c0 = n.c0, c1 = n.c1, c2 = n.c2, c3 = n.c3;
+                cswap(t0, c0, t1, c1); cswap(t2, c2, t3, c3); cswap(t0, c0, t2, c2); cswap(t1, c1, t3, c3); cswap(t1, c1, t2, c2);
+                if (t0 < kMissT) {  // nearest child next, the others pushed far -> near
+                    if (t3 < kMissT) stack.push((uint32_t)c3);
+                    if (t2 < kMissT) stack.push((uint32_t)c2);
+                    if (t1 < kMissT) stack.push((uint32_t)c1);
+                    cur = c0;
+                    continue;
+                }
+            } else {
+                if (COUNT) st.nodes++;
+                // Every lane that stands at a node stands at a flagged one (lanes at leaves are not in this branch): the two-slot step.  The choice is a
+                // scalar branch between two bodies that meet again before the loop's one `continue`: the shape of the loop is the four-wide one's.
+                const bool narrow = __ballot(cur < kNarrowBit) == 0ull;   // (cur >= 0 here, so "flagged" is one compare)
+                const auto push = [&](int w) { stack.push((uint32_t)w); };
+                int next;
+                if (narrow) {
+                    const float4* p = node_at(src.nodes, (uint32_t)cur);
+                    float t0, t1;
+                    {
+                        NodeDataNarrow n;
+                        load_node_narrow(p, slab, n);
+                        node_entries(n, slab, tmin, best.t, t0, t1);
+                    }
+                    int c0, c1;
+                    narrow_children(p, c0, c1);
+                    next = closest_order(t0, c0, t1, c1, push);
+                } else {
+                    // a flagged node among others: its slots 2 and 3 are unused boxes, the four-wide step is right for it
+                    typename Src::Node n;
+                    load_node(src, slab, cur, n);
+                    float t0, t1, t2, t3;
+                    node_entries(n, slab, tmin, best.t, t0, t1, t2, t3);
+                    next = closest_order(t0, n.c0, t1, n.c1, t2, n.c2, t3, n.c3, push);
+                }
+                if (next != kNoChild) { cur = next; continue; }
             }
         } else {
             uint32_t enc = (uint32_t)(~cur);
@@ -397,37 +410,48 @@ __device__ inline bool closest_is(const Src& src, V3 o, V3 d, float tmin, float 
 
 // ------------------------------------------------------------------ the searches on a DeviceScene: tree in LDS (LDS_SCENE, staged by stage_scene) or in memory
 // (the fused, finishing and whole-path kernels' validating instantiations, k_trace_rays and the laboratory's stage kernels)
-template <bool LDS_SCENE>
-__device__ inline void stage_scene(const DeviceScene& sc, float4* lds_nodes, float4* lds_tris) {
+// NARROW: behind the copy, every child word of the LDS copy that names a half-empty node gets kNarrowBit (node_step.hpp narrow_child: the rule reads
+// planes, the pass writes child words, so no thread reads what another writes); `flag` = false leaves the copy as it is and every step four-wide.
+template <bool LDS_SCENE, bool NARROW = false>
+__device__ inline void stage_scene(const DeviceScene& sc, float4* lds_nodes, float4* lds_tris, bool flag = true) {
     if (LDS_SCENE) {
         const float4* gn = reinterpret_cast<const float4*>(sc.nodes_wide);
         const float4* gt = reinterpret_cast<const float4*>(sc.tris);
         for (uint32_t i = threadIdx.x; i < sc.node_count * 8; i += blockDim.x) lds_nodes[i] = gn[i];
         for (uint32_t i = threadIdx.x; i < sc.tri_count * 3; i += blockDim.x) lds_tris[i] = gt[i];
         __syncthreads();
+        if (NARROW) {
+            if (flag)
+                for (uint32_t i = threadIdx.x; i < sc.node_count * 4; i += blockDim.x) {
+                    int32_t* w = reinterpret_cast<int32_t*>(lds_nodes + (i >> 2) * 8 + 6) + (i & 3u);
+                    const int32_t word = *w;
+                    if (word < (int32_t)sc.node_count && narrow_child(reinterpret_cast<const BvhNodeWide*>(lds_nodes), word)) *w = word | kNarrowBit;
+                }
+            __syncthreads();
+        }
     }
 }
-template <bool LDS_SCENE, bool COUNT, class Sc, class Stack>
+template <bool LDS_SCENE, bool COUNT, bool NARROW = false, class Sc, class Stack>
 __device__ inline bool trace_any(const Sc& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, float tmin,
                                  float tmax, const Stack& stack, HitRec& h, TravStats& st) {
-    if constexpr (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
+    if constexpr (LDS_SCENE) { LdsSceneSrcT<NARROW> src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
     else { GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u}; return trace_closest<COUNT>(src, o, d, tmin, tmax, stack, h, st); }
 }
 
 // Sky visibility / light identity as exact any-hit queries (above).
 // rq: USE_RAY_QUERIES (RTCommon.slang:52-63: the direction as it is, TMin 1e-4, TMax 1e6); otherwise RTCommon.slang:64-84: normalised, TMin 1e-5, TMax 1000.
-template <bool LDS_SCENE, bool COUNT, class Sc, class Stack>
+template <bool LDS_SCENE, bool COUNT, bool NARROW = false, class Sc, class Stack>
 __device__ inline bool sky_visible(const Sc& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, const Stack& stack, TravStats& st, bool rq) {
     const float tmin = rq ? 0.0001f : 0.00001f, tmax = rq ? 1000000.0f : 1000.0f;
     if (!rq) d = normalize(d);
-    if constexpr (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
+    if constexpr (LDS_SCENE) { LdsSceneSrcT<NARROW> src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
     else { GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u}; return !trace_occluded<COUNT, false>(src, o, d, tmin, tmax, 0.0f, 0u, stack, st); }
 }
-template <bool LDS_SCENE, bool COUNT, class Sc, class Stack>
+template <bool LDS_SCENE, bool COUNT, bool NARROW = false, class Sc, class Stack>
 __device__ inline bool light_visible(const Sc& sc, const float4* lds_nodes, const float4* lds_tris, V3 o, V3 d, uint32_t gid, const Stack& stack, TravStats& st) {
     uint32_t slot = sc.tri_slot_of_gid[gid];
     if (slot == 0xffffffffu) return false;  // the sampled light triangle is a sliver: nothing can hit it
-    if constexpr (LDS_SCENE) { LdsSceneSrc src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
+    if constexpr (LDS_SCENE) { LdsSceneSrcT<NARROW> src{lds_nodes, lds_tris, sc.strict_hits != 0u, kSlabFmaReach * sc.scene_extent}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
     else { GlobalSceneSrc src{sc.nodes, sc.tris, sc.strict_hits != 0u}; return closest_is<COUNT>(src, o, d, 0.0001f, 1000000.0f, gid, slot, stack, st); }
 }
 

@@ -24,7 +24,7 @@ struct WholeArgs {
     PathState ps;
     Counters* ctr;
     uint32_t n_slots, dispatch_base;
-    uint32_t static_rounds, chunk_tiles;
+    uint32_t static_rounds, chunk_tiles;   // chunk_tiles: whole_refill.hpp Shape (bits 0-8) | kernels.hpp kWholeNarrowOff
 };
 
 // What a launch hands over: the arguments, and behind them the rectangle of the image outside which no camera ray can reach the scene, as
