@@ -779,6 +779,63 @@ int vpt_set_temporal_options(vpt_ctx* ctx, const vpt_temporal_options* options);
 int vpt_get_temporal_options(const vpt_ctx* ctx, vpt_temporal_options* out);
 int vpt_get_temporal_motion(vpt_ctx* ctx, float* motion_host);   /* width*height*2 floats */
 
+/* ---- auto-exposure: luminance histogram metering ahead of the tonemap ------------------------------------------------------------------
+ * vpt_post_params.exposure is a constant the host chooses without seeing the image; swapping the environment, moving an emitter or flying from
+ * the lamp into the shadow changes the mean radiance by orders of magnitude.  With the option on, every vpt_postprocess / vpt_postprocess_device
+ * meters its source image on the device and the tonemap follows — nothing is read back, nothing is waited for, any number of frames can be in
+ * flight.  The reference has no counterpart.  The loop of a viewport ends as before, the exposure following the image:
+ *     ... -> vpt_temporal_accumulate -> vpt_denoise -> vpt_postprocess
+ * vpt_set_exposure_options: context state, like vpt_set_post_source and vpt_set_svgf_options; the call only validates and stores.  With mode == 0
+ *                     (default) every call returns the bits it returned without these options, and nothing is allocated or launched.  With mode == 1
+ *                     a post-process call first runs two more launches on the context's stream; the arithmetic is csrc/exposure.hpp's, the sums
+ *                     are of integers, and the device result equals a host compile of that header bit for bit.
+ *   histogram         256 bins over the post source (the accumulation image, or the denoised one under VPT_POST_SOURCE_DENOISED) BEFORE bloom, of
+ *                     l = (0.2126 r + 0.7152 g) + 0.0722 b; alpha is ignored.  Bin 0, the black bin: l zero, negative or NaN — it never takes part
+ *                     in the average, so a black environment or miss pixels do not drag the exposure.  Bin 255: l infinite, or at or above
+ *                     2^max_log2.  Bin 1 also holds everything below 2^min_log2.  Otherwise 1 + floor((log2 l - min_log2) 254 / (max_log2 - min_log2)).
+ *   metering          N = the pixels in bins 1..255.  In order of luminance, the pixels [lo, hi) are averaged: lo = (N rint(low_percentile 65536)) >> 16,
+ *                     hi = min(max((N rint(high_percentile 65536)) >> 16, lo + 1), N).  avg_log2 = min_log2 + (their mean bin - 0.5) (max_log2 -
+ *                     min_log2) / 254, and target_log2 = clamp(log2 key - avg_log2 + compensation_log2, min_exposure_log2, max_exposure_log2).
+ *   adaptation        the first metering after mode went to 1 or after vpt_exposure_reset sets cur_log2 = target_log2.  Every other one blends:
+ *                     cur += (target - cur) a with a = rate_up where the target is brighter (larger) and rate_down where it is darker; where a is 1,
+ *                     cur is the target itself, not the rounding of the expression.  A metering with N == 0 (an all-black image) has no target and
+ *                     leaves cur_log2, target_log2 and avg_log2 as they are; if nothing has been metered with a target yet, cur_log2 is 0, valid stays
+ *                     0 and the next metering with a target jumps.  scale = 2^cur_log2.
+ *   the tonemap       multiplies by exposure * scale — vpt_post_params.exposure times the adapted scale, the product formed once in fp32 — where it
+ *                     multiplied by exposure; both schedules, both bloom taps.  Bloom threshold and strength act on the unexposed image, as before.
+ *   two calls         on the same image meter twice and adapt twice, as two vpt_temporal_accumulate calls count their frames twice.
+ *   the state         is a scalar about the scene's brightness: it survives vpt_resize, vpt_set_camera, vpt_reset, scene edits and everything else
+ *                     except a change of `mode` (which starts it afresh, meterings included) and vpt_exposure_reset.  Changing only rates, key,
+ *                     percentiles, range or clamps keeps it, so a host can set time-based rates every frame.
+ *   vpt_get_exposure_state  waits for the work in flight like the other read-backs.  With mode == 0, or before the first metering, it is VPT_OK
+ *                     with scale = 1 and everything else 0.  vpt_get_exposure_histogram: the 256 counts of the latest metering (a test hook and a
+ *                     debug view); VPT_ERR_INVALID_ARGUMENT before the first metering.
+ *   vpt_stats         the two launches are counted and (profile) timed under VPT_K_TONEMAP.
+ *   memory            2.1 KB on the device, allocated by the first metering and kept until vpt_destroy.
+ *   errors            VPT_ERR_INVALID_ARGUMENT for a NULL argument, a field that is not finite, a violated constraint below, a non-zero reserved
+ *                     word.  A refused call changes nothing and leaves the context usable. */
+typedef struct vpt_exposure_options {
+    uint32_t mode;              /* 0 (default): off — every call returns the bits it returned without these options, nothing allocated or launched. 1: on */
+    float min_log2, max_log2;   /* luminance range of the histogram, log2; defaults -10, 6; min < max, both finite */
+    float low_percentile, high_percentile; /* trimmed mean; defaults 0.5, 0.95; 0 <= low < high <= 1 */
+    float key;                  /* luminance the average is mapped to; default 0.18; > 0 */
+    float compensation_log2;    /* default 0 */
+    float min_exposure_log2, max_exposure_log2; /* clamp of the result; defaults -8, 8; min <= max */
+    float rate_up, rate_down;   /* blend per metering towards a brighter / darker exposure, in (0, 1]; defaults 0.1, 0.25; 1 = at once */
+    uint32_t reserved;          /* 0 */
+} vpt_exposure_options;
+typedef struct vpt_exposure_state {
+    float scale, cur_log2, target_log2, avg_log2;
+    uint32_t valid, meterings;  /* valid: a metering with a target has set cur_log2; meterings: post-process calls metered since mode went to 1 */
+    uint64_t counted;           /* N of the latest metering */
+} vpt_exposure_state;
+void vpt_default_exposure_options(vpt_exposure_options* out);
+int vpt_set_exposure_options(vpt_ctx* ctx, const vpt_exposure_options* options);
+int vpt_get_exposure_options(const vpt_ctx* ctx, vpt_exposure_options* out);
+int vpt_get_exposure_state(vpt_ctx* ctx, vpt_exposure_state* out);
+int vpt_get_exposure_histogram(vpt_ctx* ctx, uint32_t out[256]);
+int vpt_exposure_reset(vpt_ctx* ctx);   /* the next metering jumps to its target */
+
 /* ---- energy-compensation lookup tables -------------------------------------------
  * Replaces LookupTableCalculator::CalculateTable(tableSize, sampleCount) (LookupTableCalculator.cpp:44-157)
  * with its shaders LookupReflect.slang / LookupRefract.slang (+ ABOVE_SURFACE / BELOW_SURFACE): sampleCount/20

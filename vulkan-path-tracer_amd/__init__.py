@@ -17,6 +17,7 @@ from ._abi import default_denoise_params, DENOISE_DEMODULATE, DENOISE_MAX_ITERAT
 from ._abi import default_temporal_params, TEMPORAL_DEMODULATE, TEMPORAL_MATCH_INSTANCE, DENOISE_SOURCE_RADIANCE, DENOISE_SOURCE_TEMPORAL  # noqa: F401
 from ._abi import SvgfOptions, default_svgf_options  # noqa: F401
 from ._abi import TemporalOptions, default_temporal_options  # noqa: F401
+from ._abi import ExposureOptions, ExposureState, default_exposure_options, EXPOSURE_BINS  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -459,6 +460,40 @@ class PathTracer:
         out = np.empty((self.height, self.width, 2), np.float32)
         _check(self.lib, self.ctx, self.lib.vpt_get_temporal_motion(self.ctx, out.ctypes.data), "vpt_get_temporal_motion")
         return out
+
+    # ---- auto-exposure (include/vpt.h vpt_set_exposure_options / vpt_get_exposure_options / vpt_get_exposure_state / vpt_get_exposure_histogram / vpt_exposure_reset)
+    def set_exposure_options(self, **kw):
+        """vpt_set_exposure_options: the context's options with the fields given replaced (mode, min_log2, max_log2, low_percentile, high_percentile, key,
+        compensation_log2, min_exposure_log2, max_exposure_log2, rate_up, rate_down).  With mode = 1 every postprocess / postprocess_device meters its source
+        image on the device and the tonemap multiplies by exposure * the adapted scale.  Changing `mode` starts the adapted state afresh; nothing else does."""
+        o = self.exposure_options()
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        _check(self.lib, self.ctx, self.lib.vpt_set_exposure_options(self.ctx, C.byref(o)), "vpt_set_exposure_options")
+
+    def exposure_options(self):
+        """vpt_get_exposure_options -> ExposureOptions."""
+        o = _abi.ExposureOptions()
+        _check(self.lib, self.ctx, self.lib.vpt_get_exposure_options(self.ctx, C.byref(o)), "vpt_get_exposure_options")
+        return o
+
+    def exposure_state(self):
+        """vpt_get_exposure_state -> ExposureState (waits for the work in flight).  scale 1 and valid 0 with the option off or before the first metering."""
+        s = _abi.ExposureState()
+        _check(self.lib, self.ctx, self.lib.vpt_get_exposure_state(self.ctx, C.byref(s)), "vpt_get_exposure_state")
+        return s
+
+    def exposure_histogram(self):
+        """vpt_get_exposure_histogram: the 256 bin counts of the latest metering -> uint32 [256]."""
+        out = np.empty(_abi.EXPOSURE_BINS, np.uint32)
+        _check(self.lib, self.ctx, self.lib.vpt_get_exposure_histogram(self.ctx, out.ctypes.data), "vpt_get_exposure_histogram")
+        return out
+
+    def exposure_reset(self):
+        """vpt_exposure_reset: the next metering jumps to its target instead of blending towards it."""
+        _check(self.lib, self.ctx, self.lib.vpt_exposure_reset(self.ctx), "vpt_exposure_reset")
 
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("primitive", "<u4"), ("instance", "<u4")])

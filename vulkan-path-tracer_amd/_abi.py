@@ -280,6 +280,30 @@ def default_temporal_options(**kw):
     return p
 
 
+class ExposureOptions(C.Structure):  # vpt_exposure_options
+    _fields_ = [("mode", C.c_uint32), ("min_log2", C.c_float), ("max_log2", C.c_float), ("low_percentile", C.c_float), ("high_percentile", C.c_float),
+                ("key", C.c_float), ("compensation_log2", C.c_float), ("min_exposure_log2", C.c_float), ("max_exposure_log2", C.c_float),
+                ("rate_up", C.c_float), ("rate_down", C.c_float), ("reserved", C.c_uint32)]
+
+
+class ExposureState(C.Structure):  # vpt_exposure_state
+    _fields_ = [("scale", C.c_float), ("cur_log2", C.c_float), ("target_log2", C.c_float), ("avg_log2", C.c_float),
+                ("valid", C.c_uint32), ("meterings", C.c_uint32), ("counted", C.c_uint64)]
+
+
+EXPOSURE_BINS = 256
+
+
+def default_exposure_options(**kw):
+    """vpt_default_exposure_options: mode off, range 2^-10 .. 2^6, percentiles 0.5 .. 0.95, key 0.18, no compensation, clamp 2^-8 .. 2^8, rates 0.1 up / 0.25 down."""
+    p = ExposureOptions(0, -10.0, 6.0, 0.5, 0.95, 0.18, 0.0, -8.0, 8.0, 0.1, 0.25, 0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 # every symbol include/vpt.h declares, with (restype, argtypes)
 PROTOTYPES = {
     "vpt_create": (C.c_void_p, [C.POINTER(Config), C.POINTER(C.c_int)]),
@@ -352,6 +376,12 @@ PROTOTYPES = {
     "vpt_set_temporal_options": (C.c_int, [C.c_void_p, C.POINTER(TemporalOptions)]),
     "vpt_get_temporal_options": (C.c_int, [C.c_void_p, C.POINTER(TemporalOptions)]),
     "vpt_get_temporal_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vpt_default_exposure_options": (None, [C.POINTER(ExposureOptions)]),
+    "vpt_set_exposure_options": (C.c_int, [C.c_void_p, C.POINTER(ExposureOptions)]),
+    "vpt_get_exposure_options": (C.c_int, [C.c_void_p, C.POINTER(ExposureOptions)]),
+    "vpt_get_exposure_state": (C.c_int, [C.c_void_p, C.POINTER(ExposureState)]),
+    "vpt_get_exposure_histogram": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vpt_exposure_reset": (C.c_int, [C.c_void_p]),
     "vpt_lab_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "vpt_lab_set_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "vpt_lab_whole_culled": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -494,6 +494,7 @@ void vpt_destroy(vpt_ctx* c) {
     free_scene(c);
     free_render_buffers(c);
     if (c->d_launch_off) (void)hipFree(c->d_launch_off);
+    if (c->ex_dev) (void)hipFree(c->ex_dev);
     if (c->d_volumes) (void)hipFree(c->d_volumes);
     for (DensityGrid& g : c->grids) { (void)hipFree((void*)g.values); (void)hipFree((void*)g.block_max); (void)hipFree((void*)g.bricks); }
     if (c->d_grids) (void)hipFree(c->d_grids);

@@ -252,6 +252,12 @@ struct vpt_ctx {
     size_t tp_motion_cap = 0;        // records each table holds
     uint32_t tp_motion_latest = 0;
     bool tp_motion_valid = false;    // the latest temporal result was made with the option on: tp_motion goes with it
+    // auto-exposure (vpt_set_exposure_options): nothing of this is allocated or launched while mode is 0.  The adapted state is a scalar about the scene's
+    // brightness: it lives on the device, outside the render buffers, and survives vpt_resize and every reset
+    exposure::Options ex_options = exposure::default_options();
+    ExposureDevice* ex_dev = nullptr;        // state | latest histogram | accumulating histogram: allocated (zeroed) by the first metering, freed by vpt_destroy
+    uint32_t ex_reset = exposure::kResetAll; // what the next metering is told (k_exposure_adapt's `reset`): mode has changed / vpt_exposure_reset / nothing
+    bool ex_metered = false;                 // a metering has been enqueued since mode went to 1: state and histogram can be read back
 
     // profiling events
     std::vector<hipEvent_t> ev_pool;

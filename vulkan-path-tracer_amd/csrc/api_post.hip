@@ -43,13 +43,27 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
     const bool linear_tap = (c->params.flags & VPT_FLAG_TONEMAP_LINEAR_BLOOM_TAP) != 0;
     auto MW = [&](uint32_t i) { return c->mip_sizes[i].first; };
     auto MH = [&](uint32_t i) { return c->mip_sizes[i].second; };
+    // Auto-exposure: the source image is metered before bloom and the tonemap kernels read the adapted scale from the device — nothing is read back or
+    // waited for.  The two launches are timed with the tonemap.
+    const float* scale = nullptr;
+    if (c->ex_options.mode) {
+        if (!c->ex_dev) {
+            HIPCHK(c, hipMalloc((void**)&c->ex_dev, sizeof(ExposureDevice)));
+            HIPCHK(c, hipMemsetAsync(c->ex_dev, 0, sizeof(ExposureDevice), s));
+        }
+        const exposure::Plan plan = exposure::plan_of(c->ex_options);
+        TIMED(c, s, VPT_K_TONEMAP, launch_luminance_histogram(s, hdr, W * H, plan, c->ex_dev));
+        TIMED(c, s, VPT_K_TONEMAP, launch_exposure_adapt(s, plan, c->ex_reset, c->ex_dev));
+        c->ex_reset = exposure::kResetNone; c->ex_metered = true;
+        scale = &c->ex_dev->state.scale;
+    }
     if (pp->schedule == VPT_POST_REFERENCE_PASSES) {   // PostProcessor.cpp:193-246 pass by pass: threshold, down x (n-1), up x (n-1), tonemap
         TIMED(c, s, VPT_K_BLOOM, launch_bloom_threshold(s, hdr, c->mips[0], W, H, pp->bloom_threshold, pp->falloff_range));
         for (uint32_t i = 1; i < mip_count; i++)
             TIMED(c, s, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
         for (uint32_t i = mip_count - 1; i > 0; i--)
             TIMED(c, s, VPT_K_BLOOM, launch_bloom_up(s, c->mips[i], MW(i), MH(i), c->mips[i - 1], MW(i - 1), MH(i - 1), pp->bloom_strength));
-        TIMED(c, s, VPT_K_TONEMAP, launch_tonemap(s, hdr, c->mips[0], c->post_out, W, H, pp->exposure, pp->gamma, linear_tap));
+        TIMED(c, s, VPT_K_TONEMAP, launch_tonemap(s, hdr, c->mips[0], c->post_out, W, H, pp->exposure, pp->gamma, linear_tap, scale));
     } else {
         // Fused schedule, same values (kernels_post.hip): mip 0 is never materialised unless the caller asks for it.
         //   T = first mip the one-launch tail keeps in LDS (<= kBloomTailMaxTexels texels, and >= 2: its base mip must exist in memory)
@@ -97,7 +111,7 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
         }
         TIMED(c, s, VPT_K_TONEMAP, launch_post_final(s, hdr, mip_count >= 2 ? c->mips[1] : nullptr, mip_count >= 2 ? MW(1) : 0u, mip_count >= 2 ? MH(1) : 0u,
                                                   bloom0 ? c->mips[0] : nullptr, c->post_out, W, H, pp->bloom_threshold, pp->falloff_range, pp->bloom_strength,
-                                                  pp->exposure, pp->gamma, linear_tap));
+                                                  pp->exposure, pp->gamma, linear_tap, scale));
     }
     return VPT_OK;
 }
@@ -451,6 +465,49 @@ int vpt_postprocess_device(vpt_ctx* c, const vpt_post_params* pp, void* rgba8_de
     if ((rc = post_source_ready(c))) return rc;
     return run_behind_frames(c, [&] { return enqueue_post(c, pp, false); }, rgba8_device, &vpt_ctx::post_out, (size_t)c->P.width * c->P.height * 4, ticket);
 }
+// ---- auto-exposure: the options (context state: stored and validated here, acted on by enqueue_post) and the read-backs of the latest metering
+static_assert(sizeof(vpt_exposure_options) == sizeof(exposure::Options) && sizeof(vpt_exposure_state) == sizeof(exposure::State), "exposure.hpp mirrors include/vpt.h");
+void vpt_default_exposure_options(vpt_exposure_options* o) {
+    const exposure::Options d = exposure::default_options();
+    if (o) memcpy(o, &d, sizeof d);
+}
+int vpt_set_exposure_options(vpt_ctx* c, const vpt_exposure_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    exposure::Options n;
+    memcpy(&n, o, sizeof n);
+    if (const char* why = exposure::check_options(n)) return fail(c, VPT_ERR_INVALID_ARGUMENT, why);
+    if (n.mode != c->ex_options.mode) { c->ex_reset = exposure::kResetAll; c->ex_metered = false; }   // the adapted state belongs to one stretch of mode == 1
+    c->ex_options = n;
+    return VPT_OK;
+}
+int vpt_get_exposure_options(const vpt_ctx* c, vpt_exposure_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    memcpy(o, &c->ex_options, sizeof *o);
+    return VPT_OK;
+}
+int vpt_exposure_reset(vpt_ctx* c) {
+    if (!c) return VPT_ERR_INVALID_ARGUMENT;
+    if (c->ex_reset == exposure::kResetNone) c->ex_reset = exposure::kResetJump;
+    return VPT_OK;
+}
+int vpt_get_exposure_state(vpt_ctx* c, vpt_exposure_state* out) {
+    if (!c || !out) return VPT_ERR_INVALID_ARGUMENT;
+    *out = vpt_exposure_state{1.0f, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u};
+    if (!c->ex_options.mode || !c->ex_metered) return VPT_OK;
+    int rc = settle_for_readback(c);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(out, &c->ex_dev->state, sizeof *out, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+int vpt_get_exposure_histogram(vpt_ctx* c, uint32_t* out) {
+    if (!c || !out) return VPT_ERR_INVALID_ARGUMENT;
+    if (!c->ex_options.mode || !c->ex_metered) return fail(c, VPT_ERR_INVALID_ARGUMENT, "no metering yet: post-process with vpt_exposure_options.mode == 1 first");
+    int rc = settle_for_readback(c);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(out, c->ex_dev->hist, sizeof c->ex_dev->hist, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
 const void* vpt_output_device(vpt_ctx* c) { return c ? c->post_out : nullptr; }
 int vpt_get_output(vpt_ctx* c, uint8_t* out8) {
     if (!c || !out8) return VPT_ERR_INVALID_ARGUMENT;

@@ -3,6 +3,7 @@
 #include "device_types.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
+#include "exposure.hpp"
 #include "whole_deal.hpp"   // + camera_cull.hpp
 #include "../../include/vpt_lab.h"   // VPT_TRACE_* / VPT_LAB_* constants (the functions exist in the laboratory build only)
 #ifndef VPT_LAB
@@ -142,10 +143,23 @@ void launch_bloom_down_first(hipStream_t s, const float* hdr, uint32_t iw, uint3
 bool bloom_tail_is_staged(uint32_t bw, uint32_t bh);
 void launch_bloom_tail(hipStream_t s, float* base, float* top_out, uint32_t bw, uint32_t bh, const uint32_t* w, const uint32_t* h, uint32_t levels, float strength);
 void launch_post_final(hipStream_t s, const float* hdr, const float* mip1, uint32_t mw, uint32_t mh, float* bloom0_out, uint8_t* out, uint32_t w, uint32_t h,
-                       float threshold, float falloff, float strength, float exposure, float gamma, bool linear_tap);
+                       float threshold, float falloff, float strength, float exposure, float gamma, bool linear_tap, const float* scale = nullptr);
 constexpr uint32_t kBloomTailMaxTexels = 2048, kBloomTailMaxLevels = 8;   // largest mip the one-launch tail keeps in LDS; levels it can hold
 void launch_tonemap(hipStream_t s, const float* hdr, const float* bloom0, uint8_t* out, uint32_t w, uint32_t h, float exposure,
-                    float gamma, bool linear_tap);
+                    float gamma, bool linear_tap, const float* scale = nullptr);
+// Auto-exposure (exposure.hpp holds the arithmetic).  scale (launch_tonemap, launch_post_final; device memory): nullptr — the multiply is c * exposure, the
+// bits of a build without the option; otherwise c * (exposure * *scale), the product formed once.  What the two kernels below keep on the device:
+struct ExposureDevice {
+    exposure::State state;
+    uint32_t hist[exposure::kBins];   // the latest metering's histogram (vpt_get_exposure_histogram)
+    uint32_t acc[exposure::kBins];    // what k_luminance_histogram adds into: all zeros between two meterings (k_exposure_adapt leaves it so)
+};
+// acc[bin_of(pixel)] += 1 for the n RGBA32F pixels of img: a grid-stride pass of at most kHistMaxBlocks blocks of kHistThreads threads, two pixels per
+// thread and trip — an image of more than 2 * kHistMaxBlocks * kHistThreads pixels takes a second trip
+constexpr uint32_t kHistThreads = 1024, kHistMaxBlocks = 256;
+void launch_luminance_histogram(hipStream_t s, const float* img, uint32_t n, const exposure::Plan& p, ExposureDevice* d);
+// one wave: meter and adapt on acc, the state and a copy of acc written, acc zeroed (reset: exposure::kReset*)
+void launch_exposure_adapt(hipStream_t s, const exposure::Plan& p, uint32_t reset, ExposureDevice* d);
 // vpt_denoise (denoise.hpp holds the arithmetic).  prepare: e = the (demodulated) colour of c; `guide` holds the first-hit normal image on entry and the
 // packed (n.xyz, t) on exit.  atrous: one pass in -> out at ps.step (steps 1 and 2 through an LDS tile, larger ones from memory); remodulate: the last pass
 // of a demodulated run, which reads `albedo`.  All images RGBA32F of w x h but depth (one float per pixel).

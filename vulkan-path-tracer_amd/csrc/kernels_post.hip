@@ -4,6 +4,7 @@
 // summation order is the reference's (x offset outer, y offset inner) so results are bit-identical to
 // the scalar restatement.
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace vpt {
 using namespace vptfp;
@@ -109,8 +110,10 @@ __device__ inline V3 aces_fitted(V3 c) {  // Tonemap.slang:20-55
 }
 
 // Tonemap.slang:159-176: hdr + bloom tap at uv = xy/size (no half-texel offset), exposure, gamma, ACES, RGBA8.
+// scale (here and in k_post_final): nullptr, or the adapted exposure on the device (auto-exposure: k_exposure_adapt's state.scale) — then the factor is
+// exposure * *scale, formed once.
 __global__ __launch_bounds__(256) void k_tonemap(const float4* hdr, const float4* bloom, uchar4* out, int w, int h, float exposure,
-                                                 float gamma, int linear_tap) {
+                                                 float gamma, int linear_tap, const float* scale) {
     int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
     float4 p = hdr[(size_t)y * w + x];
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(256) void k_tonemap(const float4* hdr, const float4
         bl = v3(q.x, q.y, q.z);
     }
     c = c + bl;
-    c = c * exposure;
+    c = c * (scale ? exposure * *scale : exposure);
     float ig = 1.0f / gamma;
     c = v3(pow_(c.x, ig), pow_(c.y, ig), pow_(c.z, ig));
     c = aces_fitted(c);
@@ -449,13 +452,14 @@ __global__ __launch_bounds__(256) void k_bloom_up_chain(UpChain c) {
 // from an LDS copy of the HDR tile and of the 36 x 6 mip-1 texels those taps can touch.
 template <bool UP, bool LINEAR>
 __global__ __launch_bounds__(256) void k_post_final(const float4* hdr, const float4* mip1, int mw, int mh, float4* bloom0_out, uchar4* out, int w, int h,
-                                                    float threshold, float falloff, float strength, float exposure, float gamma) {
+                                                    float threshold, float falloff, float strength, float exposure, float gamma, const float* scale) {
     constexpr int BW = kTileW + 1, BH = kTileH + 1;           // 65 x 5 texels of mip 0
     constexpr int MW = kTileW / 2 + 4, MH = kTileH / 2 + 4;   // 36 x 6 texels of mip 1
     __shared__ float4 s_hdr[BH][BW];
     __shared__ float4 s_bloom[BH][BW];
     __shared__ float4 s_m1[UP ? MH : 1][UP ? MW : 1];
     const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
+    const float factor = scale ? exposure * *scale : exposure;   // (read beside the tile: the tonemap at the end does not wait for it)
     for (int i = threadIdx.x; i < BW * BH; i += 256) {
         const int ty = i / BW, tx = i - ty * BW;
         s_hdr[ty][tx] = hdr[(size_t)iclamp(y0 - 1 + ty, 0, h - 1) * w + iclamp(x0 - 1 + tx, 0, w - 1)];
@@ -525,7 +529,7 @@ __global__ __launch_bounds__(256) void k_post_final(const float4* hdr, const flo
         bl = B(tx, ty);
     }
     c = c + bl;
-    c = c * exposure;
+    c = c * factor;
     const float ig = 1.0f / gamma;
     c = v3(pow_(c.x, ig), pow_(c.y, ig), pow_(c.z, ig));
     c = aces_fitted(c);
@@ -702,13 +706,13 @@ void launch_bloom_tail(hipStream_t s, float* base, float* top_out, uint32_t bw, 
     hipLaunchKernelGGL(k, dim3(1), dim3(kTailThreads), 0, s, t);
 }
 void launch_post_final(hipStream_t s, const float* hdr, const float* mip1, uint32_t mw, uint32_t mh, float* bloom0_out, uint8_t* out, uint32_t w, uint32_t h,
-                       float threshold, float falloff, float strength, float exposure, float gamma, bool linear_tap) {
+                       float threshold, float falloff, float strength, float exposure, float gamma, bool linear_tap, const float* scale) {
     const dim3 g(cdiv_(w, 64), cdiv_(h, 4)), b(256);
-    void (*k)(const float4*, const float4*, int, int, float4*, uchar4*, int, int, float, float, float, float, float);
+    void (*k)(const float4*, const float4*, int, int, float4*, uchar4*, int, int, float, float, float, float, float, const float*);
     if (mip1) k = linear_tap ? k_post_final<true, true> : k_post_final<true, false>;
     else k = linear_tap ? k_post_final<false, true> : k_post_final<false, false>;
     hipLaunchKernelGGL(k, g, b, 0, s, reinterpret_cast<const float4*>(hdr), reinterpret_cast<const float4*>(mip1), (int)mw, (int)mh,
-                       reinterpret_cast<float4*>(bloom0_out), reinterpret_cast<uchar4*>(out), (int)w, (int)h, threshold, falloff, strength, exposure, gamma);
+                       reinterpret_cast<float4*>(bloom0_out), reinterpret_cast<uchar4*>(out), (int)w, (int)h, threshold, falloff, strength, exposure, gamma, scale);
 }
 void launch_bloom_up(hipStream_t s, const float* in, uint32_t iw, uint32_t ih, float* out, uint32_t ow, uint32_t oh, float strength) {
     hipLaunchKernelGGL(k_bloom_up, dim3(cdiv_(ow, 64), cdiv_(oh, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(in), (int)iw, (int)ih,
@@ -730,9 +734,91 @@ void launch_bloom_up_chain(hipStream_t s, float* const* mips, const uint32_t* w,
     hipLaunchKernelGGL(k_bloom_up_chain, dim3(cdiv_(w[0], kTileW), cdiv_(h[0], kChainTileH)), dim3(256), 0, s, c);
 }
 void launch_tonemap(hipStream_t s, const float* hdr, const float* bloom0, uint8_t* out, uint32_t w, uint32_t h, float exposure, float gamma,
-                    bool linear_tap) {
+                    bool linear_tap, const float* scale) {
     hipLaunchKernelGGL(k_tonemap, dim3(cdiv_(w, 64), cdiv_(h, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(hdr),
-                       reinterpret_cast<const float4*>(bloom0), reinterpret_cast<uchar4*>(out), (int)w, (int)h, exposure, gamma, linear_tap ? 1 : 0);
+                       reinterpret_cast<const float4*>(bloom0), reinterpret_cast<uchar4*>(out), (int)w, (int)h, exposure, gamma, linear_tap ? 1 : 0, scale);
+}
+
+// ---- auto-exposure (api_post.hip enqueue_post, ahead of the bloom chain): exposure.hpp does all the arithmetic; the kernels only decide which lane
+// counts which pixel and which bin, and every sum is of integers, so the device gives the bits of the host compile (tests/test_gpu_exposure.py).
+namespace ex = exposure;
+
+// One pixel into its wave's sub-histogram.  A flat image — a wall, a black sky — puts all 64 lanes of a wave on one LDS word, where an atomic per lane
+// is served one lane after the other: the lanes that share the FIRST active lane's bin are counted by ballot and added once; only the others add one each.
+__device__ __forceinline__ void hist_count(uint32_t* mine, uint32_t bin) {
+    const uint32_t lead = __builtin_amdgcn_readfirstlane(bin);
+    const unsigned long long same = __ballot(bin == lead);
+    if (bin != lead) atomicAdd(&mine[bin], 1u);
+    else if (lanes_below(same) == 0u) atomicAdd(&mine[lead], (uint32_t)__popcll(same));
+}
+// A grid-stride pass, one coalesced float4 per lane and two of them in flight per trip; a sub-histogram per wave in LDS (16 KB), summed at the end and
+// flushed with one global atomic per non-empty bin per block.  At most kHistMaxBlocks blocks — one per CU, 16 waves each — so a bin's word sees at most
+// that many adds per image, spread over the time the blocks take to finish.
+__global__ __launch_bounds__(kHistThreads) void k_luminance_histogram(const float4* img, uint32_t n, float min_log2, float rcp_bin, uint32_t* acc) {
+    constexpr int kWaves = kHistThreads / 64;
+    __shared__ uint32_t sub[kWaves][ex::kBins];
+    for (int i = threadIdx.x; i < kWaves * ex::kBins; i += kHistThreads) (&sub[0][0])[i] = 0u;
+    __syncthreads();
+    uint32_t* mine = sub[threadIdx.x >> 6];
+    const size_t stride = (size_t)gridDim.x * kHistThreads;
+    for (size_t i = (size_t)blockIdx.x * kHistThreads + threadIdx.x; i < n; i += 2 * stride) {
+        const bool two = i + stride < n;
+        const float4 p = img[i];
+        float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (two) q = img[i + stride];
+        hist_count(mine, ex::bin_of(p.x, p.y, p.z, min_log2, rcp_bin));
+        if (two) hist_count(mine, ex::bin_of(q.x, q.y, q.z, min_log2, rcp_bin));
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)ex::kBins) {
+        uint32_t v = 0u;
+#pragma unroll
+        for (int k = 0; k < kWaves; k++) v += sub[k][threadIdx.x];
+        if (v) atomicAdd(&acc[threadIdx.x], v);
+    }
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+    return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src);
+}
+// One wave, four bins per lane: exposure.hpp's meter with its two running sums formed by a scan over the lanes (integers: the order cannot matter), then
+// adapt by lane 0.  The metered histogram is kept for read-back and the accumulating one zeroed, so the next metering needs no memset launch.
+__global__ __launch_bounds__(64) void k_exposure_adapt(ExposureDevice* d, ex::Plan p, uint32_t reset) {
+    const int lane = (int)threadIdx.x;
+    const uint4 h4 = reinterpret_cast<const uint4*>(d->acc)[lane];
+    reinterpret_cast<uint4*>(d->hist)[lane] = h4;
+    reinterpret_cast<uint4*>(d->acc)[lane] = make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t h[4] = {lane == 0 ? 0u : h4.x, h4.y, h4.z, h4.w};   // (bin 0, the black bin, counts nowhere)
+    const uint64_t own = ((uint64_t)h[0] + h[1]) + ((uint64_t)h[2] + h[3]);
+    uint64_t incl = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t below = shfl64(incl, lane >= o ? lane - o : lane);
+        if (lane >= o) incl += below;
+    }
+    const uint64_t N = shfl64(incl, 63);
+    const ex::Window w = ex::window_of(N, p.lo_q16, p.hi_q16);
+    uint64_t c = incl - own, S = 0u, W = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint64_t t = ex::take(c, h[k], w);   // (lane 0, k == 0: h is 0 and so is t)
+        W += t; S += t * (uint64_t)(4 * lane + k);
+        c += h[k];
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { S += shfl64(S, lane ^ o); W += shfl64(W, lane ^ o); }
+    if (lane == 0) {
+        ex::State s = d->state;
+        ex::adapt(s, ex::finish(N, S, W, p), p, reset);
+        d->state = s;
+    }
+}
+void launch_luminance_histogram(hipStream_t s, const float* img, uint32_t n, const exposure::Plan& p, ExposureDevice* d) {
+    const uint32_t blocks = cdiv_(n, kHistThreads) < kHistMaxBlocks ? cdiv_(n, kHistThreads) : kHistMaxBlocks;
+    hipLaunchKernelGGL(k_luminance_histogram, dim3(blocks), dim3(kHistThreads), 0, s, reinterpret_cast<const float4*>(img), n, p.min_log2, p.rcp_bin, d->acc);
+}
+void launch_exposure_adapt(hipStream_t s, const exposure::Plan& p, uint32_t reset, ExposureDevice* d) {
+    hipLaunchKernelGGL(k_exposure_adapt, dim3(1), dim3(64), 0, s, d, p, reset);
 }
 
 }  // namespace vpt

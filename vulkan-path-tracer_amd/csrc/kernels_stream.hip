@@ -437,3 +437,6 @@ int shade_stream_blocks_per_cu() {
     return nb > 0 ? nb : 1;
 }
 }  // namespace vpt
+
+// k_finish rides in this translation unit (same flags; one fat binary and its page padding less: DESIGN.md "Library size").
+#include "kernels_finish.hip"

@@ -793,3 +793,6 @@ int trace_shadow_blocks_per_cu() {
 }
 
 }  // namespace vpt
+
+// The auxiliary kernels (first hit, refit, resolve, ...) ride in this translation unit (same flags; one fat binary and its page padding less: DESIGN.md "Library size").
+#include "kernels_aux.hip"

@@ -21,6 +21,16 @@ uint64_t PostProcessor::PostProcessAsync(void* rgba8Device) {
     if (rc != VPT_OK) throw std::runtime_error(std::string("vpt_postprocess_device failed: ") + vpt_last_error(m_Source->Context()));
     return ticket;
 }
+void PostProcessor::SetAutoExposureData(const vpt_exposure_options& data) {
+    if (!m_Source || !m_Source->Context()) throw std::runtime_error("SetAutoExposureData: SetInputImage with a PathTracer that has a scene first");
+    if (vpt_set_exposure_options(m_Source->Context(), &data) != VPT_OK) throw std::runtime_error(std::string("vpt_set_exposure_options failed: ") + vpt_last_error(m_Source->Context()));
+}
+vpt_exposure_state PostProcessor::GetExposureState() const {
+    if (!m_Source || !m_Source->Context()) throw std::runtime_error("GetExposureState: SetInputImage with a PathTracer that has a scene first");
+    vpt_exposure_state s;
+    if (vpt_get_exposure_state(m_Source->Context(), &s) != VPT_OK) throw std::runtime_error(std::string("vpt_get_exposure_state failed: ") + vpt_last_error(m_Source->Context()));
+    return s;
+}
 const void* PostProcessor::GetOutputImageView() const { return m_Source && m_Source->Context() ? vpt_output_device(m_Source->Context()) : nullptr; }
 
 }  // namespace vpthost

@@ -25,6 +25,11 @@ public:
     void ReloadShaders() {}
     void SetTonemappingData(const TonemappingData& data) { m_Tonemap = data; }
     void SetBloomData(const BloomData& data) { m_Bloom = data; }
+    // Auto-exposure (an extension: no upstream member; include/vpt.h vpt_set_exposure_options): with mode 1 every PostProcess / PostProcessAsync meters the
+    // input image on the device and the tonemap multiplies by Exposure * the adapted scale.  The options are state of the INPUT's context: SetInputImage first.
+    static vpt_exposure_options DefaultAutoExposureData() { vpt_exposure_options o; vpt_default_exposure_options(&o); return o; }
+    void SetAutoExposureData(const vpt_exposure_options& data);
+    [[nodiscard]] vpt_exposure_state GetExposureState() const;   // waits for the work in flight; scale 1, valid 0 before the first metering
     [[nodiscard]] const std::vector<uint8_t>& GetOutputImage() const { return m_Output; }  // RGBA8 UNORM
 
 private:

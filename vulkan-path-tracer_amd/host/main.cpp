@@ -7,6 +7,8 @@
 //                               PREFIX_normal.png (n * 0.5 + 0.5) and PREFIX_albedo.png, each clamped to [0, 1], (uint8)(v * 255 + 0.5), alpha 255
 //              [--denoise [ITERATIONS]]   PathTracer::Denoise with the default parameters (ITERATIONS 0..6, default 5) after the render; --ppm / --png then come
 //                                         from the denoised image through the normal post chain (SetPostSource(VPT_POST_SOURCE_DENOISED))
+//              [--auto-exposure]   PostProcessor::SetAutoExposureData with both rates 1 before the final PostProcess: the exposure is metered from the image (a
+//                                  still: the one metering jumps to its target) instead of the constant 1; the adapted state is printed
 //              [--env-late]   apply --env-constant / --env-hdr after SetScene instead of before (the Editor's order of calls: the map is swapped on the installed scene)
 //              [--volume minx,miny,minz,maxx,maxy,maxz,density,g,r,g,b]... [--phase hg|draine|hg+draine]
 //              [--density-bricks FILE]   AddDensityDataToVolume on the last --volume, from 8x8x8 bricks: FILE = u32 dim_x, dim_y, dim_z, bricks; u32[3 * bricks]
@@ -47,7 +49,7 @@ int main(int argc, char** argv) {
     std::vector<PathTracer::Volume> volumes; std::vector<std::pair<uint32_t, std::string>> brickFiles; int phase = 0; bool atmosphere = false; float sunAlt = 0.0f, sunAz = 0.0f;
     uint32_t lutSamples = 10000000u, lutTime = 0; UVec3 lutSize{0, 0, 0};
     uint32_t w = 0, h = 0, spp = 16, depth = 8, seed = 1, split = 1, gpus = 1; std::vector<int> devices;
-    bool async = false, rayQueries = true, envLate = false; uint32_t asyncStep = 1; int denoise = -1;
+    bool async = false, rayQueries = true, envLate = false, autoExposure = false; uint32_t asyncStep = 1; int denoise = -1;
     bool info = false, selftest = false; float env[3] = {0, 0, 0}; bool haveEnv = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -77,6 +79,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--env-hdr") envHdr = next();          // SetEnvMapFilepath
         else if (a == "--env-late") envLate = true;
+        else if (a == "--auto-exposure") autoExposure = true;
         else if (a == "--dump-env") dumpEnv = next();        // with --env-hdr: decoded RGBA32F (no device needed)
         else if (a == "--decode-image") decodeImage = next(); // with --dump-image: a PNG / JPEG texture as the importer decodes it, raw RGBA8 (no device needed)
         else if (a == "--dump-image") dumpImage = next();
@@ -266,7 +269,16 @@ int main(int argc, char** argv) {
             (void)pt.Denoise(dp, false);
             pt.SetPostSource(VPT_POST_SOURCE_DENOISED);
         }
+        if (autoExposure) {
+            vpt_exposure_options eo = PostProcessor::DefaultAutoExposureData();
+            eo.mode = 1; eo.rate_up = eo.rate_down = 1.0f;
+            post.SetAutoExposureData(eo);
+        }
         post.PostProcess();
+        if (autoExposure) {
+            const vpt_exposure_state es = post.GetExposureState();
+            printf("auto-exposure: scale %g (2^%g), average luminance 2^%g over %llu pixels\n", es.scale, es.cur_log2, es.avg_log2, (unsigned long long)es.counted);
+        }
         if (!radiance.empty()) write_file(radiance, img.data(), img.size() * 4);
         if (!camera.empty()) { float m[32]; memcpy(m, pt.GetCameraViewInverse().m, 64); memcpy(m + 16, pt.GetCameraProjectionInverse().m, 64); write_file(camera, m, sizeof(m)); }
         if (!ppm.empty()) {
