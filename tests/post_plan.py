@@ -1,7 +1,9 @@
-"""The fused bloom/tonemap schedule restated in plain Python: which launches enqueue_post (csrc/api_post.hip) makes for an image
-size and a mip_count, and the tile ranges the two chain kernels (csrc/kernels_post.hip) evaluate per block.  Written from the
-C++ rules; it never calls into the library.  The constants are parsed out of the C++ sources, so a change of one of them moves
-the plan — and the case selection of tests/test_gpu_post_shapes.py that tests/test_post_plan_cpu.py checks — with it.
+"""The fused bloom/tonemap schedule restated in plain Python: which launches a vpt_postprocess makes for an image size and a
+mip_count (csrc/post_plan.hpp decides, csrc/api_post.hip's enqueue_post walks the plan), and the tile ranges the two chain
+kernels (csrc/kernels_post.hip) evaluate per block.  Written from the C++ rules; it never calls into the library or into the
+C++ plan: tests/test_post_plan_cpu.py holds the two to each other step by step.  The constants are parsed out of the C++
+sources, so a change of one of them moves the plan — and the case selection of tests/test_gpu_post_shapes.py that
+tests/test_post_plan_cpu.py checks — with it.
 
 Helper module: no tests, no GPU import."""
 import os
@@ -29,14 +31,14 @@ def parse_constants(*paths):
     return env
 
 
-K = parse_constants(os.path.join(_CSRC, "kernels.hpp"), os.path.join(_CSRC, "kernels_post.hip"))
-# what the partition depends on (the issue's five, and the two level limits next to them)
+K = parse_constants(os.path.join(_CSRC, "post_plan.hpp"), os.path.join(_CSRC, "kernels_post.hip"))
+# what the partition depends on (the issue's five, and the two level limits next to them): all of post_plan.hpp
 PLAN_CONSTANTS = ("kBloomTailMaxTexels", "kBloomTailMaxLevels", "kTailMaxBase", "kBloomDownChainTexels", "kBloomDownChainMax", "kBloomChainMax")
-MAX_MIPS = 10  # PostProcessor.cpp:136-157 (MAX_BLOOM_LEVELS), a literal in ensure_post_buffers
+MAX_MIPS = K["kMaxMips"]  # PostProcessor.cpp:136-157 (MAX_BLOOM_LEVELS)
 
 
 def mip_sizes(w, h):
-    """ensure_post_buffers: (width, height) of every bloom mip the context allocates."""
+    """post_plan.hpp mips_of: (width, height) of every bloom mip the context allocates."""
     out = []
     for _ in range(MAX_MIPS):
         out.append((w, h))
@@ -54,7 +56,7 @@ def clamp_mip_count(w, h, mip_count):
 
 
 def launches(w, h, mip_count, k=None):
-    """enqueue_post, fused schedule: [(entry, levels)] in launch order.  `levels` are the mip indices the launch produces
+    """post_plan.hpp fused_plan, restated: [(entry, levels)] in launch order.  `levels` are the mip indices the launch produces
     (down-samples, tail) or updates (up-samples: lowest first); the source of a down-sample launch is levels[0] - 1 and
     an up-sample launch reads levels[-1] + 1."""
     k = k or K
@@ -66,7 +68,7 @@ def launches(w, h, mip_count, k=None):
         if texels(i) <= k["kBloomTailMaxTexels"]:
             T = i
             break
-    if mc - T > k["kBloomTailMaxLevels"]:
+    if mc - T > k["kBloomTailMaxLevels"]:  # never taken with the shipped constants: post_plan.hpp states that as a static_assert; kept for other k
         T = mc
     out = []
     if mc >= 2:

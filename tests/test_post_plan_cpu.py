@@ -1,8 +1,14 @@
 """What the case table of tests/test_gpu_post_shapes.py reaches, checked without a GPU against tests/post_plan.py, the plain restatement
 of enqueue_post's fused schedule: a census of the launch kinds, level counts and odd-size classes a sweep of image sizes can produce
 (the table must reach all of them), the LDS bounds of the tail and of the two chain kernels over the same sweep, and the agreement of
-the two CPU references (the scalar oracle and the vectorised numpy restatement) at every case of the table."""
+the two CPU references (the scalar oracle and the vectorised numpy restatement) at every case of the table.
+
+And the restatement itself against what it restates: csrc/post_plan.hpp, the plan enqueue_post walks, compiled into the stand-alone
+tests/tools/post_plan_driver.cpp and compared step by step over the whole sweep — a second time under the address and undefined-behaviour
+sanitizers (the plan's steps live in a fixed-size array)."""
 import itertools
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -21,10 +27,105 @@ def test_constants_come_from_the_sources():
     for name in post_plan.PLAN_CONSTANTS + ("kTailMaxLevels", "kTailMaxTexels", "kTileW", "kChainTileH", "kChainW1", "kChainRows", "kChainMax",
                                             "kDcMax", "kDcTW", "kDcTH", "kDcW0", "kDcH0", "kDcW1", "kDcH1"):
         assert isinstance(K.get(name), int) and K[name] > 0, name
-    # the host's limits (kernels.hpp) and the kernels' own (kernels_post.hip) describe the same launches
+    # the plan's limits (post_plan.hpp) and the kernels' own (kernels_post.hip) describe the same launches
     assert K["kBloomChainMax"] == K["kChainMax"] and K["kBloomDownChainMax"] == K["kDcMax"]
     assert K["kBloomTailMaxLevels"] <= K["kTailMaxLevels"]
     assert (K["kDcW0"], K["kDcH0"], K["kDcW1"], K["kDcH1"]) == (41, 25, 19, 11)
+
+
+# ---- csrc/post_plan.hpp against the restatement: SWEEP_CASES, and every size again with a mip_count of 0 and beyond the mips there are
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAN_CASES = SWEEP_CASES + [(w, h, m) for w, h in itertools.product(SWEEP, SWEEP) for m in (0, post_plan.MAX_MIPS + 1, 4000)]
+FUSED, REFERENCE = 0, 1   # the driver's `schedule`
+
+
+def compile_plan_driver(exe, extra=()):
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror"] + list(extra) + ["-I", os.path.join(_ROOT, "vulkan-path-tracer_amd", "csrc"),
+                                                                                      os.path.join(_ROOT, "tests", "tools", "post_plan_driver.cpp"), "-o", exe])
+    return exe
+
+
+def plan_driver_input():
+    return "".join("%d %d %d %d\n" % (w, h, m, s) for s in (FUSED, REFERENCE) for w, h, m in PLAN_CASES)
+
+
+def parse_plan_line(line):
+    """-> ([(w, h)] of the mips, [(kind, first level, level count, staged)] in launch order)"""
+    head, _, tail = line.partition(" | ")
+    words = head.split()
+    assert words[0] == "mips" and int(words[1]) == len(words) - 2, line
+    steps = [s.split() for s in tail.split(";") if s.strip()]
+    return [tuple(int(v) for v in x.split("x")) for x in words[2:]], [(s[0], int(s[1]), int(s[2]), int(s[3])) for s in steps]
+
+
+def steps_of(launches):
+    """post_plan.launches' entries as the C++ plan holds them: (kind, first level, level count, staged).  The levels are the restatement's; a final
+    launch has one level when it up-samples mip 1 into mip 0 and none when there is no mip 1."""
+    out = []
+    for entry, levels in launches:
+        words = entry.split()
+        assert levels == list(range(levels[0], levels[0] + len(levels))), entry
+        if words[0] == "final":
+            assert levels == [0] and words[1] in ("up", "noup"), entry
+            out.append(("final", 0, 1 if words[1] == "up" else 0, 0))
+        elif words[0] == "tail":
+            assert words[1] in ("staged", "plain") and int(words[2]) == len(levels), entry
+            out.append(("tail", levels[0], len(levels), int(words[1] == "staged")))
+        else:
+            assert words[0] in ("first", "down", "down_chain", "up", "up_chain") and (len(words) == 1 or int(words[1]) == len(levels)), entry
+            out.append((words[0], levels[0], len(levels), 0))
+    return out
+
+
+@pytest.fixture(scope="module")
+def plan_driver_output(tmp_path_factory):
+    exe = compile_plan_driver(str(tmp_path_factory.mktemp("post_plan") / "post_plan_driver"))
+    out = subprocess.run([exe], input=plan_driver_input(), capture_output=True, text=True)
+    assert out.returncode == 0 and out.stderr == "", out.stderr[-2000:]
+    return out.stdout
+
+
+@pytest.fixture(scope="module")
+def cpp_plans(plan_driver_output):
+    lines = plan_driver_output.splitlines()
+    assert len(lines) == 2 * len(PLAN_CASES)
+    parsed = [parse_plan_line(l) for l in lines]
+    return {(s, c): parsed[s * len(PLAN_CASES) + i] for s in (FUSED, REFERENCE) for i, c in enumerate(PLAN_CASES)}
+
+
+def test_cpp_mip_sizes_equal_the_restatement(cpp_plans):
+    for (s, (w, h, m)), (sizes, _) in cpp_plans.items():
+        assert sizes == post_plan.mip_sizes(w, h), (w, h, m, s)
+
+
+def test_cpp_fused_plan_equals_the_restatement(cpp_plans):
+    """Entry by entry: kind, staged or plain, first level and level count of every launch, in launch order."""
+    kinds = set()
+    for w, h, m in PLAN_CASES:
+        _, steps = cpp_plans[FUSED, (w, h, m)]
+        assert steps == steps_of(post_plan.launches(w, h, m)), (w, h, m)
+        kinds |= {(k, st) for k, _, _, st in steps}
+    # (the sweep reaches every kind of launch, both tails among them)
+    assert kinds == {("first", 0), ("down", 0), ("down_chain", 0), ("tail", 0), ("tail", 1), ("up", 0), ("up_chain", 0), ("final", 0)}
+
+
+def test_cpp_reference_plan_has_the_shape_the_restatement_counts(cpp_plans):
+    for w, h, m in PLAN_CASES:
+        _, steps = cpp_plans[REFERENCE, (w, h, m)]
+        n = post_plan.clamp_mip_count(w, h, m)
+        assert steps == [("threshold", 0, 1, 0)] + [("down", i, 1, 0) for i in range(1, n)] + [("up", i - 1, 1, 0) for i in range(n - 1, 0, -1)] + [("tonemap", 0, 1, 0)], (w, h, m)
+        assert (len(steps) - 1, 1) == post_plan.reference_launches(w, h, m)
+
+
+def test_plan_driver_is_clean_under_the_sanitizers(plan_driver_output, tmp_path):
+    """The same program built with -fsanitize=address,undefined and made to stop at the first report, over the same input, as a process of its own: it
+    ends with status 0, reports nothing and prints what the plain build printed."""
+    exe = compile_plan_driver(str(tmp_path / "post_plan_driver_san"), extra=("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"))
+    out = subprocess.run([exe], input=plan_driver_input(), capture_output=True, text=True)
+    assert out.returncode == 0 and out.stderr == "", out.stderr[-2000:]
+    assert out.stdout == plan_driver_output
+    bad = subprocess.run([exe], input="64 64 x 0\n", capture_output=True, text=True)
+    assert bad.returncode == 2
 
 
 def test_plan_of_the_baseline_size():

@@ -40,7 +40,7 @@ void free_render_buffers(vpt_ctx* c) {
     if (c->gather_buf) (void)hipFree(c->gather_buf);
     c->gather_buf = nullptr;
     for (float* m : c->mips) (void)hipFree(m);
-    c->mips.clear(); c->mip_sizes.clear();
+    c->mips.clear(); c->mip_dims = post::Mips{};
     if (c->post_out) (void)hipFree(c->post_out);
     c->post_out = nullptr; c->post_w = c->post_h = 0;
     free_denoise_buffers(c);

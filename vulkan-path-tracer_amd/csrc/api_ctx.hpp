@@ -3,11 +3,14 @@
 //   api_context.hip  the context's life: create, size, configure, tear down; lanes, path buffers, the timing pool
 //   api_scene.hip    what a batch only reads: scene installation and its partial updates
 //   api_render.hip   a batch from decision to resolve; asynchronous batches, tickets, statistics
-//   api_post.hip     the image passes behind a render: post-process (bloom, tonemap, RGBA8), denoise, temporal accumulation with SVGF's variance and instance motion
+//   api_post.hip     the image passes behind a render: post-process (bloom, tonemap, RGBA8: one launch per step of post_plan.hpp's plan), denoise, temporal
+//                    accumulation with SVGF's variance and instance motion
 //   api_comm.hip     shards and gathers (the only file that sees RCCL)
 //   api_lab.hip      the vpt_lab_* entry points (laboratory library only)
 // None of them defines a __global__ function or launches one directly: the host layer calls the launch_* wrappers of kernels.hpp only.  That is
 // what keeps these files free of a fat binary of their own (_build.link), which the product library's size bound has no room for.
+// What these files decide is decided in headers that compile without HIP and are tested on the CPU — path_plan.hpp, scene_prep.hpp, camera_cull.hpp,
+// post_plan.hpp, exposure.hpp, denoise.hpp, temporal.hpp (the last four through kernels.hpp) — the files here turn the decisions into buffers and launches.
 // There is no CPU fallback in the host layer: without a HIP device vpt_create() fails.
 #pragma once
 #include <algorithm>
@@ -217,9 +220,9 @@ struct vpt_ctx {
     uint32_t frame_count = 0, samples_accum = 0;
     vpt_stats stats{};
 
-    // post
+    // post: the bloom mips of post_w x post_h — their sizes as post_plan.hpp's mips_of gives them, one allocation each
     std::vector<float*> mips;
-    std::vector<std::pair<uint32_t, uint32_t>> mip_sizes;
+    post::Mips mip_dims;
     uint8_t* post_out = nullptr;
     uint32_t post_w = 0, post_h = 0;
     // denoise (api_post.hip): allocated on the first vpt_denoise*, freed with the render buffers (vpt_resize, vpt_destroy)

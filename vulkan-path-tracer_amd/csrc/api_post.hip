@@ -1,5 +1,6 @@
 // api_post.hip — the image passes that run behind a render, each as a blocking entry and a _device entry queued behind the frames in flight:
-//   vpt_postprocess           the bloom chain + tonemap schedule (kernels_post.hip) and the RGBA8 output
+//   vpt_postprocess           the bloom chain + tonemap and the RGBA8 output: the mips' sizes and the schedule are post_plan.hpp's, enqueue_post meters the
+//                             exposure and then issues one launch (kernels_post.hip) per step of the plan
 //   vpt_denoise               the edge-avoiding a-trous filter over first-hit guides, variance-guided with vpt_svgf_options.variance
 //   vpt_temporal_accumulate   the image carried across camera and instance moves: the two records, SVGF's luminance moments and variance, the per-instance
 //                             motion tables and the motion image, with their options and read-backs
@@ -14,18 +15,14 @@ int ensure_post_buffers(vpt_ctx* c) {
     const uint32_t w = c->P.width, h = c->P.height;
     if (c->post_w == w && c->post_h == h && !c->mips.empty()) return VPT_OK;
     for (float* m : c->mips) (void)hipFree(m);
-    c->mips.clear(); c->mip_sizes.clear();
+    c->mips.clear();
     if (c->post_out) (void)hipFree(c->post_out);
     c->post_out = nullptr;
-    uint32_t cw = w, ch = h;
-    for (int i = 0; i < 10; i++) {  // PostProcessor.cpp:136-157 (MAX_BLOOM_LEVELS = 10)
+    c->mip_dims = post::mips_of(w, h);
+    for (uint32_t i = 0; i < c->mip_dims.count; i++) {
         float* m = nullptr;
-        HIPCHK(c, hipMalloc((void**)&m, (size_t)cw * ch * 16));
-        c->mips.push_back(m); c->mip_sizes.push_back({cw, ch});
-        if (cw % 2 != 0) cw -= 1;
-        if (ch % 2 != 0) ch -= 1;
-        cw /= 2; ch /= 2;
-        if (cw < 2 || ch < 2) break;
+        HIPCHK(c, hipMalloc((void**)&m, (size_t)c->mip_dims.texels(i) * 16));
+        c->mips.push_back(m);
     }
     HIPCHK(c, hipMalloc((void**)&c->post_out, (size_t)w * h * 4));
     c->post_w = w; c->post_h = h;
@@ -39,10 +36,7 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
     hipStream_t s = c->main.stream;
     const float* hdr = c->post_source == VPT_POST_SOURCE_DENOISED ? c->dn_out : whole_image(c);   // (post_source_ready has been asked)
     const uint32_t W = c->P.width, H = c->P.height;
-    uint32_t mip_count = std::max(1u, std::min(pp->mip_count, (uint32_t)c->mips.size()));
     const bool linear_tap = (c->params.flags & VPT_FLAG_TONEMAP_LINEAR_BLOOM_TAP) != 0;
-    auto MW = [&](uint32_t i) { return c->mip_sizes[i].first; };
-    auto MH = [&](uint32_t i) { return c->mip_sizes[i].second; };
     // Auto-exposure: the source image is metered before bloom and the tonemap kernels read the adapted scale from the device — nothing is read back or
     // waited for.  The two launches are timed with the tonemap.
     const float* scale = nullptr;
@@ -57,62 +51,28 @@ int enqueue_post(vpt_ctx* c, const vpt_post_params* pp, bool bloom0) {
         c->ex_reset = exposure::kResetNone; c->ex_metered = true;
         scale = &c->ex_dev->state.scale;
     }
-    if (pp->schedule == VPT_POST_REFERENCE_PASSES) {   // PostProcessor.cpp:193-246 pass by pass: threshold, down x (n-1), up x (n-1), tonemap
-        TIMED(c, s, VPT_K_BLOOM, launch_bloom_threshold(s, hdr, c->mips[0], W, H, pp->bloom_threshold, pp->falloff_range));
-        for (uint32_t i = 1; i < mip_count; i++)
-            TIMED(c, s, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
-        for (uint32_t i = mip_count - 1; i > 0; i--)
-            TIMED(c, s, VPT_K_BLOOM, launch_bloom_up(s, c->mips[i], MW(i), MH(i), c->mips[i - 1], MW(i - 1), MH(i - 1), pp->bloom_strength));
-        TIMED(c, s, VPT_K_TONEMAP, launch_tonemap(s, hdr, c->mips[0], c->post_out, W, H, pp->exposure, pp->gamma, linear_tap, scale));
-    } else {
-        // Fused schedule, same values (kernels_post.hip): mip 0 is never materialised unless the caller asks for it.
-        //   T = first mip the one-launch tail keeps in LDS (<= kBloomTailMaxTexels texels, and >= 2: its base mip must exist in memory)
-        uint32_t T = mip_count;
-        for (uint32_t i = 2; i < mip_count; i++) if ((uint64_t)MW(i) * MH(i) <= kBloomTailMaxTexels) { T = i; break; }
-        if (mip_count - T > kBloomTailMaxLevels) T = mip_count;   // cannot happen with <= 10 mips; the per-pass kernels cover it
-        if (mip_count >= 2) TIMED(c, s, VPT_K_BLOOM, launch_bloom_down_first(s, hdr, W, H, c->mips[1], MW(1), MH(1), pp->bloom_strength, pp->bloom_threshold, pp->falloff_range));
-        {   // down-samples between mip 1 and the tail's base: one launch each while the levels are large, the last (up to three, at most
-            // kBloomDownChainTexels texels in the first of them) in one launch
-            const uint32_t last = std::min(T, mip_count) - 1;   // last level produced here
-            uint32_t i = 2;
-            while (i <= last) {
-                const uint32_t left = last - i + 1;
-                if (left >= 2 && left <= kBloomDownChainMax && (uint64_t)MW(i) * MH(i) <= kBloomDownChainTexels) {
-                    float* lv[kBloomDownChainMax]; uint32_t lw[kBloomDownChainMax], lh[kBloomDownChainMax];
-                    for (uint32_t k = 0; k < left; k++) { lv[k] = c->mips[i + k]; lw[k] = MW(i + k); lh[k] = MH(i + k); }
-                    TIMED(c, s, VPT_K_BLOOM, launch_bloom_down_chain(s, c->mips[i - 1], MW(i - 1), MH(i - 1), lv, lw, lh, left, pp->bloom_strength));
-                    i += left;
-                } else {
-                    TIMED(c, s, VPT_K_BLOOM, launch_bloom_down(s, c->mips[i - 1], MW(i - 1), MH(i - 1), c->mips[i], MW(i), MH(i), pp->bloom_strength));
-                    i++;
-                }
-            }
+    // Which launches, on which levels, is post_plan.hpp's decision: one launch per step, in the plan's order.
+    const post::Mips& m = c->mip_dims;
+    float* const* mips = c->mips.data();
+    const post::Plan plan = pp->schedule == VPT_POST_REFERENCE_PASSES ? post::reference_plan(m, pp->mip_count) : post::fused_plan(m, pp->mip_count);
+    auto launch = [&](const post::Step& st) {
+        const uint32_t f = st.first, n = st.count;
+        switch (st.kind) {
+        case post::kThreshold: launch_bloom_threshold(s, hdr, mips[0], W, H, pp->bloom_threshold, pp->falloff_range); break;
+        case post::kDownFirst: launch_bloom_down_first(s, hdr, W, H, mips[1], m.w[1], m.h[1], pp->bloom_strength, pp->bloom_threshold, pp->falloff_range); break;
+        case post::kDown: launch_bloom_down(s, mips[f - 1], m.w[f - 1], m.h[f - 1], mips[f], m.w[f], m.h[f], pp->bloom_strength); break;
+        case post::kDownChain: launch_bloom_down_chain(s, mips, m, f, n, pp->bloom_strength); break;
+        case post::kTail: launch_bloom_tail(s, mips, m, f, n, st.staged != 0, pp->bloom_strength); break;
+        case post::kUp: launch_bloom_up(s, mips[f + 1], m.w[f + 1], m.h[f + 1], mips[f], m.w[f], m.h[f], pp->bloom_strength); break;
+        case post::kUpChain: launch_bloom_up_chain(s, mips, m, f, n, pp->bloom_strength); break;
+        case post::kFinal:   // n == 1: mip 1 is up-sampled inside the launch; bloom0: the caller wants mip 0, which nothing else materialises
+            launch_post_final(s, hdr, n ? mips[1] : nullptr, n ? m.w[1] : 0u, n ? m.h[1] : 0u, bloom0 ? mips[0] : nullptr, c->post_out, W, H, pp->bloom_threshold,
+                              pp->falloff_range, pp->bloom_strength, pp->exposure, pp->gamma, linear_tap, scale);
+            break;
+        case post::kTonemap: launch_tonemap(s, hdr, mips[0], c->post_out, W, H, pp->exposure, pp->gamma, linear_tap, scale); break;
         }
-        uint32_t up_from = std::min(T, mip_count) - 1;   // the highest level that is final once the tail has run
-        if (T < mip_count) {
-            uint32_t tw[kBloomTailMaxLevels], th[kBloomTailMaxLevels];
-            for (uint32_t i = T; i < mip_count; i++) { tw[i - T] = MW(i); th[i - T] = MH(i); }
-            const bool staged = bloom_tail_is_staged(MW(T - 1), MH(T - 1));
-            TIMED(c, s, VPT_K_BLOOM, launch_bloom_tail(s, c->mips[T - 1], c->mips[T], MW(T - 1), MH(T - 1), tw, th, mip_count - T, pp->bloom_strength));
-            if (staged) up_from = T;   // the staged tail leaves mip T finished in memory and mip T - 1 as the down-samples left it
-        }
-        // up-samples of the levels between the tail and mip 1: up to kBloomChainMax of them per launch, only the lowest level written
-        // (the levels between are read by nothing else)
-        for (uint32_t top = up_from; top > 1;) {
-            const uint32_t n = std::min(top - 1u, kBloomChainMax), base = top - n;
-            if (n == 1) {
-                TIMED(c, s, VPT_K_BLOOM, launch_bloom_up(s, c->mips[top], MW(top), MH(top), c->mips[base], MW(base), MH(base), pp->bloom_strength));
-            } else {
-                float* lv[kBloomChainMax + 1]; uint32_t lw[kBloomChainMax + 1], lh[kBloomChainMax + 1];
-                for (uint32_t k = 0; k <= n; k++) { lv[k] = c->mips[base + k]; lw[k] = MW(base + k); lh[k] = MH(base + k); }
-                TIMED(c, s, VPT_K_BLOOM, launch_bloom_up_chain(s, lv, lw, lh, n, pp->bloom_strength));
-            }
-            top = base;
-        }
-        TIMED(c, s, VPT_K_TONEMAP, launch_post_final(s, hdr, mip_count >= 2 ? c->mips[1] : nullptr, mip_count >= 2 ? MW(1) : 0u, mip_count >= 2 ? MH(1) : 0u,
-                                                  bloom0 ? c->mips[0] : nullptr, c->post_out, W, H, pp->bloom_threshold, pp->falloff_range, pp->bloom_strength,
-                                                  pp->exposure, pp->gamma, linear_tap, scale));
-    }
+    };
+    for (uint32_t i = 0; i < plan.n; i++) TIMED(c, s, plan.steps[i].kind < post::kFinal ? VPT_K_BLOOM : VPT_K_TONEMAP, launch(plan.steps[i]));
     return VPT_OK;
 }
 // A temporal result / a denoised image of the current size exists: not before the first call, and not after a resize.

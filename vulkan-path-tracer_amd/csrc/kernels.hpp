@@ -1,9 +1,11 @@
-// kernels.hpp — host-callable launch wrappers of the HIP stages (definitions in kernels_*.hip).
+// kernels.hpp — host-callable launch wrappers of the HIP stages (definitions in kernels_*.hip).  The limits of the post chain's schedule (how many levels a
+// tail or a chain takes, which base a tail stages) are not here: post_plan.hpp holds them once, with the plan that uses them.
 #pragma once
 #include "device_types.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
 #include "exposure.hpp"
+#include "post_plan.hpp"
 #include "whole_deal.hpp"   // + camera_cull.hpp
 #include "../../include/vpt_lab.h"   // VPT_TRACE_* / VPT_LAB_* constants (the functions exist in the laboratory build only)
 #ifndef VPT_LAB
@@ -125,26 +127,22 @@ int trace_shadow_blocks_per_cu();
 void launch_lut(hipStream_t s, int kind, float* table, uint32_t sx, uint32_t sy, uint32_t sz, uint32_t sample_count, uint32_t time_hash,
                 uint32_t first_dispatch, uint32_t n_dispatches);
 
-// post-process chain (kernels_post.hip)
+// post-process chain (kernels_post.hip).  Which of these a vpt_postprocess launches, on which levels, is post_plan.hpp's decision; the wrappers that take
+// (mips, m, first, n) serve one of its steps: mips = the context's mip pointers, m = their sizes, [first, first + n) = the step's levels
 void launch_bloom_threshold(hipStream_t s, const float* in, float* out, uint32_t w, uint32_t h, float threshold, float falloff);
 void launch_bloom_down(hipStream_t s, const float* in, uint32_t iw, uint32_t ih, float* out, uint32_t ow, uint32_t oh, float strength);
 void launch_bloom_up(hipStream_t s, const float* in, uint32_t iw, uint32_t ih, float* out, uint32_t ow, uint32_t oh, float strength);
-// levels mips[0 .. n - 1] receive their up-samples in one launch (only mips[0] is written); mips[n] is read as it stands; n <= kBloomChainMax
-constexpr uint32_t kBloomChainMax = 4;
-// outs[0 .. n - 1] = successive down-samples of `in`, all written, one launch; n = 2 or 3 (kBloomDownChainMax)
-constexpr uint32_t kBloomDownChainMax = 3;
-constexpr uint32_t kBloomDownChainTexels = 160000;   // 480 x 270 and below: smaller than what fills the chip for the length of a launch
-void launch_bloom_down_chain(hipStream_t s, const float* in, uint32_t iw, uint32_t ih, float* const* outs, const uint32_t* w, const uint32_t* h, uint32_t n, float strength);
-void launch_bloom_up_chain(hipStream_t s, float* const* mips, const uint32_t* w, const uint32_t* h, uint32_t n, float strength);
+// mips[first .. first + n - 1] = successive down-samples of mips[first - 1], all written, one launch; n = 2 or 3
+void launch_bloom_down_chain(hipStream_t s, float* const* mips, const post::Mips& m, uint32_t first, uint32_t n, float strength);
+// mips[first .. first + n - 1] receive their up-samples in one launch (only mips[first] is written); mips[first + n] is read as it stands; n = 2 .. 4
+void launch_bloom_up_chain(hipStream_t s, float* const* mips, const post::Mips& m, uint32_t first, uint32_t n, float strength);
 // fused schedule: threshold inside the first down-sample, the small mips down and up in one launch, last up-sample + tonemap in one
 void launch_bloom_down_first(hipStream_t s, const float* hdr, uint32_t iw, uint32_t ih, float* out, uint32_t ow, uint32_t oh, float strength, float threshold, float falloff);
-// staged (base mip <= 8448 texels, bloom_tail_is_staged): levels w[0..] go down and up in LDS and level 0, finished, is written to top_out — the
-// up-sample into the base is the caller's (the up chain's); otherwise (huge base) the base itself is updated and top_out is not used
-bool bloom_tail_is_staged(uint32_t bw, uint32_t bh);
-void launch_bloom_tail(hipStream_t s, float* base, float* top_out, uint32_t bw, uint32_t bh, const uint32_t* w, const uint32_t* h, uint32_t levels, float strength);
+// staged (the plan's choice, for a base mip small enough to be kept in LDS): mips[first .. first + n - 1] go down and up in LDS and mips[first], finished, is written —
+// the up-sample into the base, mips[first - 1], is the caller's (the up chain's); otherwise (huge base) the base itself is updated and mips[first] is not written
+void launch_bloom_tail(hipStream_t s, float* const* mips, const post::Mips& m, uint32_t first, uint32_t n, bool staged, float strength);
 void launch_post_final(hipStream_t s, const float* hdr, const float* mip1, uint32_t mw, uint32_t mh, float* bloom0_out, uint8_t* out, uint32_t w, uint32_t h,
                        float threshold, float falloff, float strength, float exposure, float gamma, bool linear_tap, const float* scale = nullptr);
-constexpr uint32_t kBloomTailMaxTexels = 2048, kBloomTailMaxLevels = 8;   // largest mip the one-launch tail keeps in LDS; levels it can hold
 void launch_tonemap(hipStream_t s, const float* hdr, const float* bloom0, uint8_t* out, uint32_t w, uint32_t h, float exposure,
                     float gamma, bool linear_tap, const float* scale = nullptr);
 // Auto-exposure (exposure.hpp holds the arithmetic).  scale (launch_tonemap, launch_post_final; device memory): nullptr — the multiply is c * exposure, the

@@ -149,6 +149,7 @@ __global__ __launch_bounds__(256) void k_tonemap(const float4* hdr, const float4
 // optional bloom mip 0 stay bit-identical (tests/test_gpu_post.py runs both schedules).
 
 constexpr int kTailThreads = 1024, kTailMaxLevels = 8, kTailMaxTexels = 2048 + 512 + 128 + 32 + 8 + 2 + 1 + 1;
+static_assert(post::kBloomTailMaxLevels <= (uint32_t)kTailMaxLevels, "BloomTail holds every level the plan gives a tail");
 struct BloomTail {
     float4* base;              // the mip above the tail (global memory): read by the first down-sample; updated by the last up-sample unless top_out
     float4* top_out;           // staged variant: the tail's first level, finished, goes here instead (the up-sample INTO the base — four times
@@ -180,9 +181,9 @@ __device__ __forceinline__ V3 up_taps(const float4* src, int iw, int ih, int x, 
 // instruction chain, so the staged variant keeps every operand a phase needs where it is cheapest to reach: the level loop is unrolled
 // (sizes and offsets of a level are scalars, not indexed loads from the argument block) and every source is an LDS array by type
 // (a pointer that may be global or LDS compiles to flat loads, which wait for both memory pipelines).
-// STAGED: the base mip (<= kTailMaxBase texels) is copied into LDS once, as rgb — its 16-tap reads by the first down-sample (32 k
+// STAGED: the base mip (<= kTailMaxBase texels, post_plan.hpp's: the plan decides with it, the kernel sizes its array by it) is copied into LDS once, as rgb — its 16-tap reads by the first down-sample (32 k
 // 16-byte loads through one CU's L1) and its read-modify-write by the last up-sample become one coalesced read and one coalesced write.
-constexpr int kTailMaxBase = 8448;
+using post::kTailMaxBase;
 template <bool STAGED>
 __global__ __launch_bounds__(kTailThreads) void k_bloom_tail(BloomTail t) {
     __shared__ float4 m[kTailMaxTexels];
@@ -297,6 +298,7 @@ __global__ __launch_bounds__(kTailThreads) void k_bloom_tail(BloomTail t) {
 // evaluate too (1.4-1.6 x redundant on levels of a few thousand texels).  Every texel by k_bloom_down's expression in its tap order; a
 // tile entry at an out-of-range position holds the clamped texel's value, so the next level indexes the tile with unclamped taps.
 constexpr int kDcMax = 3, kDcTW = 8, kDcTH = 4;
+static_assert((uint32_t)kDcMax == post::kBloomDownChainMax, "DownChain holds the levels the plan gives a down chain");
 constexpr int kDcW1 = 2 * kDcTW + 3, kDcH1 = 2 * kDcTH + 3, kDcW0 = 2 * kDcW1 + 3, kDcH0 = 2 * kDcH1 + 3;   // 19 x 11, 41 x 25
 struct DownChain {
     int n;                       // levels produced (2 or 3)
@@ -362,6 +364,7 @@ __global__ __launch_bounds__(256) void k_bloom_down_chain(DownChain c) {
 // first, every texel by k_bloom_up's expression in its tap order.  A tile entry at an out-of-range position holds the clamped texel's
 // value (the reference clamps tap coordinates), so the next level indexes the tile with unclamped taps.
 constexpr int kChainMax = 4, kChainTileH = 8, kChainW1 = kTileW / 2 + 3, kChainRows = kChainTileH / 2 + 3;   // level 1 of the chain: 35 x 7
+static_assert((uint32_t)kChainMax == post::kBloomChainMax, "UpChain holds the levels the plan gives an up chain");
 struct UpChain {
     int n;                          // levels computed (1 .. kChainMax)
     float4* mip[kChainMax + 1];     // mip[0]: updated in place; mip[1 .. n - 1]: the down-sampled levels (read only); mip[n]: final, read only
@@ -696,13 +699,14 @@ void launch_bloom_down_first(hipStream_t s, const float* hdr, uint32_t iw, uint3
     hipLaunchKernelGGL(k_bloom_down<true>, dim3(cdiv_(ow, 64), cdiv_(oh, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(hdr), (int)iw, (int)ih,
                        reinterpret_cast<float4*>(out), (int)ow, (int)oh, strength, threshold, falloff);
 }
-bool bloom_tail_is_staged(uint32_t bw, uint32_t bh) { return (uint64_t)bw * bh <= (uint64_t)kTailMaxBase; }
-void launch_bloom_tail(hipStream_t s, float* base, float* top_out, uint32_t bw, uint32_t bh, const uint32_t* w, const uint32_t* h, uint32_t levels, float strength) {
+// The wrappers of a plan's multi-level steps (post_plan.hpp): the step's levels are mips[first .. first + n - 1] with the sizes m has for them.
+void launch_bloom_tail(hipStream_t s, float* const* mips, const post::Mips& m, uint32_t first, uint32_t n, bool staged, float strength) {
     BloomTail t{};
-    t.base = reinterpret_cast<float4*>(base); t.top_out = reinterpret_cast<float4*>(top_out); t.bw = (int)bw; t.bh = (int)bh; t.levels = (int)levels; t.strength = strength;
+    t.base = reinterpret_cast<float4*>(mips[first - 1]); t.top_out = reinterpret_cast<float4*>(mips[first]); t.bw = (int)m.w[first - 1]; t.bh = (int)m.h[first - 1];
+    t.levels = (int)n; t.strength = strength;
     int off = 0;
-    for (uint32_t k = 0; k < levels; k++) { t.w[k] = (int)w[k]; t.h[k] = (int)h[k]; t.off[k] = off; off += (int)(w[k] * h[k]); }
-    void (*k)(BloomTail) = bloom_tail_is_staged(bw, bh) ? k_bloom_tail<true> : k_bloom_tail<false>;
+    for (uint32_t k = 0; k < n; k++) { t.w[k] = (int)m.w[first + k]; t.h[k] = (int)m.h[first + k]; t.off[k] = off; off += (int)m.texels(first + k); }
+    void (*k)(BloomTail) = staged ? k_bloom_tail<true> : k_bloom_tail<false>;
     hipLaunchKernelGGL(k, dim3(1), dim3(kTailThreads), 0, s, t);
 }
 void launch_post_final(hipStream_t s, const float* hdr, const float* mip1, uint32_t mw, uint32_t mh, float* bloom0_out, uint8_t* out, uint32_t w, uint32_t h,
@@ -718,20 +722,24 @@ void launch_bloom_up(hipStream_t s, const float* in, uint32_t iw, uint32_t ih, f
     hipLaunchKernelGGL(k_bloom_up, dim3(cdiv_(ow, 64), cdiv_(oh, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(in), (int)iw, (int)ih,
                        reinterpret_cast<float4*>(out), (int)ow, (int)oh, strength);
 }
-void launch_bloom_down_chain(hipStream_t s, const float* in, uint32_t iw, uint32_t ih, float* const* outs, const uint32_t* w, const uint32_t* h, uint32_t n, float strength) {
+void launch_bloom_down_chain(hipStream_t s, float* const* mips, const post::Mips& m, uint32_t first, uint32_t n, float strength) {
     DownChain c{};
-    c.n = (int)n; c.in = reinterpret_cast<const float4*>(in); c.iw = (int)iw; c.ih = (int)ih; c.strength = strength;
-    for (uint32_t j = 0; j < kDcMax; j++) { const uint32_t k = j < n ? j : n - 1; c.out[j] = reinterpret_cast<float4*>(outs[k]); c.w[j] = (int)w[k]; c.h[j] = (int)h[k]; }
-    hipLaunchKernelGGL(k_bloom_down_chain, dim3(cdiv_(w[n - 1], kDcTW), cdiv_(h[n - 1], kDcTH)), dim3(256), 0, s, c);
+    c.n = (int)n; c.in = reinterpret_cast<const float4*>(mips[first - 1]); c.iw = (int)m.w[first - 1]; c.ih = (int)m.h[first - 1]; c.strength = strength;
+    for (uint32_t j = 0; j < kDcMax; j++) {   // unused levels repeat the last one
+        const uint32_t k = first + (j < n ? j : n - 1);
+        c.out[j] = reinterpret_cast<float4*>(mips[k]); c.w[j] = (int)m.w[k]; c.h[j] = (int)m.h[k];
+    }
+    const uint32_t top = first + n - 1;
+    hipLaunchKernelGGL(k_bloom_down_chain, dim3(cdiv_(m.w[top], kDcTW), cdiv_(m.h[top], kDcTH)), dim3(256), 0, s, c);
 }
-void launch_bloom_up_chain(hipStream_t s, float* const* mips, const uint32_t* w, const uint32_t* h, uint32_t n, float strength) {
+void launch_bloom_up_chain(hipStream_t s, float* const* mips, const post::Mips& m, uint32_t first, uint32_t n, float strength) {
     UpChain c{};
     c.n = (int)n; c.strength = strength;
     for (uint32_t j = 0; j <= kChainMax; j++) {   // unused levels repeat the last one: the range arithmetic stays defined
-        const uint32_t k = j <= n ? j : n;
-        c.mip[j] = reinterpret_cast<float4*>(mips[k]); c.w[j] = (int)w[k]; c.h[j] = (int)h[k];
+        const uint32_t k = first + (j <= n ? j : n);
+        c.mip[j] = reinterpret_cast<float4*>(mips[k]); c.w[j] = (int)m.w[k]; c.h[j] = (int)m.h[k];
     }
-    hipLaunchKernelGGL(k_bloom_up_chain, dim3(cdiv_(w[0], kTileW), cdiv_(h[0], kChainTileH)), dim3(256), 0, s, c);
+    hipLaunchKernelGGL(k_bloom_up_chain, dim3(cdiv_(m.w[first], kTileW), cdiv_(m.h[first], kChainTileH)), dim3(256), 0, s, c);
 }
 void launch_tonemap(hipStream_t s, const float* hdr, const float* bloom0, uint8_t* out, uint32_t w, uint32_t h, float exposure, float gamma,
                     bool linear_tap, const float* scale) {
