@@ -2,7 +2,7 @@
 // searches on the tree in memory; k_finish_done, launch_finish and finish_blocks_per_cu.
 #include "kernels.hpp"
 #include "traverse.hpp"
-#include "wave.hpp"
+#include "wave_cursor.hpp"
 #include "shade_core.hpp"
 #include "vote.hpp"
 
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kTraverseBlock, VPT_FINISH_MIN_BLOCKS) void k_finis
     const uint32_t n = sctr->queue_len[parity].v;
     TravStats st, sst; st.nodes = 0; st.tris = 0; sst.nodes = 0; sst.tris = 0;
     uint32_t w_paths = 0u, w_rays = 0u, w_taken = 0u;   // wave totals (uniform): closest-hit rays, shadow rays, paths taken over
-    // the wave's cursor into the queue, wave-uniform by construction (kernels_trace.hip k_trace_vote)
+    // the wave's cursor into the queue: wave_cursor.hpp DealCursor's statements, written out on local scalars, wave-uniform by construction (that header says why both)
     const uint32_t n_static = gridDim.x * (kTraverseBlock / 64u) * 64u;
     uint32_t w_next = __builtin_amdgcn_readfirstlane((blockIdx.x * (kTraverseBlock / 64u) + (threadIdx.x >> 6)) * 64u), w_end = w_next + 64u < n ? w_next + 64u : n;
     if (w_next >= n) { w_next = 0u; w_end = 0u; }

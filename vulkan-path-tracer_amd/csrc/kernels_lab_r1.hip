@@ -2,7 +2,7 @@
 // launchers and occupancy helpers.  Laboratory library only (_build.LAB_SOURCES): the product neither compiles nor declares any of it.
 #include "kernels.hpp"
 #include "traverse.hpp"
-#include "wave.hpp"
+#include "wave_cursor.hpp"
 #include "shade_core.hpp"
 
 namespace vpt {

@@ -20,6 +20,7 @@
 #include "kernels.hpp"
 #include "shade_core.hpp"
 #include "vote.hpp"
+#include "wave_cursor.hpp"
 
 namespace vpt {
 
@@ -28,28 +29,6 @@ namespace {
 constexpr uint32_t kMF_Sky = 1u, kMF_Light = 2u, kMF_SkyAdd = 4u, kMF_LightAdd = 8u, kMF_SkyKindShift = 4u, kMF_LightKind = 64u, kMF_InMedium = 128u,
                    kMF_Aborted = 256u;
 
-// the wave's next 64 queue entries: its static first 64, then chunks through the cursor (as k_shade_stream)
-struct WaveCursor {
-    uint32_t pos, end, n, active, chunk;
-    bool done;
-    __device__ __forceinline__ void init(uint32_t gw, uint32_t n_, uint32_t active_) {
-        n = n_; active = active_; chunk = fetch_chunk(n_); pos = gw * 64u; end = pos + 64u; done = false;
-    }
-    // returns false when the queue is exhausted; otherwise `i` is this lane's entry (may be >= n: no entry)
-    __device__ __forceinline__ bool next(uint32_t* head, uint32_t& i) {
-        while (pos >= end || pos >= n) {
-            if (done || active * 64u >= n) { done = true; return false; }
-            uint32_t nb = 0u;
-            if (lane_id() == 0u) nb = atomicAdd(head, chunk);
-            pos = active * 64u + __builtin_amdgcn_readfirstlane(nb);
-            end = pos + chunk;
-            if (pos >= n) { done = true; return false; }
-        }
-        i = pos + lane_id();
-        pos += 64u;
-        return true;
-    }
-};
 }  // namespace
 
 // ------------------------------------------------------------------ scatter decision (RayGen.slang:76-88, 162-262)
@@ -88,7 +67,7 @@ __global__ __launch_bounds__(256, 3) void k_shade_media(DeviceScene sc, RenderPa
     const bool exact = sctr->class_exact[0] != 0u;
     WaveAppender a_sky, a_light;
     a_sky.init(gw, exact); a_light.init(gw, exact);
-    WaveCursor cur; cur.init(gw, n, active);
+    StrideCursor cur; cur.init(gw, n, active);   // the wave's next 64 queue entries (wave_cursor.hpp)
     uint32_t w_paths = 0u, w_rays = 0u;
     uint32_t i;
     while (cur.next(&sctr->class_head[0].v, i)) {
@@ -164,7 +143,7 @@ __global__ __launch_bounds__(256, 3) void k_media_tail(DeviceScene sc, RenderPar
     const bool exact = sctr->class_exact[0] != 0u;
     WaveAppender a_next;
     a_next.init(gw, exact);
-    WaveCursor cur; cur.init(gw, n, active);
+    StrideCursor cur; cur.init(gw, n, active);   // the wave's next 64 queue entries (wave_cursor.hpp)
     uint32_t w_alive = 0u, w_pend = 0u;
     uint32_t i;
     while (cur.next(&sctr->class_head[1].v, i)) {

@@ -14,6 +14,7 @@
 #include "kernels.hpp"
 #include "shade_core.hpp"
 #include "vote.hpp"
+#include "wave_cursor.hpp"
 
 namespace vpt {
 
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256, VPT_SHADE_MIN_BLOCKS) void k_shade_stream(Devi
     __shared__ float4 r_h[4][128];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t hit_head = 0u, hit_count = 0u, miss_head = 0u, miss_count = 0u;   // wave-uniform
-    uint32_t pos = gw * 64u, end = pos + 64u;      // the wave's static first 64 entries, then chunks through the cursor
+    uint32_t pos = gw * 64u, end = pos + 64u;      // the wave's static first 64 entries, then chunks through the cursor (wave_cursor.hpp StrideCursor's statements)
     bool done = false;
     while (true) {
         {

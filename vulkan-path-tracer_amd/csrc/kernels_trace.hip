@@ -5,7 +5,7 @@
 //                  (the structure of round 1's extend kernel, kept as the measured baseline)
 //   k_trace_vote   persistent lanes with a wave-level vote: every iteration the wave executes ONE kind of step for the
 //                  lanes that want it — an inner-node step (fetch 64 B, four slab tests, order, push), a triangle step
-//                  (ONE triangle of the lane's current leaf) or a fetch step (retire finished rays, load new ones into
+//                  (up to two triangles of the lane's current leaf; one in the counting and validating forms) or a fetch step (retire finished rays, load new ones into
 //                  the idle lanes) — chosen by ballot/popcount as the kind most lanes are waiting for.  A lane that
 //                  reached a leaf no longer drags the whole wave through the triangle code while its neighbours sit at
 //                  inner nodes, a leaf of four triangles no longer makes one-triangle lanes wait, and a finished lane is
@@ -16,7 +16,7 @@
 // same (t, u, v, primitive, instance) for a ray whatever it visits first.
 #include "kernels.hpp"
 #include "traverse.hpp"
-#include "wave.hpp"
+#include "wave_cursor.hpp"
 #include "vote.hpp"
 
 namespace vpt {
@@ -84,8 +84,8 @@ __global__ __launch_bounds__(kTraverseBlock, 8) void k_trace_base(DeviceScene sc
 
 // ------------------------------------------------------------------ vote-scheduled persistent lanes
 // Lane state: `cur` >= 0 inner node to visit; < 0 leaf code ~(first << 3 | count - 1) with `first` advancing as the
-// triangles are consumed; kLaneDone / kLaneIdle.  The wave owns a chunk [w_next, w_end) of the stream (one atomic per
-// chunk) and deals its entries to idle lanes in fetch steps.
+// triangles are consumed; kLaneDone / kLaneIdle.  The wave owns a run [w_next, w_end) of the stream (wave_cursor.hpp: its own
+// 64 entries first, then chunks, one atomic per chunk) and deals its entries to idle lanes in fetch steps.
 // TUNED: the vote parameters are the compile-time defaults (fetch step at 16 idle lanes, weighted vote: kVoteParamDefault), which
 // the pipeline always uses; the lab's other settings go through the instantiation that reads them from a.param.
 // STRICT (VPT_FLAG_LOCAL_HITS, traverse.hpp trace_closest_strict / trace_occluded_strict): a closest-hit winner is validated when its
@@ -106,8 +106,8 @@ __global__ __launch_bounds__(kTraverseBlock, 8) void k_trace_vote(DeviceScene sc
     const uint32_t fetch_at = TUNED ? kVoteFetchAt : (a.param & 0xffu) ? (a.param & 0xffu) : 16u;  // idle lanes that trigger a fetch step (64: only when all are idle)
     const bool weighted = TUNED || ((a.param >> 8) & 1u) != 0u;  // vote by lanes served per instruction issued: a triangle step costs about half a node step
     const uint32_t w4 = TUNED ? kVoteWeight4 : ((a.param >> 12) & 15u) ? ((a.param >> 12) & 15u) : kVoteWeight4;   // the weight in quarters (lab: bits 12-15)
-    // every wave starts on its own 64 entries without an atomic (8192 waves fetching at once would queue ~90 us on the cursor);
-    // entries beyond the grid's static part are fetched chunk-wise through the cursor
+    // every wave starts on its own 64 entries without an atomic, entries beyond the grid's static part are fetched chunk-wise through the
+    // cursor: DealCursor's statements (wave_cursor.hpp) on local scalars — that header says why this kernel does not hold the struct
     const uint32_t n_static = gridDim.x * (kTraverseBlock / 64u) * 64u;
     // wave-uniform on purpose (readfirstlane): with the wave index taken from threadIdx the compiler must treat the chunk bounds, and
     // through them `exhausted` and every branch of the vote loop, as divergent, which turns the loop into exec-masked regions with
@@ -307,14 +307,10 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_trace_pool(DeviceScene sc
     const BvhNode* const nodes = sc.nodes;
     const BvhTri* const tris = sc.tris;
     const uint32_t n = a.n_dev ? *a.n_dev : a.n;
-    const uint32_t chunk = fetch_chunk(n);
     const uint32_t fetch_at = (a.param & 0xffu) ? (a.param & 0xffu) : (uint32_t)SLOTS * 5u / 16u;   // idle SLOTS that trigger a fetch step
     const uint32_t w4 = ((a.param >> 12) & 15u) ? ((a.param >> 12) & 15u) : kVoteWeight4;
     const uint32_t tri_at = ((a.param >> 16) & 63u) ? ((a.param >> 16) & 63u) : 32u;                  // DUAL: slots at leaves that make an iteration carry a triangle step
-    const uint32_t n_static = gridDim.x * (kTraverseBlock / 64u) * (uint32_t)SLOTS;   // every wave starts on its own SLOTS entries, no atomic
-    uint32_t w_next = gw * (uint32_t)SLOTS, w_end = w_next + (uint32_t)SLOTS < n ? w_next + (uint32_t)SLOTS : n;
-    if (w_next >= n) { w_next = 0u; w_end = 0u; }
-    bool exhausted = false;
+    DealCursor wc(n, (uint32_t)SLOTS, fetch_chunk(n), kTraverseBlock / 64u);   // every wave starts on its own SLOTS entries, no atomic
     uint32_t st_nodes = 0u, st_tris = 0u;
     const bool two = lane < kHalf2;   // this lane looks after slot lane + 64 as well
     ST(13, lane) = (uint32_t)kLaneIdle; if (two) ST(13, lane + 64u) = (uint32_t)kLaneIdle;
@@ -325,7 +321,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_trace_pool(DeviceScene sc
         const bool n0 = c0 >= 0 && c0 < kLaneDone, n1 = c1 >= 0 && c1 < kLaneDone, l0 = c0 < 0, l1 = c1 < 0;
         const unsigned long long bn0 = __ballot(n0), bn1 = __ballot(n1), bl0 = __ballot(l0), bl1 = __ballot(l1);
         const uint32_t nn = (uint32_t)(__popcll(bn0) + __popcll(bn1)), nl = (uint32_t)(__popcll(bl0) + __popcll(bl1));
-        if ((!exhausted && (uint32_t)SLOTS - nn - nl >= fetch_at) || nn + nl == 0u) {
+        if ((!wc.exhausted && (uint32_t)SLOTS - nn - nl >= fetch_at) || nn + nl == 0u) {
             // ---- fetch step: retire finished slots, deal new rays to the idle ones (two passes of 64 slots)
 #pragma unroll 1
             for (uint32_t h = 0u; h < (SLOTS > 64 ? 2u : 1u); h++) {
@@ -337,21 +333,12 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_trace_pool(DeviceScene sc
                     (void)store_closest(a, tris, ST(15, s), bslot != 0xffffffffu, SF(9, s), SF(10, s), SF(11, s), bslot);
                     c = kLaneIdle; ST(13, s) = (uint32_t)kLaneIdle;
                 }
-                if (exhausted) continue;
-                if (w_next >= w_end) {
-                    if (n_static >= n) exhausted = true;
-                    else {
-                        uint32_t base = 0u;
-                        if (lane == 0u) base = atomicAdd(a.head, chunk);
-                        base = n_static + __builtin_amdgcn_readfirstlane(base);
-                        if (base >= n) exhausted = true;
-                        else { w_next = base; w_end = base + chunk < n ? base + chunk : n; }
-                    }
-                }
-                if (exhausted) continue;
+                if (wc.exhausted) continue;
+                wc.refill(a.head);
+                if (wc.exhausted) continue;
                 const unsigned long long m_idle = __ballot(c == kLaneIdle);
-                const uint32_t i = w_next + lanes_below(m_idle);
-                if (c == kLaneIdle && i < w_end) {
+                const uint32_t i = wc.index(m_idle);
+                if (c == kLaneIdle && i < wc.end) {
                     const uint32_t rid = a.order ? a.order[i] : i;
                     V3 o = xyz4(ld_stream(&a.ro[rid])), d = xyz4(ld_stream(&a.rd[rid]));
                     if (a.normalize_dir) d = vptfp::normalize(d);
@@ -359,11 +346,10 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_trace_pool(DeviceScene sc
                     SF(0, s) = o.x; SF(1, s) = o.y; SF(2, s) = o.z; SF(3, s) = d.x; SF(4, s) = d.y; SF(5, s) = d.z; SF(6, s) = inv.x; SF(7, s) = inv.y; SF(8, s) = inv.z;
                     SF(9, s) = a.tmax; ST(12, s) = 0xffffffffu; ST(13, s) = 0u; ST(14, s) = 0u; ST(15, s) = rid;
                 }
-                const uint32_t want = (uint32_t)__popcll(m_idle), left = w_end - w_next;
-                w_next += want < left ? want : left;
+                wc.advance(m_idle);
             }
             wave_lds_sync();
-            if (exhausted) {   // nothing came in: done when no slot is busy
+            if (wc.exhausted) {   // nothing came in: done when no slot is busy
                 const int d0 = (int)ST(13, lane), d1 = two ? (int)ST(13, lane + 64u) : kLaneIdle;
                 if (__ballot(d0 < kLaneDone) == 0ull && __ballot(d1 < kLaneDone) == 0ull) break;
             }
@@ -457,33 +443,20 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_trace_pair(DeviceScene sc
     const BvhTri* const tris = sc.tris;
     TreeTop top; top.lds = nullptr; top.count = 0;
     const uint32_t n = a.n_dev ? *a.n_dev : a.n;
-    const uint32_t chunk = fetch_chunk(n);
     const uint32_t fetch_at = (a.param & 0xffu) ? (a.param & 0xffu) : 48u;   // idle RAYS (of 128) that trigger a fetch step
-    const uint32_t n_static = gridDim.x * (kTraverseBlock / 64u) * 128u;     // every wave starts on its own 128 entries, no atomic
-    uint32_t w_next = __builtin_amdgcn_readfirstlane((blockIdx.x * (kTraverseBlock / 64u) + (threadIdx.x >> 6)) * 128u), w_end = w_next + 128u < n ? w_next + 128u : n;
-    if (w_next >= n) { w_next = 0u; w_end = 0u; }
-    bool exhausted = false;
+    DealCursor wc(n, 128u, fetch_chunk(n), kTraverseBlock / 64u);            // every wave starts on its own 128 entries, no atomic
     RayRegs r0, r1;
     r0.cur = kLaneIdle; r0.sp = 0; r0.rid = 0u; r0.bslot = 0xffffffffu; r0.bgid = 0xffffffffu; r0.o = vptfp::v3(0.0f, 0.0f, 0.0f); r0.d = r0.o; r0.inv = r0.o; r0.best_t = 0.0f; r0.bu = 0.0f; r0.bv = 0.0f;
     r1 = r0;
     uint32_t st_nodes = 0u, st_tris = 0u;
     auto retire_and_refill = [&](RayRegs& r) {   // every lane of the wave calls
         if (r.cur == kLaneDone) { (void)store_closest(a, tris, r.rid, r.bslot != 0xffffffffu, r.best_t, r.bu, r.bv, r.bslot); r.cur = kLaneIdle; }
-        if (exhausted) return;
-        if (w_next >= w_end) {
-            if (n_static >= n) exhausted = true;
-            else {
-                uint32_t base = 0u;
-                if (lane_id() == 0u) base = atomicAdd(a.head, chunk);
-                base = n_static + __builtin_amdgcn_readfirstlane(base);
-                if (base >= n) exhausted = true;
-                else { w_next = base; w_end = base + chunk < n ? base + chunk : n; }
-            }
-        }
-        if (exhausted) return;
+        if (wc.exhausted) return;
+        wc.refill(a.head);
+        if (wc.exhausted) return;
         const unsigned long long m_idle = __ballot(r.cur == kLaneIdle);
-        const uint32_t i = w_next + lanes_below(m_idle);
-        if (r.cur == kLaneIdle && i < w_end) {
+        const uint32_t i = wc.index(m_idle);
+        if (r.cur == kLaneIdle && i < wc.end) {
             r.rid = a.order ? a.order[i] : i;
             r.o = xyz4(ld_stream(&a.ro[r.rid]));
             r.d = xyz4(ld_stream(&a.rd[r.rid]));
@@ -491,17 +464,16 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_trace_pair(DeviceScene sc
             r.inv = safe_inverse(r.d);
             r.best_t = a.tmax; r.bslot = 0xffffffffu; r.bgid = 0xffffffffu; r.sp = 0; r.cur = 0;
         }
-        const uint32_t want = (uint32_t)__popcll(m_idle), left = w_end - w_next;
-        w_next += want < left ? want : left;
+        wc.advance(m_idle);
     };
     while (true) {
         const bool n0 = r0.cur >= 0 && r0.cur < kLaneDone, n1 = r1.cur >= 0 && r1.cur < kLaneDone, l0 = r0.cur < 0, l1 = r1.cur < 0;
         const uint32_t nn = (uint32_t)__popcll(__ballot(n0 | n1)), nl = (uint32_t)__popcll(__ballot(l0 | l1));
         const uint32_t busy = (uint32_t)(__popcll(__ballot(n0 | l0)) + __popcll(__ballot(n1 | l1)));
-        if ((!exhausted && 128u - busy >= fetch_at) || busy == 0u) {
+        if ((!wc.exhausted && 128u - busy >= fetch_at) || busy == 0u) {
             retire_and_refill(r0);
             retire_and_refill(r1);
-            if (exhausted && __ballot(r0.cur < kLaneDone) == 0ull && __ballot(r1.cur < kLaneDone) == 0ull) break;
+            if (wc.exhausted && __ballot(r0.cur < kLaneDone) == 0ull && __ballot(r1.cur < kLaneDone) == 0ull) break;
             continue;
         }
         const bool node_wins = 4u * nn > kVoteWeight4 * nl;
@@ -560,7 +532,7 @@ __global__ __launch_bounds__(kTraverseBlock, 8) void k_trace_shadow(DeviceScene 
     // RTCommon.slang:52-63 (USE_RAY_QUERIES: the direction as it is, [1e-4, 1e6]) or :64-84 (normalised direction, [1e-5, 1000]; sky rays only — light rays are not queued then, shade_core.hpp)
     const float tmin = ray_queries ? 0.0001f : 0.00001f, tmax = ray_queries ? 1000000.0f : 1000.0f;
     const uint32_t n_static = gridDim.x * (kTraverseBlock / 64u) * 64u;  // every wave starts on its own 64 entries, no atomic
-    // wave-uniform by construction (see k_trace_vote)
+    // wave_cursor.hpp DealCursor's statements, written out on local scalars, wave-uniform by construction (that header says why both)
     uint32_t w_next = __builtin_amdgcn_readfirstlane((blockIdx.x * (kTraverseBlock / 64u) + (threadIdx.x >> 6)) * 64u), w_end = w_next + 64u < n ? w_next + 64u : n;
     if (w_next >= n) { w_next = 0u; w_end = 0u; }
     bool exhausted = false;
@@ -570,7 +542,7 @@ __global__ __launch_bounds__(kTraverseBlock, 8) void k_trace_shadow(DeviceScene 
     V3 o = vptfp::v3(0.0f, 0.0f, 0.0f), d = o, inv = o;
     float tlim = tmax;
     uint32_t st_nodes = 0u, st_tris = 0u;
-    while (true) {   // fetch steps outside, node / triangle steps in the inner loop, one kind per iteration (kernels_trace.hip k_trace_vote)
+    while (true) {   // fetch steps outside, node / triangle steps in the inner loop, one kind per iteration (k_trace_vote above)
         while (true) {
             VPT_MARK("vote");
             const bool busy = cur < kLaneDone;
@@ -656,139 +628,126 @@ __global__ __launch_bounds__(kTraverseBlock, 8) void k_trace_shadow(DeviceScene 
 // pipeline always runs the compile-time vote parameters) and eight of k_trace_shadow.  Everything else — the baseline loop, the eight-wide
 // tree, culling, packed arithmetic, ray pools, ray pairs, the one-triangle step for the A/B, run-time vote parameters, any-hit k_trace_vote —
 // was measured slower (profiles/REJECTED.md) and lives in the LABORATORY build only (-DVPT_LAB=1: libvpt_hip_lab.so, include/vpt_lab.h, tests/tools/trace_lab.py).
-int trace_blocks_per_cu(uint32_t variant, bool any) {
-    int nb = 0;
+//
+// Every combination of switches in use, once, under a name.  k_trace_vote<ANY, COUNT, WIDE8, TUNED, STRICT, CULL, PK, TRI2, SPLIT4>:
+using TraceKernel = void (*)(DeviceScene, TraceArgs, Counters*);   // every kernel of this file that works through a closest-hit / any-hit ray stream
+// compile-time vote parameters; two triangles per triangle step unless visits are counted, so the visit statistics stay what a ray needs
+template <bool ANY, bool COUNT> constexpr TraceKernel kVoteProduct = k_trace_vote<ANY, COUNT, false, true, false, false, false, !COUNT>;
+// VPT_FLAG_LOCAL_HITS: the validating forms (one triangle per step)
+template <bool ANY, bool COUNT> constexpr TraceKernel kVoteValidating = k_trace_vote<ANY, COUNT, false, true, true>;
 #if VPT_LAB
-    if (variant == VPT_TRACE_PAIR) {
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_pair<false>, kTraverseBlock, kPairLdsBytes);
-        return nb > 0 ? nb : 1;
-    }
-    if (variant == VPT_TRACE_POOL) {   // (the 128-slot form: 3 blocks per CU; the launch scales the grid for the smaller pools)
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_pool<false, 128, 10, false>, kTraverseBlock, pool_lds_bytes(128, 10));
-        return nb > 0 ? nb : 1;
-    }
-    const size_t lds_lab = variant == VPT_TRACE_BASE ? kVoteStackBytes : kVoteLdsBytes;
-    if (variant == VPT_TRACE_BASE) {
-        if (any) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_base<true, false>, kTraverseBlock, lds_lab);
-        else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_base<false, false>, kTraverseBlock, lds_lab);
-        return nb > 0 ? nb : 1;
-    }
-    if (variant == VPT_TRACE_VOTE4S) {
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_vote<false, false, false, true, false, false, false, true, true>, kTraverseBlock, lds_lab);
-        return nb > 0 ? nb : 1;
-    }
-    if (variant == VPT_TRACE_VOTE8) {
-        if (any) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_vote<true, false, true, false>, kTraverseBlock, lds_lab);
-        else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_vote<false, false, true, false>, kTraverseBlock, lds_lab);
-        return nb > 0 ? nb : 1;
-    }
-    if (any) {
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_vote<true, false, false, true, false, false, false, true>, kTraverseBlock, lds_lab);
-        return nb > 0 ? nb : 1;
-    }
+template <bool ANY> constexpr TraceKernel kVoteOneTri = k_trace_vote<ANY, false, false, true, false, false, false, false>;   // round 3's step with the product vote parameters
+template <bool ANY, bool COUNT> constexpr TraceKernel kVotePacked = k_trace_vote<ANY, COUNT, false, true, false, false, true>;   // packed plane arithmetic in the node step
+template <bool COUNT, bool TUNED> constexpr TraceKernel kVoteCull = k_trace_vote<false, COUNT, false, TUNED, false, true>;      // stale-entry culling (closest hit only)
+template <bool ANY, bool COUNT> constexpr TraceKernel kVoteRuntime = k_trace_vote<ANY, COUNT, false, false>;                    // vote parameters from a.param
+template <bool ANY, bool COUNT> constexpr TraceKernel kVoteWide8 = k_trace_vote<ANY, COUNT, true, false>;                       // the eight-wide tree
+// the split-order tree: product vote parameters, two triangles per step, the counting form one (any-hit: the plain node step, its order tables masked off)
+template <bool ANY, bool COUNT> constexpr TraceKernel kVoteSplit4 = k_trace_vote<ANY, COUNT, false, true, false, false, false, !COUNT, true>;
 #endif
-    (void)variant; (void)any;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_vote<false, false, false, true, false, false, false, true>, kTraverseBlock, kVoteLdsBytes);
-    return nb > 0 ? nb : 1;
-}
+// k_trace_shadow<LIGHT, COUNT, TUNED, STRICT, TRI2>, the same three kinds
+using ShadowKernel = void (*)(DeviceScene, const float4*, const float4*, unsigned char*, const uint32_t*, uint32_t*, Counters*, uint32_t, uint32_t);
+template <bool LIGHT, bool COUNT> constexpr ShadowKernel kShadowProduct = k_trace_shadow<LIGHT, COUNT, true, false, !COUNT>;
+template <bool LIGHT, bool COUNT> constexpr ShadowKernel kShadowValidating = k_trace_shadow<LIGHT, COUNT, true, true, false>;
+#if VPT_LAB
+template <bool LIGHT, bool COUNT> constexpr ShadowKernel kShadowRuntime = k_trace_shadow<LIGHT, COUNT, false, false, false>;
+#endif
+// a name's form for the picks' run-time switches — the macros read the locals `count`, `any` and `light` of pick_trace / pick_trace_shadow and are
+// undefined behind them (each use instantiates both forms of every switch it takes)
+#define VPT_BY_COUNT(K, A) (count ? K<A, true> : K<A, false>)
+#define VPT_BY_ANY_COUNT(K) (any ? VPT_BY_COUNT(K, true) : VPT_BY_COUNT(K, false))
+#define VPT_BY_LIGHT_COUNT(K) (light ? VPT_BY_COUNT(K, true) : VPT_BY_COUNT(K, false))
 
-// every kernel of this file that works through a closest-hit / any-hit ray stream
-using TraceKernel = void (*)(DeviceScene, TraceArgs, Counters*);
-
-void launch_trace(hipStream_t s, uint32_t blocks, uint32_t variant, bool any, bool count, const DeviceScene& sc, const TraceArgs& a, Counters* ctr) {
-    TraceKernel k = nullptr;   // one launch site: a laboratory variant where the trace lab asks for one, else (still nullptr) the product's search
-    uint32_t grid = blocks;
-    size_t lds = kVoteLdsBytes;
+// THE pick: what launch_trace launches and what trace_blocks_per_cu sizes the grid for.  grid = blocks + blocks * extra_thirds / 3.
+struct TracePick { TraceKernel k; size_t lds; uint32_t extra_thirds; };
+static TracePick pick_trace(uint32_t variant, bool any, bool count, bool strict_hits, const TraceArgs& a) {
+    TracePick p = {nullptr, kVoteLdsBytes, 0u};
 #if VPT_LAB
     if (variant == VPT_TRACE_PAIR) {   // closest hit only
-        k = count ? k_trace_pair<true> : k_trace_pair<false>;
-        lds = kPairLdsBytes;
+        p.k = count ? k_trace_pair<true> : k_trace_pair<false>;
+        p.lds = kPairLdsBytes;
     } else if (variant == VPT_TRACE_POOL) {   // closest hit only (the lab refuses the any-hit form).  param bits 8-9: slots per wave / LDS stack entries 128/10, 96/10, 80/8, 64/8
         // (3, 4, 5, 6 blocks per CU: the grid — and with it the slot-indexed spill region — keeps blocks x slots constant); bit 10: DUAL
         const uint32_t cfg = (a.param >> 8) & 3u;
         const bool dual = ((a.param >> 10) & 1u) != 0u;
         if (cfg == 0u) {
-            k = dual ? (count ? k_trace_pool<true, 128, 10, true> : k_trace_pool<false, 128, 10, true>) : (count ? k_trace_pool<true, 128, 10, false> : k_trace_pool<false, 128, 10, false>);
-            lds = pool_lds_bytes(128, 10);
+            p.k = dual ? (count ? k_trace_pool<true, 128, 10, true> : k_trace_pool<false, 128, 10, true>) : (count ? k_trace_pool<true, 128, 10, false> : k_trace_pool<false, 128, 10, false>);
+            p.lds = pool_lds_bytes(128, 10);
         } else if (cfg == 1u) {
-            k = dual ? (count ? k_trace_pool<true, 96, 10, true> : k_trace_pool<false, 96, 10, true>) : (count ? k_trace_pool<true, 96, 10, false> : k_trace_pool<false, 96, 10, false>);
-            grid = blocks + blocks / 3u; lds = pool_lds_bytes(96, 10);
+            p.k = dual ? (count ? k_trace_pool<true, 96, 10, true> : k_trace_pool<false, 96, 10, true>) : (count ? k_trace_pool<true, 96, 10, false> : k_trace_pool<false, 96, 10, false>);
+            p.extra_thirds = 1u; p.lds = pool_lds_bytes(96, 10);
         } else if (cfg == 2u) {
-            k = dual ? (count ? k_trace_pool<true, 80, 8, true> : k_trace_pool<false, 80, 8, true>) : (count ? k_trace_pool<true, 80, 8, false> : k_trace_pool<false, 80, 8, false>);
-            grid = blocks + (blocks * 2u) / 3u; lds = pool_lds_bytes(80, 8);
+            p.k = dual ? (count ? k_trace_pool<true, 80, 8, true> : k_trace_pool<false, 80, 8, true>) : (count ? k_trace_pool<true, 80, 8, false> : k_trace_pool<false, 80, 8, false>);
+            p.extra_thirds = 2u; p.lds = pool_lds_bytes(80, 8);
         } else {
-            k = dual ? (count ? k_trace_pool<true, 64, 8, true> : k_trace_pool<false, 64, 8, true>) : (count ? k_trace_pool<true, 64, 8, false> : k_trace_pool<false, 64, 8, false>);
-            grid = blocks * 2u; lds = pool_lds_bytes(64, 8);
+            p.k = dual ? (count ? k_trace_pool<true, 64, 8, true> : k_trace_pool<false, 64, 8, true>) : (count ? k_trace_pool<true, 64, 8, false> : k_trace_pool<false, 64, 8, false>);
+            p.extra_thirds = 3u; p.lds = pool_lds_bytes(64, 8);
         }
-    } else if (variant == VPT_TRACE_VOTE4S) {   // product vote parameters, two triangles per step; the counting form one.  Any-hit: the plain node step on the split-order tree (its order tables masked off)
-        if (any) k = count ? k_trace_vote<true, true, false, true, false, false, false, false, true> : k_trace_vote<true, false, false, true, false, false, false, true, true>;
-        else k = count ? k_trace_vote<false, true, false, true, false, false, false, false, true> : k_trace_vote<false, false, false, true, false, false, false, true, true>;
+    } else if (variant == VPT_TRACE_VOTE4S) {
+        p.k = VPT_BY_ANY_COUNT(kVoteSplit4);
     } else if (variant == VPT_TRACE_BASE) {
-        if (any) k = count ? k_trace_base<true, true> : k_trace_base<true, false>;
-        else k = count ? k_trace_base<false, true> : k_trace_base<false, false>;
-        lds = kVoteStackBytes;
+        p.k = VPT_BY_ANY_COUNT(k_trace_base);
+        p.lds = kVoteStackBytes;
     } else if (variant == VPT_TRACE_VOTE8) {
-        if (any) k = count ? k_trace_vote<true, true, true, false> : k_trace_vote<true, false, true, false>;
-        else k = count ? k_trace_vote<false, true, true, false> : k_trace_vote<false, false, true, false>;
-    } else if (!sc.strict_hits) {
-        if (a.one_tri && !count) {   // trace lab bit 19: ONE triangle per triangle step (round 3's step) with the product vote parameters, for the A/B against the product's two
-            k = any ? k_trace_vote<true, false, false, true, false, false, false, false> : k_trace_vote<false, false, false, true, false, false, false, false>;
-        } else if (a.packed) {   // trace lab bit 18: packed plane arithmetic in the node step, product vote parameters
-            if (any) k = count ? k_trace_vote<true, true, false, true, false, false, true> : k_trace_vote<true, false, false, true, false, false, true>;
-            else k = count ? k_trace_vote<false, true, false, true, false, false, true> : k_trace_vote<false, false, false, true, false, false, true>;
-        } else if (a.cull && !any) {   // stale-entry culling (closest-hit only)
-            if (count) k = k_trace_vote<false, true, false, false, false, true>;
-            else k = a.param == kVoteParamDefault ? k_trace_vote<false, false, false, true, false, true> : k_trace_vote<false, false, false, false, false, true>;
-        } else if (a.param != kVoteParamDefault) {   // run-time vote parameters
-            if (any) k = count ? k_trace_vote<true, true, false, false> : k_trace_vote<true, false, false, false>;
-            else k = count ? k_trace_vote<false, true, false, false> : k_trace_vote<false, false, false, false>;
-        } else if (any) {   // (the pipeline's shadow rays go through k_trace_shadow: the any-hit form of k_trace_vote exists for the lab's ray sets)
-            k = count ? k_trace_vote<true, true, false, true> : k_trace_vote<true, false, false, true, false, false, false, true>;
-        }
+        p.k = VPT_BY_ANY_COUNT(kVoteWide8);
+    } else if (!strict_hits) {
+        if (a.one_tri && !count) p.k = any ? kVoteOneTri<true> : kVoteOneTri<false>;   // trace lab bit 19, for the A/B against the product's two
+        else if (a.packed) p.k = VPT_BY_ANY_COUNT(kVotePacked);   // trace lab bit 18
+        else if (a.cull && !any) {
+            if (count) p.k = kVoteCull<true, false>;
+            else p.k = a.param == kVoteParamDefault ? kVoteCull<false, true> : kVoteCull<false, false>;
+        } else if (a.param != kVoteParamDefault) p.k = VPT_BY_ANY_COUNT(kVoteRuntime);
+        else if (any) p.k = VPT_BY_COUNT(kVoteProduct, true);   // (the pipeline's shadow rays go through k_trace_shadow: the any-hit form of k_trace_vote exists for the lab's ray sets)
     } else if (any) {
-        k = count ? k_trace_vote<true, true, false, true, true> : k_trace_vote<true, false, false, true, true>;
+        p.k = VPT_BY_COUNT(kVoteValidating, true);
     }
 #endif
-    (void)variant; (void)any;
-    if (!k) {   // ---- the product's closest-hit search: compile-time vote parameters; two triangles per triangle step unless visits are counted or hits validated
-        if (sc.strict_hits) k = count ? k_trace_vote<false, true, false, true, true> : k_trace_vote<false, false, false, true, true>;   // VPT_FLAG_LOCAL_HITS: the validating instantiations
-        else k = count ? k_trace_vote<false, true, false, true> : k_trace_vote<false, false, false, true, false, false, false, true>;
-    }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kTraverseBlock), lds, s, sc, a, ctr);
+    (void)variant; (void)any; (void)a;
+    if (!p.k) p.k = strict_hits ? VPT_BY_COUNT(kVoteValidating, false) : VPT_BY_COUNT(kVoteProduct, false);   // ---- the product's closest-hit search
+    return p;
+}
+static ShadowKernel pick_trace_shadow(bool light, bool count, bool strict_hits, uint32_t param) {
+#if VPT_LAB
+    if (param != kVoteParamDefault && !strict_hits) return VPT_BY_LIGHT_COUNT(kShadowRuntime);   // run-time vote parameters (trace-lab sweeps through the pipeline)
+#endif
+    (void)param;
+    // (VPT_FLAG_LOCAL_HITS with vpt_config.count_traversal runs the counting + validating one, so the visit statistics are not silently zero)
+    return strict_hits ? VPT_BY_LIGHT_COUNT(kShadowValidating) : VPT_BY_LIGHT_COUNT(kShadowProduct);
+}
+#undef VPT_BY_LIGHT_COUNT
+#undef VPT_BY_ANY_COUNT
+#undef VPT_BY_COUNT
+static int blocks_per_cu(const void* k, size_t lds) {
+    int nb = 0;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kTraverseBlock, lds);
+    return nb;
+}
+
+void launch_trace(hipStream_t s, uint32_t blocks, uint32_t variant, bool any, bool count, const DeviceScene& sc, const TraceArgs& a, Counters* ctr) {
+    const TracePick p = pick_trace(variant, any, count, sc.strict_hits != 0u, a);
+    hipLaunchKernelGGL(p.k, dim3(blocks + blocks * p.extra_thirds / 3u), dim3(kTraverseBlock), p.lds, s, sc, a, ctr);
+}
+// The non-counting form of what launch_trace picks for default arguments — with two answers kept as they were before there was one pick: the
+// non-validating kernel whatever the scene's strict_hits (the caller has no scene), and for VPT_TRACE_VOTE4S the closest-hit kernel whatever `any`.
+int trace_blocks_per_cu(uint32_t variant, bool any) {
+    TraceArgs plain = {};
+    plain.param = variant == VPT_TRACE_POOL ? 0u : kVoteParamDefault;   // the pool's own default (bits 8-10 clear: the 128-slot form, 3 blocks per CU; the launch scales the grid for the smaller pools); the vote variants': off the run-time-parameter kernels
+    const TracePick p = pick_trace(variant, any && variant != VPT_TRACE_VOTE4S, false, false, plain);
+    const int nb = blocks_per_cu(reinterpret_cast<const void*>(p.k), p.lds);
+    return nb > 0 ? nb : 1;
 }
 
 void launch_trace_shadow(hipStream_t s, uint32_t blocks, bool light, bool count, const DeviceScene& sc, const StreamState& ss, Counters* ctr,
                          StreamCounters* sctr, uint32_t param, uint32_t ray_queries) {
-    const size_t lds = kVoteLdsBytes;
-    const dim3 g(blocks), b(kTraverseBlock);
     const float4 *RO = light ? ss.LTO : ss.SKO, *RD = light ? ss.LTD : ss.SKD;
     unsigned char* vis = light ? ss.vis_light : ss.vis_sky;
     uint32_t *len = light ? &sctr->light_len.v : &sctr->sky_len.v, *head = light ? &sctr->light_head.v : &sctr->sky_head.v;
-    void (*k)(DeviceScene, const float4*, const float4*, unsigned char*, const uint32_t*, uint32_t*, Counters*, uint32_t, uint32_t);
-#if VPT_LAB
-    if (param != kVoteParamDefault && !sc.strict_hits) {   // run-time vote parameters (trace-lab sweeps through the pipeline)
-        if (light) k = count ? k_trace_shadow<true, true, false, false, false> : k_trace_shadow<true, false, false, false, false>;
-        else k = count ? k_trace_shadow<false, true, false, false, false> : k_trace_shadow<false, false, false, false, false>;
-    } else
-#endif
-    // the product instantiations: compile-time vote parameters; two triangles per triangle step unless visits are counted or hits validated
-    // (VPT_FLAG_LOCAL_HITS with vpt_config.count_traversal runs the counting + validating one, so the visit statistics are not silently zero)
-    if (sc.strict_hits) {
-        if (light) k = count ? k_trace_shadow<true, true, true, true, false> : k_trace_shadow<true, false, true, true, false>;
-        else k = count ? k_trace_shadow<false, true, true, true, false> : k_trace_shadow<false, false, true, true, false>;
-    } else if (count) {
-        k = light ? k_trace_shadow<true, true, true, false, false> : k_trace_shadow<false, true, true, false, false>;
-    } else {
-        k = light ? k_trace_shadow<true, false, true, false, true> : k_trace_shadow<false, false, true, false, true>;
-    }
-    hipLaunchKernelGGL(k, g, b, lds, s, sc, RO, RD, vis, len, head, ctr, param, ray_queries);
+    hipLaunchKernelGGL(pick_trace_shadow(light, count, sc.strict_hits != 0u, param), dim3(blocks), dim3(kTraverseBlock), kVoteLdsBytes, s, sc, RO, RD, vis, len, head, ctr, param, ray_queries);
 }
+// one grid size serves both queues: the smaller answer of the two product forms (non-counting, non-validating, as above)
 int trace_shadow_blocks_per_cu() {
-    int a = 0, b = 0;
-    const size_t lds = kVoteLdsBytes;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_trace_shadow<true, false, true, false, true>, kTraverseBlock, lds);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<false, false, true, false, true>, kTraverseBlock, lds);
-    int nb = a < b ? a : b;
+    const int a = blocks_per_cu(reinterpret_cast<const void*>(pick_trace_shadow(true, false, false, kVoteParamDefault)), kVoteLdsBytes);
+    const int b = blocks_per_cu(reinterpret_cast<const void*>(pick_trace_shadow(false, false, false, kVoteParamDefault)), kVoteLdsBytes);
+    const int nb = a < b ? a : b;
     return nb > 0 ? nb : 1;
 }
 

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kTraverseBlock, 3) void k_whole(WholeLaunch wl) {  
     __shared__ float f_ox[kWaves][refill::kTile], f_oy[kWaves][refill::kTile], f_oz[kWaves][refill::kTile];
     __shared__ float f_dx[kWaves][refill::kTile], f_dy[kWaves][refill::kTile], f_dz[kWaves][refill::kTile];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (uniform: the rings' and the buffer's rows are addressed from a scalar base)
-    // tile cursor and fresh-ray buffer, wave-uniform by construction (kernels_trace.hip k_trace_vote)
+    // tile cursor and fresh-ray buffer, wave-uniform by construction (wave_cursor.hpp DealCursor)
     const refill::Shape shape{a.n_slots, gridDim.x * kWaves, a.static_rounds, a.chunk_tiles};
     refill::Cursor cur = refill::make_cursor(shape, blockIdx.x * kWaves + wave);
     refill::Fresh fresh = refill::make_fresh();

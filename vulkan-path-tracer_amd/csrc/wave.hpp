@@ -1,5 +1,5 @@
-// wave.hpp — wave64 building blocks shared by the stage kernels: lane id, ballot prefix, one-atomic-per-wave append,
-// and the persistent work-fetch chunk size.
+// wave.hpp — wave64 building blocks shared by the stage kernels: lane id, ballot prefix, one-atomic-per-wave append, stream loads and
+// stores.  (How a persistent wave takes its work, and the work-fetch chunk size: wave_cursor.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,14 +26,6 @@ __device__ inline uint32_t wave_append(bool pred, uint32_t* counter) {
         base = __shfl(base, (int)leader);
     }
     return base + lanes_below(mask);
-}
-
-// One atomic on a single word costs ~11 ns under contention (MI355X_MICROARCH.md 'dequeue': a head word
-// saturates at ~88 dequeues/us), so the number of fetches per launch is kept near 8k: a wave takes
-// n/8192 queue entries per fetch, rounded up to whole waves, between 64 and 1024.
-__device__ inline uint32_t fetch_chunk(uint32_t n) {
-    uint32_t c = ((n >> 13) + 63u) & ~63u;
-    return c < 64u ? 64u : (c > 1024u ? 1024u : c);
 }
 
 // Stream records are written once and read once, a bounce later: stores and loads that bypass cache retention leave L2 to the
