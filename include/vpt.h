@@ -742,6 +742,39 @@ int vpt_get_svgf_options(const vpt_ctx* ctx, vpt_svgf_options* out);
 int vpt_get_temporal_variance(vpt_ctx* ctx, float* var_host);   /* width*height floats */
 int vpt_get_temporal_moments(vpt_ctx* ctx, float* mu_host);     /* width*height*2 floats: mu1, mu2 per pixel */
 
+/* ---- SVGF: the variance of young pixels from their neighbourhood ------------------------------------------------------------------------
+ * The variance image above is -1 wherever a hit pixel's new history length is below min_history * m — such a pixel is YOUNG: every pixel of the
+ * first min_history images after a reset or a scene edit, and the band a moving camera or a moved instance uncovers, every frame — and vpt_denoise*
+ * filters those with the fixed-sigma_color rule.  SVGF (Schied et al. 2017, §4.2) estimates their variance spatially instead.
+ * vpt_set_svgf_spatial_options: context state, like vpt_set_svgf_options; the call only validates and stores, and does NOT drop the temporal
+ *                     history (it touches no record).  With vpt_svgf_options.variance == 0 it is stored and ignored.  With mode == 0 (default)
+ *                     every call returns the bits it returned without these options, and nothing more is launched.  With mode == 1 and variance == 1:
+ *   vpt_temporal_accumulate*  runs one more launch behind the temporal one, on the same stream.  Per young pixel p, over the (2 radius + 1)^2 window
+ *                     around it, rows then columns: a tap q outside the image or on a miss is skipped; the centre has weight 1; any other tap, at
+ *                     ring r = max(|dx|, |dy|), has w = exp(-(dn + dz)) with dn = max(0, 1 - dot(n_p, n_q)) / sigma_normal and dz = |t_p - t_q| /
+ *                     (sigma_depth r max(t_p, 1e-6)).  sw = sum w, M1 = sum w mu1_q / sw, M2 = sum w mu2_q / sw over the moments the call has just
+ *                     written.  The pixel's variance becomes max(0, M2 - M1 M1) where sw >= min_weight and stays -1 where it is not (too little of
+ *                     the window is this surface).  The instance id is not tested, and there is no history-length boost: long-lived neighbours
+ *                     bring their temporal moments, history-less ones (l, l l), and both estimate the per-call variance the temporal one estimates.
+ *                     The arithmetic is csrc/svgf_spatial.hpp's spatial_variance_pixel.
+ *   what survives     everything but the variance image at young pixels: image, record, moments, history length, motion image and the variance of
+ *                     every other pixel (misses: 0) keep their bits.  The variance image is not history: nothing feeds back into the next call.
+ *   vpt_denoise*      is unchanged: a young pixel now enters the passes with a variance >= 0 and takes the variance-guided rule.
+ *   memory            none.
+ *   errors            VPT_ERR_INVALID_ARGUMENT for a NULL argument, mode > 1, a radius outside 1..3, a sigma that is not finite or not > 0, a
+ *                     min_weight that is not finite or below 1, a non-zero reserved word.  A refused call changes nothing. */
+typedef struct vpt_svgf_spatial_options {
+    uint32_t mode;         /* 0 (default): off — every call returns the bits it returned before, nothing more is launched.  1: on */
+    uint32_t radius;       /* 1..3; default 3 (7 x 7) */
+    float    sigma_normal; /* default 0.1; > 0 */
+    float    sigma_depth;  /* default 0.05; > 0 */
+    float    min_weight;   /* least sum of tap weights that is an estimate; default 4; >= 1 */
+    uint32_t reserved[3];  /* 0 */
+} vpt_svgf_spatial_options;
+void vpt_default_svgf_spatial_options(vpt_svgf_spatial_options* out);   /* mode 0, radius 3, sigma_normal 0.1, sigma_depth 0.05, min_weight 4 */
+int vpt_set_svgf_spatial_options(vpt_ctx* ctx, const vpt_svgf_spatial_options* options);
+int vpt_get_svgf_spatial_options(const vpt_ctx* ctx, vpt_svgf_spatial_options* out);
+
 /* ---- the temporal history across instance moves -------------------------------------------------------------------------------------
  * The loop of an animated viewport:
  *     vpt_set_instance_transforms -> vpt_set_base_seed(frame_index) -> vpt_render(k) -> vpt_temporal_accumulate -> vpt_denoise -> vpt_postprocess

@@ -16,6 +16,7 @@ from ._abi import FEATURES_CENTER, FEATURES_SAMPLE  # noqa: F401
 from ._abi import default_denoise_params, DENOISE_DEMODULATE, DENOISE_MAX_ITERATIONS, POST_SOURCE_RADIANCE, POST_SOURCE_DENOISED  # noqa: F401
 from ._abi import default_temporal_params, TEMPORAL_DEMODULATE, TEMPORAL_MATCH_INSTANCE, DENOISE_SOURCE_RADIANCE, DENOISE_SOURCE_TEMPORAL  # noqa: F401
 from ._abi import SvgfOptions, default_svgf_options  # noqa: F401
+from ._abi import SvgfSpatialOptions, default_svgf_spatial_options  # noqa: F401
 from ._abi import TemporalOptions, default_temporal_options  # noqa: F401
 from ._abi import ExposureOptions, ExposureState, default_exposure_options, EXPOSURE_BINS  # noqa: F401
 
@@ -422,6 +423,22 @@ class PathTracer:
         """vpt_get_svgf_options -> SvgfOptions."""
         o = _abi.SvgfOptions()
         _check(self.lib, self.ctx, self.lib.vpt_get_svgf_options(self.ctx, C.byref(o)), "vpt_get_svgf_options")
+        return o
+
+    def set_svgf_spatial_options(self, **kw):
+        """vpt_set_svgf_spatial_options: the context's options with the fields given replaced (mode, radius, sigma_normal, sigma_depth, min_weight).  With
+        mode = 1 and svgf variance = 1, temporal_accumulate gives a young pixel (variance -1) the variance of its neighbourhood's moments.  Keeps the history."""
+        o = self.svgf_spatial_options()
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        _check(self.lib, self.ctx, self.lib.vpt_set_svgf_spatial_options(self.ctx, C.byref(o)), "vpt_set_svgf_spatial_options")
+
+    def svgf_spatial_options(self):
+        """vpt_get_svgf_spatial_options -> SvgfSpatialOptions."""
+        o = _abi.SvgfSpatialOptions()
+        _check(self.lib, self.ctx, self.lib.vpt_get_svgf_spatial_options(self.ctx, C.byref(o)), "vpt_get_svgf_spatial_options")
         return o
 
     def temporal_variance(self):

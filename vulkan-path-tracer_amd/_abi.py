@@ -266,6 +266,21 @@ def default_svgf_options(**kw):
     return p
 
 
+class SvgfSpatialOptions(C.Structure):  # vpt_svgf_spatial_options
+    _fields_ = [("mode", C.c_uint32), ("radius", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("min_weight", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
+def default_svgf_spatial_options(**kw):
+    """vpt_default_svgf_spatial_options: mode off, radius 3 (7 x 7), sigma_normal 0.1, sigma_depth 0.05, min_weight 4."""
+    p = SvgfSpatialOptions(0, 3, 0.1, 0.05, 4.0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 class TemporalOptions(C.Structure):  # vpt_temporal_options
     _fields_ = [("instance_motion", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
@@ -370,6 +385,9 @@ PROTOTYPES = {
     "vpt_default_svgf_options": (None, [C.POINTER(SvgfOptions)]),
     "vpt_set_svgf_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfOptions)]),
     "vpt_get_svgf_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfOptions)]),
+    "vpt_default_svgf_spatial_options": (None, [C.POINTER(SvgfSpatialOptions)]),
+    "vpt_set_svgf_spatial_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfSpatialOptions)]),
+    "vpt_get_svgf_spatial_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfSpatialOptions)]),
     "vpt_get_temporal_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_get_temporal_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_default_temporal_options": (None, [C.POINTER(TemporalOptions)]),

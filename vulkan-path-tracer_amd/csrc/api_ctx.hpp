@@ -246,6 +246,8 @@ struct vpt_ctx {
     float* sv_block = nullptr;       // one allocation: moments[0] | moments[1] (mu1, mu2 per pixel, swapped with the records) | variance
     float *sv_moments[2] = {nullptr, nullptr}, *sv_variance = nullptr;
     bool sv_valid = false;           // the latest temporal result was made with the option on: moments tp_latest and the variance image go with it
+    // ... and its spatial estimate for young pixels (vpt_set_svgf_spatial_options): state only, no memory; ignored while svgf.variance is 0
+    vpt_svgf_spatial_options sv_spatial{0u, 3u, 0.1f, 0.05f, 4.0f, {0u, 0u, 0u}};
     // moved instances (vpt_set_temporal_options): nothing of this is allocated, kept or uploaded while instance_motion is 0
     vpt_temporal_options tp_options{0u, {0u, 0u, 0u}};
     temporal::MotionSnapshot tp_snapshot;   // the matrices, at the latest record, of the instances moved since: only while a history is there to carry

@@ -240,6 +240,9 @@ int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
     launch_temporal(c->main.stream, whole_image(c), c->tp_depth, c->tp_albedo, c->tp_ids, c->tp_hist[prev], c->tp_guide[prev], c->tp_inst[prev],
                     c->tp_hist[next], c->tp_guide[next], c->tp_inst[next], c->tp_out, f, variance ? c->sv_moments[prev] : nullptr, variance ? c->sv_moments[next] : nullptr,
                     variance ? c->sv_variance : nullptr, (float)c->svgf.min_history * f.m, motion_table, (uint32_t)c->instances.size(), motion ? c->tp_motion : nullptr);
+    if (variance && c->sv_spatial.mode)   // the young pixels' variance from their neighbourhood, on the record just written: the variance image alone changes
+        launch_variance_spatial(c->main.stream, c->tp_guide[next], c->sv_moments[next], c->tp_hist[next], c->sv_variance, W, H,
+                                svgf_spatial::plan_of(c->sv_spatial.radius, c->sv_spatial.sigma_normal, c->sv_spatial.sigma_depth, c->sv_spatial.min_weight), (float)c->svgf.min_history * f.m);
     c->tp_camera = temporal::prev_camera_of(c->P.view_inv, c->P.proj_inv);
     c->tp_snapshot.clear();   // the new record was made with the matrices the instances have now
     c->tp_latest = next; c->tp_valid = true; c->tp_history = true; c->sv_valid = variance; c->tp_motion_valid = motion;
@@ -346,6 +349,24 @@ int vpt_set_svgf_options(vpt_ctx* c, const vpt_svgf_options* o) {
 int vpt_get_svgf_options(const vpt_ctx* c, vpt_svgf_options* o) {
     if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
     *o = c->svgf;
+    return VPT_OK;
+}
+// ---- ... and the spatial estimate for young pixels: validated and stored; enqueue_temporal acts on it.  No record is touched, so the history stays.
+void vpt_default_svgf_spatial_options(vpt_svgf_spatial_options* o) {
+    if (o) *o = vpt_svgf_spatial_options{0u, 3u, 0.1f, 0.05f, 4.0f, {0u, 0u, 0u}};
+}
+int vpt_set_svgf_spatial_options(vpt_ctx* c, const vpt_svgf_spatial_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    const float big = 3.402823466e+38f;   // (FLT_MAX.  x <= big: finite; a NaN fails every comparison)
+    if (o->mode > 1u || o->radius - 1u >= (uint32_t)svgf_spatial::kMaxRadius || !(o->sigma_normal > 0.0f && o->sigma_normal <= big) || !(o->sigma_depth > 0.0f && o->sigma_depth <= big) ||
+        !(o->min_weight >= 1.0f && o->min_weight <= big) || (o->reserved[0] | o->reserved[1] | o->reserved[2]))
+        return fail(c, VPT_ERR_INVALID_ARGUMENT, "svgf spatial options: mode 0 or 1, radius 1..3, finite sigmas > 0, finite min_weight >= 1, reserved words 0");
+    c->sv_spatial = *o;
+    return VPT_OK;
+}
+int vpt_get_svgf_spatial_options(const vpt_ctx* c, vpt_svgf_spatial_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    *o = c->sv_spatial;
     return VPT_OK;
 }
 int vpt_get_temporal_variance(vpt_ctx* c, float* var_host) { return read_variance_result(c, var_host, false); }

@@ -4,6 +4,7 @@
 #include "device_types.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
+#include "svgf_spatial.hpp"
 #include "exposure.hpp"
 #include "post_plan.hpp"
 #include "whole_deal.hpp"   // + camera_cull.hpp
@@ -174,5 +175,9 @@ void launch_denoise_atrous(hipStream_t s, const float* in, const float* guide, c
 void launch_temporal(hipStream_t s, const float* cur, const float* depth, const float* albedo, const uint32_t* ids, const float* prev_hist, const float* prev_guide, const uint32_t* prev_inst,
                      float* hist, float* guide, uint32_t* inst, float* out, const temporal::Frame& f, const float* prev_moments, float* moments, float* variance, float min_len,
                      const temporal::InstanceMotion* motion_table, uint32_t motion_count, float* motion);
+// vpt_svgf_spatial_options (svgf_spatial.hpp holds the arithmetic): one launch over w x h behind launch_temporal, on the record it has just written — guide
+// (packed F4), moments (two floats) and hist (F4, whose .w is the length) per pixel.  `variance` is rewritten in place at the young hit pixels (length below
+// min_len) and nowhere else; a block whose 64 x 4 tile holds none returns before it reads a neighbour.
+void launch_variance_spatial(hipStream_t s, const float* guide, const float* moments, const float* hist, float* variance, uint32_t w, uint32_t h, const svgf_spatial::Plan& plan, float min_len);
 
 }  // namespace vpt

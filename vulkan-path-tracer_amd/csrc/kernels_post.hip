@@ -687,6 +687,56 @@ void launch_temporal(hipStream_t s, const float* cur, const float* depth, const 
                        reinterpret_cast<const uint4*>(ids), rec, reinterpret_cast<dn::F4*>(out), f, min_len);
 }
 
+// ---- vpt_svgf_spatial_options (api_post.hip enqueue_temporal, behind k_temporal): svgf_spatial.hpp's spatial_variance_pixel does all the arithmetic; the
+// kernel only decides where a value is read from, so the device gives the bits of the host compile (tests/test_gpu_svgf_spatial.py).  The 64 x 4 tile, a wave
+// per row.  After the first images of a moving viewport the young pixels are a thin band, so a block first asks whether its tile holds any: every thread —
+// those outside the image too — brings its own pixel's answer to ONE block-wide OR (a barrier all 256 threads reach), and a block without a young hit pixel
+// returns there, having read 20 B per pixel and no neighbour.  Only a block with one stages its tile plus a halo of `radius` pixels in LDS — at most 70 x 10
+// entries of 24 B = 16.8 KB — and its young threads run the window from there; no thread leaves before the second barrier.
+// 64 x 4 and not 32 x 8 (halo read amplification 2.7 against 2.1 at radius 3, which only the staging blocks pay): a wave's row stays one coalesced 1 KB
+// request of the guide, as everywhere in this file, and for the early-out neither shape wins — the band a yaw uncovers is upright (32 x 8 would stage half as
+// many pixels for it), the band a pitch uncovers lies flat (64 x 4 stages half as many).  No bit depends on the choice.
+// LDS banks: guide and moments are two arrays, not one of 24-byte entries (which are not 16-byte aligned: no ds_read_b128 at all).  A wave reads 64
+// CONSECUTIVE entries of a tile row for every tap — the tap offset is the same for all lanes.  The guide's ds_read_b128 is served in four groups of 16 lanes,
+// bank = dword address mod 64: each group's lanes cover 16 distinct 16-byte slots mod 256 B whatever the row pitch (k_denoise_atrous's argument).  The
+// moments' ds_read_b64 is served in two halves of 32 lanes: 32 consecutive 8-byte entries are the 64 banks, each once.  No padding is needed and none is there.
+constexpr int kSvTW = kTileW + 2 * svgf_spatial::kMaxRadius, kSvTH = kTileH + 2 * svgf_spatial::kMaxRadius;   // 70 x 10
+struct SvTileSrc {
+    const dn::F4 (&g)[kSvTW * kSvTH]; const temporal::M2 (&m)[kSvTW * kSvTH]; int ox, oy;   // image position of tile entry (0, 0)
+    __device__ __forceinline__ dn::F4 guide(int x, int y) const { return g[(y - oy) * kSvTW + (x - ox)]; }
+    __device__ __forceinline__ temporal::M2 moments(int x, int y) const { return m[(y - oy) * kSvTW + (x - ox)]; }
+};
+__global__ __launch_bounds__(256) void k_variance_spatial(const dn::F4* guide, const temporal::M2* moments, const dn::F4* hist, float* variance, int w, int h, svgf_spatial::Plan plan, float min_len) {
+    __shared__ dn::F4 s_g[kSvTW * kSvTH];
+    __shared__ temporal::M2 s_m[kSvTW * kSvTH];
+    const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
+    const int x = x0 + (int)(threadIdx.x & 63u), y = y0 + (int)(threadIdx.x >> 6);
+    const bool inside = x < w && y < h;
+    const size_t p = inside ? (size_t)y * w + x : 0;
+    dn::F4 gp = dn::f4(0.0f, 0.0f, 0.0f, -1.0f);
+    float len_p = 0.0f;
+    if (inside) { gp = guide[p]; len_p = hist[p].w; }
+    const bool young = inside && dn::is_hit(gp) && !(len_p >= min_len);   // spatial_variance_pixel's own test: everyone else keeps v_in, which is already there
+    if (!__syncthreads_or(young ? 1 : 0)) return;                        // (block-uniform: all threads leave, or none)
+    const int halo = plan.radius;   // <= kMaxRadius (the host's check)
+    const int tw = kTileW + 2 * halo, th = kTileH + 2 * halo;
+    for (int i = threadIdx.x; i < tw * th; i += 256) {
+        const int ty = i / tw, tx = i - ty * tw;
+        const int gx = x0 - halo + tx, gy = y0 - halo + ty;
+        if (gx < 0 || gx >= w || gy < 0 || gy >= h) continue;   // never read: spatial_variance_pixel skips taps outside the image
+        s_g[ty * kSvTW + tx] = guide[(size_t)gy * w + gx];
+        s_m[ty * kSvTW + tx] = moments[(size_t)gy * w + gx];
+    }
+    __syncthreads();
+    if (!young) return;
+    const SvTileSrc src{s_g, s_m, x0 - halo, y0 - halo};
+    variance[p] = svgf_spatial::spatial_variance_pixel(src, x, y, w, h, plan, len_p, min_len, gp, variance[p]);
+}
+void launch_variance_spatial(hipStream_t s, const float* guide, const float* moments, const float* hist, float* variance, uint32_t w, uint32_t h, const svgf_spatial::Plan& plan, float min_len) {
+    hipLaunchKernelGGL(k_variance_spatial, dim3(cdiv_(w, kTileW), cdiv_(h, kTileH)), dim3(256), 0, s, reinterpret_cast<const dn::F4*>(guide), reinterpret_cast<const temporal::M2*>(moments),
+                       reinterpret_cast<const dn::F4*>(hist), variance, (int)w, (int)h, plan, min_len);
+}
+
 void launch_bloom_threshold(hipStream_t s, const float* in, float* out, uint32_t w, uint32_t h, float threshold, float falloff) {
     uint32_t n = w * h;
     hipLaunchKernelGGL(k_bloom_threshold, dim3(cdiv_(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(in), reinterpret_cast<float4*>(out), n, threshold, falloff);

@@ -318,6 +318,10 @@ void PathTracer::SetSvgfOptions(const vpt_svgf_options& options) {
     if (!m_Ctx) throw std::runtime_error("SetSvgfOptions before SetScene");
     Check(vpt_set_svgf_options(m_Ctx, &options), "vpt_set_svgf_options");
 }
+void PathTracer::SetSvgfSpatialOptions(const vpt_svgf_spatial_options& options) {
+    if (!m_Ctx) throw std::runtime_error("SetSvgfSpatialOptions before SetScene");
+    Check(vpt_set_svgf_spatial_options(m_Ctx, &options), "vpt_set_svgf_spatial_options");
+}
 void PathTracer::SetTemporalOptions(const vpt_temporal_options& options) {
     if (!m_Ctx) throw std::runtime_error("SetTemporalOptions before SetScene");
     Check(vpt_set_temporal_options(m_Ctx, &options), "vpt_set_temporal_options");

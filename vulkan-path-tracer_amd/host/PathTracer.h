@@ -212,6 +212,9 @@ public:
     // EXTENSION: SVGF's luminance variance and the variance-guided a-trous passes (vpt_set_svgf_options); context state, so after SetScene like SetPostSource.
     static vpt_svgf_options DefaultSvgfOptions() { vpt_svgf_options o; vpt_default_svgf_options(&o); return o; }
     void SetSvgfOptions(const vpt_svgf_options& options);
+    // EXTENSION: SVGF's spatial variance estimate for pixels whose history is too short (vpt_set_svgf_spatial_options); keeps the temporal history.
+    static vpt_svgf_spatial_options DefaultSvgfSpatialOptions() { vpt_svgf_spatial_options o; vpt_default_svgf_spatial_options(&o); return o; }
+    void SetSvgfSpatialOptions(const vpt_svgf_spatial_options& options);
     // EXTENSION: the temporal history carried across instance moves (vpt_set_temporal_options); context state, so after SetScene like SetSvgfOptions.
     // GetTemporalMotion: width*height*2 floats of the latest TemporalAccumulate made with instance_motion == 1.
     static vpt_temporal_options DefaultTemporalOptions() { vpt_temporal_options o; vpt_default_temporal_options(&o); return o; }
