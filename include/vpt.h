@@ -775,6 +775,57 @@ void vpt_default_svgf_spatial_options(vpt_svgf_spatial_options* out);   /* mode 
 int vpt_set_svgf_spatial_options(vpt_ctx* ctx, const vpt_svgf_spatial_options* options);
 int vpt_get_svgf_spatial_options(const vpt_ctx* ctx, vpt_svgf_spatial_options* out);
 
+/* ---- outlier ("firefly") rejection ahead of the two filters -------------------------------------------------------------------------------
+ * One 1-spp spike on a dark wall enters the temporal history and stays for max_history images, inflates its own second moment so that the
+ * variance-guided rule widens around it, is spread into a 5 x 5 blot by every a-trous pass and drags the exposure histogram's top bin.  The
+ * integrator's max_luminance clamp is global: a pixel at 400 on a wall whose neighbours sit at 0.3 passes it untouched.
+ * vpt_set_firefly_options: context state, like vpt_set_svgf_spatial_options; the call only validates and stores, and does NOT drop the temporal
+ *                     history (it touches no record).  With mode == 0 (default) every call returns the bits it returned without these options and
+ *                     nothing is allocated or launched.  With mode == 1 one image pass runs ahead of the filter and the filter reads ITS output:
+ *   vpt_temporal_accumulate*  between the first-hit guides and the temporal launch, on the accumulation image; demodulate = VPT_TEMPORAL_DEMODULATE.
+ *   vpt_denoise*      from VPT_DENOISE_SOURCE_RADIANCE with iterations > 0 only, between the guides and the prepare pass; demodulate =
+ *                     VPT_DENOISE_DEMODULATE.  From VPT_DENOISE_SOURCE_TEMPORAL the filter has already run ahead of the history and is not run
+ *                     again; iterations == 0 stays a copy of the unfiltered source; vpt_postprocess* from VPT_POST_SOURCE_RADIANCE is untouched.
+ *   the rule          l(q) = luminance (0.2126, 0.7152, 0.0722) of the pixel as the filter sees it: c.rgb / max(albedo, 1e-3) when the call
+ *                     demodulates, c.rgb otherwise.  A miss keeps its bits and is never a tap.  A hit pixel p looks at the (2 radius + 1)^2 window
+ *                     without its centre: a tap counts when it is inside the image, a hit and l_q >= 0 (a NaN is no tap, +inf is one); n = the
+ *                     counted taps, L = the rank-th largest counted luminance.  n < rank: untouched.  limit = max(threshold L, floor); l_p > limit:
+ *                     rgb is multiplied by limit / l_p, alpha kept (CLAMPED); otherwise untouched — a NaN centre too.  A hit with n >= rank is
+ *                     CONSIDERED.  No guard beyond that: a +inf centre over a finite limit gets 0 in its finite channels and NaN in its infinite
+ *                     ones.  The arithmetic is csrc/firefly.hpp's firefly_pixel.
+ *   two limits        The clamp REMOVES energy — it is a bias: the mean of the filtered images lies below the unfiltered mean.  And an emitter ONE
+ *                     pixel wide has no neighbour as bright as itself: it is dimmed to threshold x its surroundings; floor is the lever for that —
+ *                     nothing at or below floor is ever touched.
+ *   what survives     the accumulation image (vpt_get_radiance) keeps its bits: the pass writes an image of its own.  vpt_stats is untouched.
+ *   vpt_get_firefly_state  of the latest filtered call: clamped and considered pixels, and the filtered calls since mode went to 1.  VPT_OK with
+ *                     zeros before the first filtered call of the current size.
+ *   vpt_get_firefly_image  the filtered image of the latest filtered call, width*height*4 floats; VPT_ERR_INVALID_ARGUMENT before the first one
+ *                     of the current size.  Both read-backs wait for the work in flight.
+ *   memory            16 B per pixel and 8 KB of counters: allocated by the first filtered call, re-made after vpt_resize, freed by vpt_destroy.
+ *   sharded contexts  vpt_denoise's rule: the calls need vpt_assemble_shards first and filter the whole image.
+ *   errors            VPT_ERR_INVALID_ARGUMENT for a NULL argument, mode > 1, a radius outside 1..2, a rank outside 1..3 (every window holds at
+ *                     least 8 taps, so no rank in range exceeds it), a threshold that is not finite or below 1, a floor that is not finite or below
+ *                     0, a non-zero reserved word.  A refused call changes nothing. */
+typedef struct vpt_firefly_options {
+    uint32_t mode;         /* 0 (default): off — every call returns the bits it returned before; nothing allocated or launched.  1: on */
+    uint32_t radius;       /* 1..2; default 1 (3 x 3) */
+    uint32_t rank;         /* 1..3; default 2 */
+    float    threshold;    /* default 2; finite, >= 1 */
+    float    floor;        /* default 1 (radiance units, like sigma_color); finite, >= 0 */
+    uint32_t reserved[3];  /* 0 */
+} vpt_firefly_options;
+typedef struct vpt_firefly_state {
+    uint64_t clamped;      /* pixels the latest filtered call scaled down */
+    uint64_t considered;   /* hit pixels with at least rank counted neighbours */
+    uint32_t calls;        /* filtered calls since mode went to 1 */
+    uint32_t reserved;
+} vpt_firefly_state;
+void vpt_default_firefly_options(vpt_firefly_options* out);   /* mode 0, radius 1, rank 2, threshold 2, floor 1 */
+int vpt_set_firefly_options(vpt_ctx* ctx, const vpt_firefly_options* options);
+int vpt_get_firefly_options(const vpt_ctx* ctx, vpt_firefly_options* out);
+int vpt_get_firefly_state(vpt_ctx* ctx, vpt_firefly_state* out);
+int vpt_get_firefly_image(vpt_ctx* ctx, float* rgba_host);    /* width*height*4 floats */
+
 /* ---- the temporal history across instance moves -------------------------------------------------------------------------------------
  * The loop of an animated viewport:
  *     vpt_set_instance_transforms -> vpt_set_base_seed(frame_index) -> vpt_render(k) -> vpt_temporal_accumulate -> vpt_denoise -> vpt_postprocess

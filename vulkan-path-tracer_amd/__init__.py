@@ -17,6 +17,7 @@ from ._abi import default_denoise_params, DENOISE_DEMODULATE, DENOISE_MAX_ITERAT
 from ._abi import default_temporal_params, TEMPORAL_DEMODULATE, TEMPORAL_MATCH_INSTANCE, DENOISE_SOURCE_RADIANCE, DENOISE_SOURCE_TEMPORAL  # noqa: F401
 from ._abi import SvgfOptions, default_svgf_options  # noqa: F401
 from ._abi import SvgfSpatialOptions, default_svgf_spatial_options  # noqa: F401
+from ._abi import FireflyOptions, FireflyState, default_firefly_options  # noqa: F401
 from ._abi import TemporalOptions, default_temporal_options  # noqa: F401
 from ._abi import ExposureOptions, ExposureState, default_exposure_options, EXPOSURE_BINS  # noqa: F401
 
@@ -452,6 +453,37 @@ class PathTracer:
         """vpt_get_temporal_moments: first and second luminance moment of the latest temporal result made with variance = 1 -> float32 [h, w, 2]."""
         out = np.empty((self.height, self.width, 2), np.float32)
         _check(self.lib, self.ctx, self.lib.vpt_get_temporal_moments(self.ctx, out.ctypes.data), "vpt_get_temporal_moments")
+        return out
+
+    # ---- outlier rejection ahead of the two filters (include/vpt.h vpt_set_firefly_options / vpt_get_firefly_options / vpt_get_firefly_state / vpt_get_firefly_image)
+    def set_firefly_options(self, **kw):
+        """vpt_set_firefly_options: the context's options with the fields given replaced (mode, radius, rank, threshold, floor).  With mode = 1
+        temporal_accumulate and denoise (from the radiance source) first scale down every hit pixel whose luminance exceeds max(threshold * the rank-th largest
+        of its neighbours, floor) and filter that image; the accumulation image keeps its bits.  A bias: the clamp removes energy.  Keeps the history."""
+        o = self.firefly_options()
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        _check(self.lib, self.ctx, self.lib.vpt_set_firefly_options(self.ctx, C.byref(o)), "vpt_set_firefly_options")
+
+    def firefly_options(self):
+        """vpt_get_firefly_options -> FireflyOptions."""
+        o = _abi.FireflyOptions()
+        _check(self.lib, self.ctx, self.lib.vpt_get_firefly_options(self.ctx, C.byref(o)), "vpt_get_firefly_options")
+        return o
+
+    def firefly_state(self):
+        """vpt_get_firefly_state -> FireflyState of the latest filtered call (waits for the work in flight): clamped and considered pixels, filtered calls
+        since mode went to 1.  Zeros before the first filtered call of the current size."""
+        s = _abi.FireflyState()
+        _check(self.lib, self.ctx, self.lib.vpt_get_firefly_state(self.ctx, C.byref(s)), "vpt_get_firefly_state")
+        return s
+
+    def firefly_image(self):
+        """vpt_get_firefly_image: the image the latest filtered call handed to its filter -> float32 [h, w, 4]."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _check(self.lib, self.ctx, self.lib.vpt_get_firefly_image(self.ctx, out.ctypes.data), "vpt_get_firefly_image")
         return out
 
     # ---- the temporal history across instance moves (include/vpt.h vpt_set_temporal_options / vpt_get_temporal_options / vpt_get_temporal_motion)

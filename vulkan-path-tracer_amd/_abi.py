@@ -281,6 +281,24 @@ def default_svgf_spatial_options(**kw):
     return p
 
 
+class FireflyOptions(C.Structure):  # vpt_firefly_options
+    _fields_ = [("mode", C.c_uint32), ("radius", C.c_uint32), ("rank", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class FireflyState(C.Structure):  # vpt_firefly_state
+    _fields_ = [("clamped", C.c_uint64), ("considered", C.c_uint64), ("calls", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def default_firefly_options(**kw):
+    """vpt_default_firefly_options: mode off, radius 1 (3 x 3), rank 2, threshold 2, floor 1."""
+    p = FireflyOptions(0, 1, 2, 2.0, 1.0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 class TemporalOptions(C.Structure):  # vpt_temporal_options
     _fields_ = [("instance_motion", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
@@ -388,6 +406,11 @@ PROTOTYPES = {
     "vpt_default_svgf_spatial_options": (None, [C.POINTER(SvgfSpatialOptions)]),
     "vpt_set_svgf_spatial_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfSpatialOptions)]),
     "vpt_get_svgf_spatial_options": (C.c_int, [C.c_void_p, C.POINTER(SvgfSpatialOptions)]),
+    "vpt_default_firefly_options": (None, [C.POINTER(FireflyOptions)]),
+    "vpt_set_firefly_options": (C.c_int, [C.c_void_p, C.POINTER(FireflyOptions)]),
+    "vpt_get_firefly_options": (C.c_int, [C.c_void_p, C.POINTER(FireflyOptions)]),
+    "vpt_get_firefly_state": (C.c_int, [C.c_void_p, C.POINTER(FireflyState)]),
+    "vpt_get_firefly_image": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_get_temporal_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_get_temporal_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vpt_default_temporal_options": (None, [C.POINTER(TemporalOptions)]),

@@ -13,13 +13,14 @@ LIB = os.path.join(HERE, "libvpt_hip.so")
 # The LABORATORY build: the same sources with -DVPT_LAB=1 plus LAB_SOURCES — every kernel variant that was measured against the product kernels and found
 # slower, round 1's stage kernels (VPT_PIPELINE_STAGED_R1) and the vpt_lab_* entry points of include/vpt_lab.h (api_lab.hip).  The product library has none of it.
 LIB_LAB = os.path.join(HERE, "libvpt_hip_lab.so")
-SOURCES = ["kernels_whole.hip", "kernels_bounce.hip", "kernels_trace.hip", "kernels_stream.hip", "kernels_media.hip", "kernels_post.hip",
+SOURCES = ["kernels_whole.hip", "kernels_bounce.hip", "kernels_trace.hip", "kernels_stream.hip", "kernels_post.hip",
            "api_context.hip", "api_scene.hip", "api_render.hip", "api_post.hip", "api_comm.hip", "bvh_build.cpp"]   # (the api_*.hip files hold no kernel: no fat binary, no per-file flag)
 LAB_SOURCES = ["kernels_lab_r1.hip", "api_lab.hip"]   # compiled and linked into the laboratory library only
 # (kernels_lut.hip is a header here: kernels_post.hip includes it — the two share their flags, and one fat binary with its page padding less is 10 KB of the
 # product's size bound, DESIGN.md "Library size"; kernels_finish.hip likewise inside kernels_stream.hip and kernels_aux.hip inside kernels_trace.hip, each pair
-# with -fno-slp-vectorize on both sides: 8 KB each, the room auto-exposure needed)
-HEADERS = ["kernels_lut.hip", "kernels_finish.hip", "kernels_aux.hip", "exposure.hpp", "post_plan.hpp", "device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "grid_prep.hpp", "denoise.hpp", "temporal.hpp", "svgf_spatial.hpp", "kernels.hpp", "api_ctx.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "bvh_refit.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "wave_cursor.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp", "node_step.hpp", "whole_refill.hpp", "whole_args.hpp", "whole_deal.hpp", "camera.hpp", "camera_cull.hpp",
+# with -fno-slp-vectorize on both sides: 8 KB each, the room auto-exposure needed; kernels_media.hip inside kernels_bounce.hip on the same terms: 12 KB, the
+# firefly filter's room)
+HEADERS = ["kernels_lut.hip", "kernels_finish.hip", "kernels_aux.hip", "kernels_media.hip", "firefly.hpp", "exposure.hpp", "post_plan.hpp", "device_types.hpp", "path_plan.hpp", "scene_prep.hpp", "grid_prep.hpp", "denoise.hpp", "temporal.hpp", "svgf_spatial.hpp", "kernels.hpp", "api_ctx.hpp", "shading.hpp", "traverse.hpp", "bvh_build.hpp", "bvh_refit.hpp", "volume.hpp", "atmosphere.hpp", "wave.hpp", "wave_cursor.hpp", "shade_core.hpp", "vote.hpp", "slab.hpp", "node_step.hpp", "whole_refill.hpp", "whole_args.hpp", "whole_deal.hpp", "camera.hpp", "camera_cull.hpp",
            os.path.join("..", "..", "include", "vpt.h"), os.path.join("..", "..", "include", "vpt_lab.h"), os.path.join("..", "..", "include", "vpt_fp32.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-result", "-Wno-pass-failed"]

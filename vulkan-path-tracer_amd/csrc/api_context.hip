@@ -45,6 +45,8 @@ void free_render_buffers(vpt_ctx* c) {
     c->post_out = nullptr; c->post_w = c->post_h = 0;
     free_denoise_buffers(c);
     free_temporal_buffers(c);
+    if (c->ff_block) (void)hipFree(c->ff_block);   // the firefly filter's image and counters: re-made by the next filtered call
+    c->ff_block = nullptr; c->ff_w = c->ff_h = 0; c->ff_valid = false;
 }
 
 // Size checks of a (width, height) before anything is freed or changed; *frames_out = the largest batch this context will render.

@@ -248,6 +248,13 @@ struct vpt_ctx {
     bool sv_valid = false;           // the latest temporal result was made with the option on: moments tp_latest and the variance image go with it
     // ... and its spatial estimate for young pixels (vpt_set_svgf_spatial_options): state only, no memory; ignored while svgf.variance is 0
     vpt_svgf_spatial_options sv_spatial{0u, 3u, 0.1f, 0.05f, 4.0f, {0u, 0u, 0u}};
+    // outlier rejection ahead of the two filters (vpt_set_firefly_options): nothing of this is allocated or launched while mode is 0
+    vpt_firefly_options ff_options{0u, 1u, 2u, 2.0f, 1.0f, {0u, 0u, 0u}};
+    float* ff_block = nullptr;       // one allocation: the filtered image (RGBA32F of ff_w x ff_h) | firefly::kCounterBytes of counter pairs (clamped, considered); made by the first filtered
+                                     // call, re-made for another size, freed with the render buffers (vpt_resize, vpt_destroy)
+    uint32_t ff_w = 0, ff_h = 0;     // size the block was made for
+    bool ff_valid = false;           // the block holds the latest filtered call's image and counts
+    uint32_t ff_calls = 0;           // filtered calls since mode went to 1
     // moved instances (vpt_set_temporal_options): nothing of this is allocated, kept or uploaded while instance_motion is 0
     vpt_temporal_options tp_options{0u, {0u, 0u, 0u}};
     temporal::MotionSnapshot tp_snapshot;   // the matrices, at the latest record, of the instances moved since: only while a history is there to carry

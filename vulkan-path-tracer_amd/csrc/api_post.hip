@@ -4,6 +4,7 @@
 //   vpt_denoise               the edge-avoiding a-trous filter over first-hit guides, variance-guided with vpt_svgf_options.variance
 //   vpt_temporal_accumulate   the image carried across camera and instance moves: the two records, SVGF's luminance moments and variance, the per-instance
 //                             motion tables and the motion image, with their options and read-backs
+//   vpt_set_firefly_options   outlier rejection ahead of the two calls above: enqueue_firefly queues k_firefly between their guides and their own first launch
 #include "api_ctx.hpp"
 
 using namespace vpt::api;
@@ -90,6 +91,28 @@ int post_source_ready(vpt_ctx* c) {
     return VPT_OK;
 }
 
+// ---- vpt_firefly_options: the pass ahead of a filter.  *image is the filter's source on entry; with the option on, k_firefly is queued on it — reading the
+// consuming call's guides, which enqueue_first_hit has just queued — and *image becomes the filtered copy.  The source itself is never written.
+bool firefly_ready(const vpt_ctx* c) { return c->ff_valid && c->ff_w == c->P.width && c->ff_h == c->P.height; }
+int enqueue_firefly(vpt_ctx* c, const float** image, const float* albedo, const float* depth, bool demodulate) {
+    if (!c->ff_options.mode) return VPT_OK;
+    const uint32_t w = c->P.width, h = c->P.height;
+    const size_t npx = (size_t)w * h;
+    if (!(c->ff_block && c->ff_w == w && c->ff_h == h)) {
+        if (c->ff_block) (void)hipFree(c->ff_block);
+        c->ff_block = nullptr; c->ff_valid = false;
+        HIPCHK(c, hipMalloc((void**)&c->ff_block, npx * 16 + firefly::kCounterBytes));   // the image, then the counter pairs
+        c->ff_w = w; c->ff_h = h;
+    }
+    uint32_t* counters = (uint32_t*)(c->ff_block + npx * 4);
+    const vpt_firefly_options& o = c->ff_options;
+    HIPCHK(c, hipMemsetAsync(counters, 0, firefly::kCounterBytes, c->main.stream));
+    launch_firefly(c->main.stream, *image, demodulate ? albedo : nullptr, depth, c->ff_block, counters, w, h, firefly::plan_of(o.radius, o.rank, o.threshold, o.floor, demodulate));
+    *image = c->ff_block;
+    c->ff_valid = true; c->ff_calls++;
+    return VPT_OK;
+}
+
 // ---- vpt_denoise
 int check_denoise(vpt_ctx* c, const vpt_denoise_params* dp, const void* device_out) {
     if (!c || !dp) return VPT_ERR_INVALID_ARGUMENT;
@@ -132,6 +155,8 @@ int enqueue_denoise(vpt_ctx* c, const vpt_denoise_params* dp) {
         a.mode = VPT_FEATURES_CENTER;
         a.depth = c->dn_depth; a.normal = (float4*)c->dn_guide; a.albedo = (float4*)c->dn_albedo;
         enqueue_first_hit(c, a);
+        // (the temporal image was filtered ahead of the history: not again)
+        if (c->denoise_source == VPT_DENOISE_SOURCE_RADIANCE && (rc = enqueue_firefly(c, &src, c->dn_albedo, c->dn_depth, demodulate))) return rc;
         launch_denoise_prepare(s, src, c->dn_depth, c->dn_albedo, c->dn_guide, c->dn_ping, W, H, demodulate, variance ? c->sv_variance : nullptr);
         const float* in = c->dn_ping;
         for (uint32_t i = 0; i < dp->iterations; i++) {
@@ -237,7 +262,9 @@ int enqueue_temporal(vpt_ctx* c, const vpt_temporal_params* tp) {
     f.have_prev = (history && c->tp_camera.ok) ? 1u : 0u;
     f.m = (float)c->frame_count; f.max_history = (float)tp->max_history;
     f.depth_tolerance = tp->depth_tolerance; f.normal_threshold = tp->normal_threshold; f.flags = tp->flags;
-    launch_temporal(c->main.stream, whole_image(c), c->tp_depth, c->tp_albedo, c->tp_ids, c->tp_hist[prev], c->tp_guide[prev], c->tp_inst[prev],
+    const float* cur = whole_image(c);
+    if ((rc = enqueue_firefly(c, &cur, c->tp_albedo, c->tp_depth, (tp->flags & VPT_TEMPORAL_DEMODULATE) != 0))) return rc;
+    launch_temporal(c->main.stream, cur, c->tp_depth, c->tp_albedo, c->tp_ids, c->tp_hist[prev], c->tp_guide[prev], c->tp_inst[prev],
                     c->tp_hist[next], c->tp_guide[next], c->tp_inst[next], c->tp_out, f, variance ? c->sv_moments[prev] : nullptr, variance ? c->sv_moments[next] : nullptr,
                     variance ? c->sv_variance : nullptr, (float)c->svgf.min_history * f.m, motion_table, (uint32_t)c->instances.size(), motion ? c->tp_motion : nullptr);
     if (variance && c->sv_spatial.mode)   // the young pixels' variance from their neighbourhood, on the record just written: the variance image alone changes
@@ -367,6 +394,46 @@ int vpt_set_svgf_spatial_options(vpt_ctx* c, const vpt_svgf_spatial_options* o) 
 int vpt_get_svgf_spatial_options(const vpt_ctx* c, vpt_svgf_spatial_options* o) {
     if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
     *o = c->sv_spatial;
+    return VPT_OK;
+}
+// ---- outlier rejection ahead of the two filters: validated and stored; enqueue_temporal and enqueue_denoise act on it.  No record is touched, so the history stays.
+static_assert(sizeof(vpt_firefly_options) == sizeof(firefly::Options), "firefly.hpp mirrors include/vpt.h");
+void vpt_default_firefly_options(vpt_firefly_options* o) {
+    const firefly::Options d = firefly::default_options();
+    if (o) memcpy(o, &d, sizeof d);
+}
+int vpt_set_firefly_options(vpt_ctx* c, const vpt_firefly_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    firefly::Options n;
+    memcpy(&n, o, sizeof n);
+    if (const char* why = firefly::check_options(n)) return fail(c, VPT_ERR_INVALID_ARGUMENT, why);
+    if (o->mode && !c->ff_options.mode) c->ff_calls = 0;
+    c->ff_options = *o;
+    return VPT_OK;
+}
+int vpt_get_firefly_options(const vpt_ctx* c, vpt_firefly_options* o) {
+    if (!c || !o) return VPT_ERR_INVALID_ARGUMENT;
+    *o = c->ff_options;
+    return VPT_OK;
+}
+int vpt_get_firefly_state(vpt_ctx* c, vpt_firefly_state* out) {
+    if (!c || !out) return VPT_ERR_INVALID_ARGUMENT;
+    *out = vpt_firefly_state{0u, 0u, 0u, 0u};
+    if (!firefly_ready(c)) return VPT_OK;
+    int rc = settle_for_readback(c);
+    if (rc) return rc;
+    uint32_t n[firefly::kCounterSlots * firefly::kCounterStride];
+    HIPCHK(c, hipMemcpy(n, c->ff_block + (size_t)c->ff_w * c->ff_h * 4, sizeof n, hipMemcpyDeviceToHost));
+    out->calls = c->ff_calls;
+    for (uint32_t k = 0; k < firefly::kCounterSlots; k++) { out->clamped += n[k * firefly::kCounterStride]; out->considered += n[k * firefly::kCounterStride + 1u]; }
+    return VPT_OK;
+}
+int vpt_get_firefly_image(vpt_ctx* c, float* rgba_host) {
+    if (!c || !rgba_host) return VPT_ERR_INVALID_ARGUMENT;
+    if (!firefly_ready(c)) return fail(c, VPT_ERR_INVALID_ARGUMENT, "no filtered image of this size: run a filtered call with vpt_firefly_options.mode == 1 first");
+    int rc = settle_for_readback(c);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(rgba_host, c->ff_block, (size_t)c->ff_w * c->ff_h * 16, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
 int vpt_get_temporal_variance(vpt_ctx* c, float* var_host) { return read_variance_result(c, var_host, false); }

@@ -5,6 +5,7 @@
 #include "denoise.hpp"
 #include "temporal.hpp"
 #include "svgf_spatial.hpp"
+#include "firefly.hpp"
 #include "exposure.hpp"
 #include "post_plan.hpp"
 #include "whole_deal.hpp"   // + camera_cull.hpp
@@ -179,5 +180,10 @@ void launch_temporal(hipStream_t s, const float* cur, const float* depth, const 
 // (packed F4), moments (two floats) and hist (F4, whose .w is the length) per pixel.  `variance` is rewritten in place at the young hit pixels (length below
 // min_len) and nowhere else; a block whose 64 x 4 tile holds none returns before it reads a neighbour.
 void launch_variance_spatial(hipStream_t s, const float* guide, const float* moments, const float* hist, float* variance, uint32_t w, uint32_t h, const svgf_spatial::Plan& plan, float min_len);
+// vpt_firefly_options (firefly.hpp holds the arithmetic): one launch over w x h AHEAD of launch_temporal / launch_denoise_prepare, which are then handed `out`
+// for their image.  cur, albedo, out: RGBA32F; depth: one float per pixel — the consuming call's first-hit guides.  albedo == nullptr: the consuming call does
+// not demodulate and nothing is read through it (plan.demodulate follows the pointer).  cur is never written.  counters: firefly::kCounterBytes of device memory, kCounterSlots pairs
+// (clamped, considered) kCounterStride words apart, each block adding into one of them: the caller zeroes them ahead of the launch, on the same stream, and sums them.
+void launch_firefly(hipStream_t s, const float* cur, const float* albedo, const float* depth, float* out, uint32_t* counters, uint32_t w, uint32_t h, const firefly::Plan& plan);
 
 }  // namespace vpt

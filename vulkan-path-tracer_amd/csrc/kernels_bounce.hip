@@ -333,3 +333,6 @@ int bounce_blocks_per_cu(bool lds_scene, const DeviceScene& sc, bool plain) {
 }
 
 }  // namespace vpt
+
+// The media stages' kernels ride in this translation unit (same flags; one fat binary and its page padding less: DESIGN.md "Library size").
+#include "kernels_media.hip"

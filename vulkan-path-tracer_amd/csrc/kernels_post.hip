@@ -737,6 +737,61 @@ void launch_variance_spatial(hipStream_t s, const float* guide, const float* mom
                        reinterpret_cast<const dn::F4*>(hist), variance, (int)w, (int)h, plan, min_len);
 }
 
+// ---- vpt_firefly_options (api_post.hip enqueue_temporal / enqueue_denoise, ahead of k_temporal / k_denoise_prepare): firefly.hpp's firefly_pixel does all the
+// arithmetic; the kernel only decides where a luminance is read from, so the device gives the bits of the host compile (tests/test_gpu_firefly.py).  The
+// 64 x 4 tile, a wave per row.  The window needs ONE float per neighbour: every thread computes staged_luminance for its share of the tile plus a halo of
+// `radius` pixels — at most 68 x 8 floats = 2,176 B — from cur, depth and (demodulating only: the pointer is null otherwise and nothing is read through it)
+// albedo, and after one barrier, which every thread reaches, the window is read from LDS.
+// LDS banks: a wave reads 64 CONSECUTIVE words of a tile row for every tap — the tap offset is the same for all lanes; ds_read_b32 is served in two halves of
+// 32 lanes, bank = dword address mod 32 (k_variance_spatial's rule for its narrower reads): 32 consecutive words are the 32 banks, each once, whatever the row
+// pitch.  No padding is needed and none is there.
+// The image is written to `out`, never in place: the accumulation image keeps its bits.  Clamped and considered pixels (hits with n >= rank) are counted per
+// wave — a ballot's popcount — and added by one global atomic per wave and count that has something to add, into the block's pair of firefly.hpp's
+// kCounterSlots pairs (which says why there is more than one): integer sums, the same whatever order they arrive in.  The host zeroes the pairs ahead of the
+// launch and sums them when the state is read.
+namespace ff = firefly;
+constexpr int kFfTW = kTileW + 2 * ff::kMaxRadius, kFfTH = kTileH + 2 * ff::kMaxRadius;   // 68 x 8
+struct FfTileSrc {
+    const float (&l)[kFfTW * kFfTH]; int ox, oy;   // image position of tile entry (0, 0)
+    __device__ __forceinline__ float lum(int x, int y) const { return l[(y - oy) * kFfTW + (x - ox)]; }
+};
+__global__ __launch_bounds__(256) void k_firefly(const dn::F4* cur, const dn::F4* albedo, const float* depth, dn::F4* out, uint32_t* counters, int w, int h, ff::Plan plan) {
+    __shared__ float s_l[kFfTW * kFfTH];
+    const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
+    const int halo = plan.radius;   // <= kMaxRadius (the host's check)
+    const int tw = kTileW + 2 * halo, th = kTileH + 2 * halo;
+    const dn::F4 none = dn::f4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int i = threadIdx.x; i < tw * th; i += 256) {
+        const int ty = i / tw, tx = i - ty * tw;
+        const int gx = x0 - halo + tx, gy = y0 - halo + ty;
+        if (gx < 0 || gx >= w || gy < 0 || gy >= h) continue;   // never read: firefly_pixel skips taps outside the image
+        const size_t q = (size_t)gy * w + gx;
+        s_l[ty * kFfTW + tx] = ff::staged_luminance(cur[q], albedo ? albedo[q] : none, depth[q], albedo != nullptr);
+    }
+    __syncthreads();
+    const int x = x0 + (int)(threadIdx.x & 63u), y = y0 + (int)(threadIdx.x >> 6);
+    bool clamped = false, considered = false;
+    if (x < w && y < h) {
+        const size_t p = (size_t)y * w + x;
+        const FfTileSrc src{s_l, x0 - halo, y0 - halo};
+        const ff::Result r = ff::firefly_pixel(src, x, y, w, h, plan, cur[p], albedo ? albedo[p] : none, depth[p]);
+        out[p] = r.pixel;
+        clamped = r.clamped; considered = r.considered;
+    }
+    const unsigned long long bc = __ballot(clamped), bk = __ballot(considered);   // (every lane of the wave is here)
+    if ((threadIdx.x & 63u) == 0u) {
+        uint32_t* mine = counters + ((blockIdx.y * gridDim.x + blockIdx.x) & (ff::kCounterSlots - 1u)) * ff::kCounterStride;
+        if (bc) atomicAdd(&mine[0], (uint32_t)__popcll(bc));
+        if (bk) atomicAdd(&mine[1], (uint32_t)__popcll(bk));
+    }
+}
+void launch_firefly(hipStream_t s, const float* cur, const float* albedo, const float* depth, float* out, uint32_t* counters, uint32_t w, uint32_t h, const firefly::Plan& plan) {
+    firefly::Plan p = plan;
+    p.demodulate = albedo ? 1 : 0;   // one fact, said once: the staged luminances and the centre's demodulate alike
+    hipLaunchKernelGGL(k_firefly, dim3(cdiv_(w, kTileW), cdiv_(h, kTileH)), dim3(256), 0, s, reinterpret_cast<const dn::F4*>(cur), reinterpret_cast<const dn::F4*>(albedo), depth,
+                       reinterpret_cast<dn::F4*>(out), counters, (int)w, (int)h, p);
+}
+
 void launch_bloom_threshold(hipStream_t s, const float* in, float* out, uint32_t w, uint32_t h, float threshold, float falloff) {
     uint32_t n = w * h;
     hipLaunchKernelGGL(k_bloom_threshold, dim3(cdiv_(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(in), reinterpret_cast<float4*>(out), n, threshold, falloff);

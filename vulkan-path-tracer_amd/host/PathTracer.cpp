@@ -322,6 +322,16 @@ void PathTracer::SetSvgfSpatialOptions(const vpt_svgf_spatial_options& options) 
     if (!m_Ctx) throw std::runtime_error("SetSvgfSpatialOptions before SetScene");
     Check(vpt_set_svgf_spatial_options(m_Ctx, &options), "vpt_set_svgf_spatial_options");
 }
+void PathTracer::SetFireflyFilter(const vpt_firefly_options& options) {
+    if (!m_Ctx) throw std::runtime_error("SetFireflyFilter before SetScene");
+    Check(vpt_set_firefly_options(m_Ctx, &options), "vpt_set_firefly_options");
+}
+vpt_firefly_state PathTracer::GetFireflyState() {
+    if (!m_Ctx) throw std::runtime_error("GetFireflyState before SetScene");
+    vpt_firefly_state s{};
+    Check(vpt_get_firefly_state(m_Ctx, &s), "vpt_get_firefly_state");
+    return s;
+}
 void PathTracer::SetTemporalOptions(const vpt_temporal_options& options) {
     if (!m_Ctx) throw std::runtime_error("SetTemporalOptions before SetScene");
     Check(vpt_set_temporal_options(m_Ctx, &options), "vpt_set_temporal_options");

@@ -215,6 +215,11 @@ public:
     // EXTENSION: SVGF's spatial variance estimate for pixels whose history is too short (vpt_set_svgf_spatial_options); keeps the temporal history.
     static vpt_svgf_spatial_options DefaultSvgfSpatialOptions() { vpt_svgf_spatial_options o; vpt_default_svgf_spatial_options(&o); return o; }
     void SetSvgfSpatialOptions(const vpt_svgf_spatial_options& options);
+    // EXTENSION: outlier ("firefly") rejection ahead of TemporalAccumulate and Denoise (vpt_set_firefly_options); keeps the temporal history.  The clamp removes
+    // energy (a bias), and an emitter one pixel wide is dimmed to threshold x its surroundings: floor is the lever.  GetFireflyState: the latest filtered call's counts.
+    static vpt_firefly_options DefaultFireflyOptions() { vpt_firefly_options o; vpt_default_firefly_options(&o); return o; }
+    void SetFireflyFilter(const vpt_firefly_options& options);
+    [[nodiscard]] vpt_firefly_state GetFireflyState();
     // EXTENSION: the temporal history carried across instance moves (vpt_set_temporal_options); context state, so after SetScene like SetSvgfOptions.
     // GetTemporalMotion: width*height*2 floats of the latest TemporalAccumulate made with instance_motion == 1.
     static vpt_temporal_options DefaultTemporalOptions() { vpt_temporal_options o; vpt_default_temporal_options(&o); return o; }

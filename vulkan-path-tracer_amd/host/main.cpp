@@ -7,6 +7,8 @@
 //                               PREFIX_normal.png (n * 0.5 + 0.5) and PREFIX_albedo.png, each clamped to [0, 1], (uint8)(v * 255 + 0.5), alpha 255
 //              [--denoise [ITERATIONS]]   PathTracer::Denoise with the default parameters (ITERATIONS 0..6, default 5) after the render; --ppm / --png then come
 //                                         from the denoised image through the normal post chain (SetPostSource(VPT_POST_SOURCE_DENOISED))
+//              [--firefly]   with --denoise: PathTracer::SetFireflyFilter with the default parameters, on, ahead of the Denoise call — outlier pixels are clamped to
+//                            twice the second-largest luminance of their 3 x 3 neighbourhood (never below 1) before the filter reads them; the counts are printed
 //              [--auto-exposure]   PostProcessor::SetAutoExposureData with both rates 1 before the final PostProcess: the exposure is metered from the image (a
 //                                  still: the one metering jumps to its target) instead of the constant 1; the adapted state is printed
 //              [--env-late]   apply --env-constant / --env-hdr after SetScene instead of before (the Editor's order of calls: the map is swapped on the installed scene)
@@ -49,7 +51,7 @@ int main(int argc, char** argv) {
     std::vector<PathTracer::Volume> volumes; std::vector<std::pair<uint32_t, std::string>> brickFiles; int phase = 0; bool atmosphere = false; float sunAlt = 0.0f, sunAz = 0.0f;
     uint32_t lutSamples = 10000000u, lutTime = 0; UVec3 lutSize{0, 0, 0};
     uint32_t w = 0, h = 0, spp = 16, depth = 8, seed = 1, split = 1, gpus = 1; std::vector<int> devices;
-    bool async = false, rayQueries = true, envLate = false, autoExposure = false; uint32_t asyncStep = 1; int denoise = -1;
+    bool async = false, rayQueries = true, envLate = false, autoExposure = false, firefly = false; uint32_t asyncStep = 1; int denoise = -1;
     bool info = false, selftest = false; float env[3] = {0, 0, 0}; bool haveEnv = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -80,6 +82,7 @@ int main(int argc, char** argv) {
         else if (a == "--env-hdr") envHdr = next();          // SetEnvMapFilepath
         else if (a == "--env-late") envLate = true;
         else if (a == "--auto-exposure") autoExposure = true;
+        else if (a == "--firefly") firefly = true;
         else if (a == "--dump-env") dumpEnv = next();        // with --env-hdr: decoded RGBA32F (no device needed)
         else if (a == "--decode-image") decodeImage = next(); // with --dump-image: a PNG / JPEG texture as the importer decodes it, raw RGBA8 (no device needed)
         else if (a == "--dump-image") dumpImage = next();
@@ -266,7 +269,12 @@ int main(int argc, char** argv) {
         const std::vector<float>& img = pt.GetOutputImage();
         if (denoise >= 0) {   // the post chain reads the denoised image; --radiance stays the accumulation image
             vpt_denoise_params dp; vpt_default_denoise_params(&dp); dp.iterations = (uint32_t)denoise;
+            if (firefly) { vpt_firefly_options fo = PathTracer::DefaultFireflyOptions(); fo.mode = 1; pt.SetFireflyFilter(fo); }
             (void)pt.Denoise(dp, false);
+            if (firefly && denoise > 0) {
+                const vpt_firefly_state fs = pt.GetFireflyState();
+                printf("firefly filter: %llu of %llu pixels clamped\n", (unsigned long long)fs.clamped, (unsigned long long)fs.considered);
+            }
             pt.SetPostSource(VPT_POST_SOURCE_DENOISED);
         }
         if (autoExposure) {
